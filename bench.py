@@ -1,8 +1,15 @@
 """Benchmark: the README AdAnalytics filtered GROUP BY (BASELINE.json configs[2], C3) on synthetic segments
 pinned in HBM, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload adanalytics|c1|c2|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload adanalytics|c1|c2|c4|c5] [--dump-outputs DIR]
+    python bench.py --full ...
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it pins the segments, warms up, times the K steps,
+writes the last step's result with --dump-outputs, and prints the result line.  --full adds, after the timed region,
+everything else the line can carry: the serialized per-query latency, the scan kernel's duration and the roofline
+(bytes_alg pass, rocprofv3 FETCH_SIZE child runs), the full-size parity check against the oracle and the CPU
+baseline (--no-pmc, --no-bytes, --no-cpu-baseline, --parity-segments trim those); without it their fields are null.
 
 --gpus N > 1 without a launcher starts the N rank processes itself (before this process touches the GPU) and exits
 with the first failing rank's code; under a launcher WORLD_SIZE must equal --gpus.  RCCL takes one GPU per rank, so
@@ -15,7 +22,8 @@ across the ranks (strong scaling: C3 = 1 000 segments of 1M docs = 1B rows over 
 1/2/4/8 GPUs"); --segments-per-gpu S instead pins S segments on every rank (weak scaling).  Queries are pipelined
 --inflight deep (default 3, each in flight on its own stream and group table): query k+1 is planned and launched
 before query k's result is finalized, as a server overlaps concurrent queries -- the GPU does not idle while the
-host finalizes.  Kernel durations for the roofline come from a separate serialized pass (--inflight 1 semantics).
+host finalizes.  With --full, kernel durations for the roofline come from a separate serialized pass (--inflight 1
+semantics).
 Rank 0 prints one JSON line.
 """
 import argparse
@@ -51,6 +59,13 @@ def parse_args():
                         "queries has passed: the per-step trace of the driver's command shows query time decaying "
                         "750 -> 670 us over the first ~20 ms of load (the GPU's clocks ramping), which a 5-step warm-up "
                         "leaves inside the timed region; 0 = exactly W steps")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline figure does not need: per-query latency, kernel "
+                        "duration and roofline (with the rocprofv3 traffic passes), parity against the oracle, the CPU "
+                        "baseline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's result (what the caller of the query "
+                        "receives) as DIR/<name>.npy, float64 (see dump_outputs)")
     p.add_argument("--workload", default="adanalytics")
     p.add_argument("--sql", default=None, help="override the workload's query (same table)")
     p.add_argument("--rows-total", type=int, default=None,
@@ -87,6 +102,53 @@ def parse_config(text):
         k, _, v = item.partition("=")
         out[k.strip()] = float(v) if "." in v else int(v)
     return out
+
+
+DUMP_MAX_BYTES = 48 << 20  # of all the arrays of one --dump-outputs directory together
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(dirname, table, query, res, rank=0, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the GroupByResult of the last timed query as float64 arrays, rows in ascending key order (the
+    C result's order depends on the group-by path; the sort makes two builds comparable row for row):
+      keys.npy        [n, num_group_by]  group keys in value space (a STRING column: its table-global dictIds)
+      values.npy      [num_aggs, n]      aggregation results (AVG: the sum of its pair)
+      avg_counts.npy  [num_aggs, n]      the AVG pairs' counts (only when the query has an AVG)
+      stats.npy       [5]                numDocsScanned, numEntriesScannedInFilter, numEntriesScannedPostFilter,
+                                         numTotalDocs, number of groups of the whole result
+    A result whose arrays would pass `max_bytes` is cut to a fixed sample of its rows (seeded choice of positions in
+    key order, the same for every run of the same query).  The data is generated from the row number, so the same
+    arguments give the same inputs in every run.  Rank r > 0 of a multi-rank run writes <name>.rank<r>.npy (its share
+    of a sharded combine, the merged table otherwise)."""
+    from pinot_amd import _lib as L
+    n = len(res)
+    dicts, gids, aggs, _ = res._col  # the columnar form GroupByResult.keys / .values are built from
+    keys = np.zeros((n, len(gids)), dtype=np.float64)
+    for j, (c, g) in enumerate(zip(query.group_by, gids)):
+        if not n:
+            continue
+        if table.types[table.index[c]] in (L.INT, L.LONG, L.FLOAT, L.DOUBLE):
+            keys[:, j] = np.asarray(dicts[j], dtype=np.float64)[g]
+        else:
+            keys[:, j] = g
+    values = np.zeros((len(aggs), n), dtype=np.float64)
+    counts = np.zeros((len(aggs), n), dtype=np.float64) if any(c is not None for _, _, _, c in aggs) else None
+    for i, (_, v, e, c) in enumerate(aggs):
+        values[i] = v if v is not None else e
+        if c is not None:
+            counts[i] = c
+    order = np.lexsort(keys.T[::-1]) if keys.shape[1] else np.arange(n)
+    row_bytes = 8 * (keys.shape[1] + len(aggs) * (2 if counts is not None else 1))
+    cap = max(1, (max_bytes - 1024) // max(row_bytes, 1))
+    if n > cap:
+        order = order[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, cap, replace=False))]
+    out = {"keys": keys[order], "values": values[:, order],
+           "stats": np.array(list(res.stats.as_tuple()) + [n], dtype=np.float64)}
+    if counts is not None:
+        out["avg_counts"] = counts[:, order]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + (".rank%d" % rank if rank else "") + ".npy"), np.ascontiguousarray(a))
 
 
 def compulsory_bytes(table, handles, query, docs_per_segment, inverted_columns=()):
@@ -192,10 +254,10 @@ def pmc_traffic(args):
     rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(rocprof) or args.workload not in CALIB_SQL:
         return None
-    base = [sys.executable, "-u", os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-            "--no-pmc", "--workload", args.workload, "--segments-per-gpu", str(args.local_segments),
-            "--docs-per-segment", str(args.docs_per_segment), "--inflight", "1", "--roofline-steps", "2",
-            "--warmup-ms", "0", "--parity-segments", "0"]
+    base = [sys.executable, "-u", os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1",
+            "--no-cpu-baseline", "--no-pmc", "--workload", args.workload,
+            "--segments-per-gpu", str(args.local_segments), "--docs-per-segment", str(args.docs_per_segment),
+            "--inflight", "1", "--roofline-steps", "2", "--warmup-ms", "0", "--parity-segments", "0"]
     if args.num_groups_limit:
         base += ["--num-groups-limit", str(args.num_groups_limit)]
     if args.config:
@@ -533,7 +595,7 @@ def main():
                 pmc = json.load(open(pmc_file))
             except (OSError, ValueError):
                 pmc = None
-    elif rank == 0 and not args.no_pmc and not args.no_bytes:
+    elif rank == 0 and args.full and not args.no_pmc and not args.no_bytes:
         # before this process initialises the GPU: the profiled runs are children, not exec'd (rank 0's share of the
         # segments, profiled as a one-rank run)
         from pinot_amd.build import build as _build
@@ -696,16 +758,17 @@ def main():
         phases["decode"] += dec_us * 1e-6
         return res, k_us
 
-    def run(n, depth, keep=1):
+    def run(n, depth, keep=1, keep_last=False):
         """n queries, at most `depth` in flight; returns (results, kernel timings) in query order.  Only the first
         `keep` results are kept (all with --verify): a server hands each result on and frees it, and holding more of
-        them (C5: 51 MB of pinned host memory each) would grow the result buffer pool inside the timed region."""
+        them (C5: 51 MB of pinned host memory each) would grow the result buffer pool inside the timed region.
+        keep_last: the last query's result is kept too, as the last element (--dump-outputs)."""
         from collections import deque
         pending, res, kus = deque(), [], []
 
         def done(item):
             r, k = complete(item)
-            if keep is None or len(res) < keep:
+            if keep is None or len(res) < keep or (keep_last and len(kus) == n - 1):
                 res.append(r)
             kus.append(k)
 
@@ -752,7 +815,8 @@ def main():
     torch.cuda.synchronize()
     del trace[:]
     t0 = time.perf_counter()
-    timed, _ = run(args.steps, inflight, keep=None if args.verify else (0 if args.warmup else 1))
+    timed, _ = run(args.steps, inflight, keep=None if args.verify else (0 if args.warmup else 1),
+                   keep_last=bool(args.dump_outputs))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -773,6 +837,8 @@ def main():
                 assert all(x == y or abs(x - y) <= 1e-9 * max(abs(x), abs(y)) for x, y in zip(v, ref[k])), k
     if not args.warmup and timed:
         ngroups = len(timed[0])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, table, q, timed[-1], rank)
     del timed, first
     if world > 1:
         e = torch.tensor([elapsed], dtype=torch.float64)
@@ -788,26 +854,30 @@ def main():
     # memory (merge included), with no timing events (as the timed region).
     # The scan kernel's duration for the roofline: a second serialized pass (one query in flight, so no other query's
     # kernels share the GPU with the one being timed) whose queries record timing events (PGPU_OPT_TIMING).
-    nser = max(1, args.roofline_steps)
-    torch.cuda.synchronize()
-    t_ser = time.perf_counter()
-    run(nser, 1, keep=0)
-    torch.cuda.synchronize()
-    latency_ms = (time.perf_counter() - t_ser) / nser * 1e3
-    q.timing = True
-    kernel_us = run(nser, 1, keep=0)[1]
-    q.timing = False
-    torch.cuda.synchronize()
-    if world > 1:
-        e = torch.tensor([latency_ms], dtype=torch.float64)
-        dist.all_reduce(e, op=dist.ReduceOp.MAX)
-        latency_ms = float(e.item())
+    # Both passes, and everything after them up to the result line, are --full's.
+    latency_ms, kernel_us = None, []
+    if args.full:
+        nser = max(1, args.roofline_steps)
+        torch.cuda.synchronize()
+        t_ser = time.perf_counter()
+        run(nser, 1, keep=0)
+        torch.cuda.synchronize()
+        latency_ms = (time.perf_counter() - t_ser) / nser * 1e3
+        q.timing = True
+        kernel_us = run(nser, 1, keep=0)[1]
+        q.timing = False
+        torch.cuda.synchronize()
+        if world > 1:
+            e = torch.tensor([latency_ms], dtype=torch.float64)
+            dist.all_reduce(e, op=dist.ReduceOp.MAX)
+            latency_ms = float(e.item())
     launches = kernel_us[0][1] if kernel_us else 1
     kernel_avg_us = float(np.mean([k for k, _ in kernel_us])) / launches if kernel_us else 0.0  # per launch
 
     log("timed region done: %.3f ms/step" % (elapsed / args.steps * 1e3))
     roofline = None
-    if not args.no_bytes and w.star_tree and not args.no_star_tree and star_work[0] > 0:
+    with_bytes = args.full and not args.no_bytes
+    if with_bytes and w.star_tree and not args.no_star_tree and star_work[0] > 0:
         # star-tree bytes model (line-granular): nodes x 28 B + star-tree documents read x the bits of
         # the dimensions they are read for + the metric arrays' 64-B sectors that hold a matched document (counted by
         # the kernel: pgpu_plan_star_metric_bytes; without it, 8 B per document per pre-aggregated array)
@@ -829,7 +899,7 @@ def main():
                     "star_docs_read": int(star_work[2]), "bytes_per_star_doc": round(per_doc, 3),
                     "star_metric_bytes": int(metric_bytes),
                     "launches_per_query": 1, "kernel_us_per_query": round(kernel_avg_us, 2)}
-    if not args.no_bytes and (not w.star_tree or args.no_star_tree):  # scan-path bytes model
+    if with_bytes and (not w.star_tree or args.no_star_tree):  # scan-path bytes model
         bytes_alg, matched = compulsory_bytes(table, handles, q, docs, w.inverted_columns)
         bytes_alg /= launches  # equal chunks of statistically identical segments: per-launch share
         achieved = bytes_alg / (kernel_avg_us * 1e-6) / 1e9 if kernel_avg_us > 0 else 0.0
@@ -842,12 +912,12 @@ def main():
         roofline["traffic"] = round(pmc["traffic"], 0)
         roofline["traffic_pmc"] = {k: v for k, v in pmc.items() if k != "traffic"}
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("bytes_alg pass done; full-size parity")
         parity = full_parity(table, handles, q, w, docs, args)
         log("parity %s; CPU baseline" % (parity and parity["ok"]))
         cpu = cpu_baseline(table, handles, q, w, docs, args)
-    elif world > 1 and args.parity_segments != 0:
+    elif args.full and world > 1 and args.parity_segments != 0:
         # the merged answer (this rank's share of it for sharded combines) of one more query, against the oracle
         res = run(1, 1, keep=1)[0][0]
         log("rank %d: multi-rank parity" % rank)
@@ -861,11 +931,13 @@ def main():
             "value": round(value, 1),
             "unit": "rows/s",
             "n_gpus": world,
+            "full": bool(args.full),
             "steps": args.steps,
             "warmup": args.warmup, "warmup_run": warmup_run,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             # ms_per_step is a pipelined throughput (--inflight queries overlap); one query alone takes this long
-            "latency_ms_per_query": round(latency_ms, 4),
+            # (--full: null in a plain run)
+            "latency_ms_per_query": round(latency_ms, 4) if latency_ms is not None else None,
             "higher_is_better": True,
             "scaling": "weak" if args.segments_per_gpu else "strong",
             "vs_baseline": None,

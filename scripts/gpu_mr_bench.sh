@@ -8,7 +8,7 @@ mkdir -p gpurun_out/mr
 export PGPU_BENCH_BACKEND=host
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 300 python -u bench.py --gpus 2 --steps 3 --warmup 1 --warmup-ms 0 --no-cpu-baseline --no-pmc \
+  timeout -k 10 300 python -u bench.py --full --gpus 2 --steps 3 --warmup 1 --warmup-ms 0 --no-cpu-baseline --no-pmc \
     --verify "$@" > gpurun_out/mr/$name.log 2>&1
   local rc=$?
   echo "$name rc=$rc"

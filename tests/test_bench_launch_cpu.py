@@ -167,6 +167,98 @@ def test_merge_partial_arrays_is_the_broker_merge():
     assert stats == (2000, 2000, 4000, 2000)
 
 
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run measures the headline figure only; the rocprofv3 child runs of --full ask for --full themselves
+    (they read roofline.bytes_alg_per_launch from the child's line)."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "d"
+    import inspect
+    assert '"--full"' in inspect.getsource(bench.pmc_traffic)
+
+
+class _FakeStats:
+    def as_tuple(self):
+        return (11, 22, 33, 44)
+
+
+class _FakeResult:
+    """The parts of a GroupByResult that dump_outputs reads."""
+
+    def __init__(self, dicts, gids, aggs):
+        self._col = (dicts, gids, aggs, len(gids[0]) if gids else 0)
+        self.stats = _FakeStats()
+
+    def __len__(self):
+        return self._col[3]
+
+
+class _FakeTable:
+    def __init__(self, names, types):
+        self.index = {n: i for i, n in enumerate(names)}
+        self.types = types
+
+
+def _fake_result(n, seed):
+    from pinot_amd import _lib as L
+    rng = np.random.default_rng(seed)
+    d0 = [10 * i for i in range(50)]
+    d1 = ["s%d" % i for i in range(40)]
+    flat = rng.permutation(50 * 40)[:n]  # distinct (a, b) pairs, in no order
+    g0, g1 = (flat // 40).astype(np.int32), (flat % 40).astype(np.int32)
+    exact = rng.integers(-1000, 1000, n).astype(np.int64)
+    fsum = rng.normal(size=n)
+    cnt = rng.integers(1, 9, n).astype(np.int64)
+    res = _FakeResult([d0, d1], [g0, g1], [("SUM", None, exact, None), ("AVG", fsum, None, cnt)])
+    return res, _FakeTable(["a", "b"], [L.INT, L.STRING]), (g0, g1, exact, fsum, cnt)
+
+
+class _Q:
+    group_by = ["a", "b"]
+
+
+def test_dump_outputs_arrays(tmp_path):
+    """--dump-outputs: float64 arrays in ascending key order, numeric keys in value space, the same files from the
+    same result whatever order its rows come in."""
+    res, table, (g0, g1, exact, fsum, cnt) = _fake_result(300, 1)
+    bench.dump_outputs(str(tmp_path / "a"), table, _Q, res)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["avg_counts", "keys", "stats", "values"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    order = np.lexsort((g1, g0))
+    assert np.array_equal(got["keys"], np.stack([10.0 * g0[order], 1.0 * g1[order]], axis=1))
+    assert np.array_equal(got["values"], np.stack([exact[order].astype(np.float64), fsum[order]]))
+    assert np.array_equal(got["avg_counts"], np.stack([np.zeros(300), cnt[order].astype(np.float64)]))
+    assert list(got["stats"]) == [11, 22, 33, 44, 300]
+    # the same groups in another row order: the same files
+    p = np.random.default_rng(5).permutation(300)
+    res2 = _FakeResult(res._col[0], [g0[p], g1[p]], [("SUM", None, exact[p], None), ("AVG", fsum[p], None, cnt[p])])
+    bench.dump_outputs(str(tmp_path / "b"), table, _Q, res2, rank=0)
+    for name, a in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (name + ".npy")), a), name
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """A result past the byte limit is cut to a seeded sample of its rows: within the limit, the same rows every
+    time, still in key order; rank r > 0 writes <name>.rank<r>.npy."""
+    res, table, _ = _fake_result(2000, 2)
+    limit = 20_000
+    bench.dump_outputs(str(tmp_path / "a"), table, _Q, res, max_bytes=limit)
+    bench.dump_outputs(str(tmp_path / "b"), table, _Q, res, rank=3, max_bytes=limit)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(x.nbytes for x in a.values()) <= limit
+    n = a["keys"].shape[0]
+    assert 0 < n < 2000 and a["values"].shape == (2, n) and a["stats"][4] == 2000
+    flat = a["keys"][:, 0] * 100 + a["keys"][:, 1]
+    assert np.all(np.diff(flat) > 0)
+    for name, x in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (name + ".rank3.npy")), x)
+    assert bench.DUMP_MAX_BYTES <= 64 * 1000 * 1000
+
+
 def test_parse_config_fields():
     """bench.py --config: pgpu_config fields as integers / floats; the names must be the ABI's (GpuTable rejects
     unknown ones)."""

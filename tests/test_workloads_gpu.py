@@ -137,3 +137,29 @@ def test_workload_c4_star_tree(oracle, gpu_lib):
         assert r.stats.num_docs_scanned < rs.stats.num_docs_scanned
     finally:
         t.close()
+
+
+def test_bench_dump_outputs_is_the_result(gpu_lib, tmp_path):
+    """bench.py --dump-outputs writes what the caller of the query receives: the arrays read back equal the decoded
+    GroupByResult (keys in value space, every aggregation, AVG counts, statistics), in ascending key order."""
+    import bench
+    w = WORKLOADS["c2"]()
+    docs = 20_000
+    q = parse_query("SELECT COUNT(*), SUM(mi), AVG(mi), MAX(md), SUM(md) FROM t WHERE f < 500 GROUP BY d, f")
+    t = GpuTable(w.schema)
+    try:
+        hs = [t.generate_segment(w.gen, row0=i * docs, num_docs=docs) for i in range(2)]
+        r = t.execute_groupby(hs, q)
+        bench.dump_outputs(str(tmp_path), t, q, r)
+        got = {n: np.load(tmp_path / (n + ".npy")) for n in ("keys", "values", "avg_counts", "stats")}
+        exp = r.as_dict()
+        assert len(exp) == len(r) > 100
+        keys = [tuple(k) for k in got["keys"].tolist()]
+        assert keys == sorted(exp)  # INT keys: exact in float64
+        for i, k in enumerate(keys):
+            cnt, s, avg, mx, sd = exp[k]
+            assert list(got["values"][:, i]) == [cnt, s, avg.sum, mx, sd]
+            assert list(got["avg_counts"][:, i]) == [0, 0, avg.count, 0, 0]
+        assert list(got["stats"]) == list(r.stats.as_tuple()) + [len(r)]
+    finally:
+        t.close()
