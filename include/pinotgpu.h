@@ -405,6 +405,16 @@ int pgpu_plan_timing(pgpu_plan plan, double* out4);
 /* Star-tree work of the last execution (after finalize): [0] segments answered from their star-tree, [1] their
  * tree nodes (28 bytes each, OffHeapStarTreeNode), [2] star-tree documents the residual scan read. */
 int pgpu_plan_star_work(pgpu_plan plan, int64_t* out3);
+/* Geometry of the plan's scan and of its last scan launch (after an execution; the partitioned group-by has its own
+ * passes and leaves [4..14] zero).  out holds 16 values:
+ * [0] the plan's grid (workgroups of a launch with at least that many tiles), [1] the scan's dynamic LDS bytes,
+ * [2] tiles per workgroup the LDS reserves for the STATS_LEAP2 bytes (0: the plan keeps none), [3] the plan's tiles;
+ * of the last launch: [4] 1 = contiguous runs per workgroup, 0 = XCD-interleaved tiles, [5] CU slots the runs are
+ * weighted by (0 = equal shares), [6..9] their weights in 1/256ths (pgpu_config.slot_weight_step), [10] the most
+ * tiles any of its workgroups took, [11] its workgroups, [12] its tiles, [13] 1 = no other execution of the table
+ * was in flight (weights are for such launches only), [14] 1 = weights were declined because the longest weighted
+ * run could pass [2]; [15] 0. */
+int pgpu_plan_scan_geometry(pgpu_plan plan, int64_t* out16);
 /* Bytes of the star-tree metric arrays the last execution's document scan read (after finalize): the 64-byte
  * sectors holding at least one matched document, summed over the arrays read; -1 where finalize did not read the
  * counter back (tables past 512 KB).  The star path's line-granular bytes model (bench.py). */

@@ -21,7 +21,7 @@ SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTI
     [("k_startree.hip", ["-DPGPU_MODE=%d" % m], "k_startree_%d" % m) for m in range(3)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h"]
+           "rt_decls.h", "tile_split.h"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
 
@@ -151,6 +151,32 @@ def build_host_fuzz(force=False):
         raise RuntimeError("hipcc (host sanitizers) link failed:\n" + res.stdout[-6000:])
     os.replace(FUZZ_PATH + ".tmp", FUZZ_PATH)
     return FUZZ_PATH
+
+
+SPLIT_CHECK_PATH = os.path.join(ROOT, "build", "tile_split_check")
+
+
+def build_tile_split_check(force=False):
+    """build/tile_split_check: tools/tile_split_check.cpp, which includes csrc/tile_split.h and nothing else of the
+    library, under AddressSanitizer + UndefinedBehaviorSanitizer.  One compile, no library linked."""
+    src = os.path.join(ROOT, "tools", "tile_split_check.cpp")
+    hdr = os.path.join(CSRC, "tile_split.h")
+    if not force and os.path.exists(SPLIT_CHECK_PATH) and \
+            all(os.path.getmtime(f) <= os.path.getmtime(SPLIT_CHECK_PATH) for f in (src, hdr)):
+        return SPLIT_CHECK_PATH
+    os.makedirs(os.path.dirname(SPLIT_CHECK_PATH), exist_ok=True)
+    hipcc = _hipcc()
+    obj = os.path.join(ROOT, "build", "tile_split_check.o")
+    # (the sanitizers are host-only flags: compiled as the library's sources are, then linked with their runtimes)
+    for cmd in ([hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS +
+                ["-c", src, "-o", obj],
+                [hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined", obj,
+                 "-o", SPLIT_CHECK_PATH + ".tmp"]):
+        res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if res.returncode != 0:
+            raise RuntimeError("hipcc (tile_split_check) failed:\n" + res.stdout[-6000:])
+    os.replace(SPLIT_CHECK_PATH + ".tmp", SPLIT_CHECK_PATH)
+    return SPLIT_CHECK_PATH
 
 
 if __name__ == "__main__":

@@ -33,6 +33,27 @@ int pgpu_plan_star_work(pgpu_plan P, int64_t* out3) try {
   return 0;
 } PGPU_ABI_CATCH
 
+int pgpu_plan_scan_geometry(pgpu_plan P, int64_t* out16) try {
+  PGPU_ABI_GUARD;
+  if (!P || !out16) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (P->composite) return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit plan: the geometry is per part");
+  const pgpu_plan_s::ScanLaunch& L = P->last_scan;
+  out16[0] = P->grid;
+  out16[1] = (int64_t)P->lds_bytes;
+  out16[2] = P->leap_reserved ? P->leap_tiles : 0;
+  out16[3] = P->num_tiles;
+  out16[4] = L.tile_chunks;
+  out16[5] = L.slot_n;
+  for (int s = 0; s < kMaxCuSlots; ++s) out16[6 + s] = L.slot_w[s];
+  out16[10] = L.grid > 0 ? launch_longest_run(L.tiles, L.grid, L.tile_chunks, L.slot_n, L.slot_w) : 0;
+  out16[11] = L.grid;
+  out16[12] = L.tiles;
+  out16[13] = L.alone ? 1 : 0;
+  out16[14] = L.declined ? 1 : 0;
+  out16[15] = 0;
+  return 0;
+} PGPU_ABI_CATCH
+
 int pgpu_plan_star_metric_bytes(pgpu_plan P, int64_t* bytes) try {
   PGPU_ABI_GUARD;
   if (!P || !bytes) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");

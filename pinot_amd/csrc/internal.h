@@ -14,9 +14,10 @@
 #pragma once
 #include <stdint.h>
 
+#include "tile_split.h"  // kBlock, kMaxStack, kWaveQ: the scan's LDS layout and tile split
+
 namespace pgpu {
 
-constexpr int kBlock = 256;                 // threads per workgroup (4 waves of 64)
 constexpr int kDocsPerLane = 32;            // one lane owns a 32-doc group = `bits` u32 words
 constexpr int kTileDocs = kBlock * kDocsPerLane;  // 8192 docs per tile
 constexpr int kLdsPackShift = 40;           // KParams.pack_shift of an LDS table (COUNT < 2^24, SUM < 2^40)
@@ -25,10 +26,8 @@ constexpr int kMaxLeaves = 16;              // predicate leaves
 constexpr int kMaxOps = 48;                 // postfix filter program length
 constexpr int kMaxKeys = 16;                // group-by columns handled on the GPU
 constexpr int kMaxSlots = 24;               // accumulator rows of the group table
-constexpr int kMaxStack = 8;                // filter evaluation stack depth
 constexpr int kFwdPadWords = 4;
-constexpr int kWaveQ = 256;                 // direct kernel: per-wave queue of sparse matched docs (LDS, u32)
-constexpr int kFlushAt = 128;               // ... aggregated in 2-per-lane batches once it holds this many
+constexpr int kFlushAt = 128;               // the per-wave match queue (kWaveQ) is aggregated in 2-per-lane batches at this fill
 constexpr int kDenseGroupMin = 256;        // matches per wave-tile (of 2048 docs) above which whole groups are decoded
 constexpr int kFastLeaves = 4;              // pure-AND programs up to this many leaves keep them in registers
 

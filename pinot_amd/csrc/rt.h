@@ -688,6 +688,14 @@ struct pgpu_plan_s {
   bool in_kernel_stats = false;           // the scan kernel counts STATS_CHAIN / STATS_LEAP2 segments
   bool any_leap2 = false;
   bool leap_reserved = false;             // the scan's LDS holds the LEAP2 bytes (configure); maps allocated
+  int64_t leap_tiles = 0;                 // ... of this many tiles per workgroup (scan_leap_tiles, tile_split.h)
+  // the last scan launch's geometry (exec_launch_chunk; pgpu_plan_scan_geometry)
+  struct ScanLaunch {
+    int64_t tiles = 0;
+    int grid = 0, tile_chunks = 0, slot_n = 0;
+    uint16_t slot_w[kMaxCuSlots] = {};
+    bool alone = false, declined = false;  // declined: weights refused for the LDS the plan reserved
+  } last_scan;
   // STATS_GENERIC segments: their filter tree, replayed on the host over the leaves' device bitmaps
   struct GenericStat { int64_t rec; int32_t num_docs; StatTree tree; int64_t out_word; };
   std::vector<GenericStat> generic;

@@ -528,16 +528,15 @@ int diag_wg_times_report(pgpu_table_s* t, const KParams& kp, int grid, hipStream
 // issue the oldest wave first: equal shares end slot by slot, 1 : 1.08 : 1.17 : 1.27 (C3, 125 and 1000 segments), and
 // weighted by those ratios the per-tile times spread further (4.55 / 4.92 / 5.47 / 6.06 us at 1000 segments), so
 // pgpu_config.slot_weight_step defaults to the latter's inverse, 1 + 0.11 (S-1-s) (r06 sessions f, g:
-// profiles/r06_ab_summary.txt); 0 gives equal shares.
-constexpr int64_t kSlotWeightMinShare = 32;
-void set_slot_weights(KParams& kp, int grid, int num_cus, double step) {
+// profiles/r06_ab_summary.txt); 0 gives equal shares.  max_run: the tiles per workgroup the plan reserved LDS for
+// (STATS_LEAP2 bytes; the kernel's tile loop has no bound of its own) -- weights whose longest run could pass it are
+// declined (returns false, equal shares), as are those past kLeapLdsTiles (slot_weights, tile_split.h).
+bool set_slot_weights(KParams& kp, int grid, int num_cus, double step, int64_t max_run) {
   kp.slot_n = 0;
-  const int S = num_cus > 0 && grid % num_cus == 0 ? grid / num_cus : 0;
-  if (!(step > 0.0) || !kp.tile_chunks || S < 2 || S > 4 || (grid & 7) || kp.claim ||
-      kp.num_tiles < kSlotWeightMinShare * grid)
-    return;
-  for (int s = 0; s < S; ++s) kp.slot_w[s] = (uint16_t)std::min(4096.0, (1.0 + step * (S - 1 - s)) * 256.0 + 0.5);
-  kp.slot_n = S;
+  if (!kp.tile_chunks || kp.claim) return true;
+  bool declined = false;
+  kp.slot_n = slot_weights(kp.num_tiles, grid, num_cus, step, std::min(max_run, kLeapLdsTiles), kp.slot_w, &declined);
+  return !declined;
 }
 
 void set_tile_claims(KParams& kp, unsigned long long* d_stats, int grid, int launch) {
@@ -690,7 +689,17 @@ int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const Laun
     static const bool wg_times = diag("wgtimes");
     if (wg_times) TRY(diag_wg_times_begin(kp, grid, stream));
     set_tile_claims(kp, P->d_stats, grid, c);
-    if (P->alone) set_slot_weights(kp, grid, P->table->num_cus, P->cfg.slot_weight_step);
+    bool fits = true;
+    if (P->alone)
+      fits = set_slot_weights(kp, grid, P->table->num_cus, P->cfg.slot_weight_step,
+                              P->leap_reserved ? P->leap_tiles : kLeapLdsTiles);
+    P->last_scan.tiles = kp.num_tiles;
+    P->last_scan.grid = grid;
+    P->last_scan.tile_chunks = kp.tile_chunks;
+    P->last_scan.slot_n = kp.slot_n;
+    for (int s = 0; s < kMaxCuSlots; ++s) P->last_scan.slot_w[s] = kp.slot_n ? kp.slot_w[s] : 0;
+    P->last_scan.alone = P->alone;
+    P->last_scan.declined = !fits;
     const int rc = launch_filter_groupby(kp, P->mode,
                                          scan_variant(P),
                                          grid, P->lds_bytes, stream);

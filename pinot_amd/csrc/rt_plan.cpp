@@ -1004,15 +1004,16 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
   // LDS-privatised tables up to 112 KB (one workgroup per CU at the top end): measured on MI355X, an 80 KB table
   // (C4: 5000 groups x 2 slots) runs 2.1x faster in LDS than with global atomics.  pgpu_config.lds_table_kb.
   const int64_t kLdsBudget = (int64_t)std::max(1, P->cfg.lds_table_kb) * 1024;
-  // direct kernel LDS: [table (MODE_LDS)] [filter stack (general programs)] [per-wave match queues]
-  const size_t stack_bytes = (pure_and ? 0 : (size_t)kMaxStack * kBlock * 4) + (size_t)(kBlock / 64) * 2 * kWaveQ * 4;
+  // direct kernel LDS: [table (MODE_LDS)] [filter stack (general programs)] [per-wave match queues] (scan_lds_layout,
+  // the kernel's own; configure adds the STATS_LEAP2 bytes)
+  const size_t stack_bytes = (size_t)scan_lds_layout(0, pure_and).maps;
   for (Segment* s : P->segs) P->total_docs += s->num_docs;
   P->pack_slot = lds_pack_slot(t, P, q, G);
   const int lds_rows = nslots - (P->pack_slot >= 0 ? 1 : 0);
   if ((int64_t)lds_rows * G * 8 <= kLdsBudget) {
     P->mode = MODE_LDS;
     P->num_keys = G;
-    P->lds_bytes = (size_t)lds_rows * G * 8 + stack_bytes;
+    P->lds_bytes = (size_t)scan_lds_layout((int64_t)lds_rows * G, pure_and).maps;
   } else if (G <= kDenseGlobalMax) {
     P->pack_slot = -1;
     P->mode = MODE_GLOBAL;
@@ -1448,12 +1449,14 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
     if (P->any_leap2 || (se && P->in_kernel_stats)) {
       P->leap_reserved = true;
       // STATS_LEAP2 bytes of a workgroup's tiles are buffered in LDS (one per tile and wave) until the end of the
-      // scan: at most kLeapLdsTiles tiles per workgroup (more workgroups than resident ones for huge plans)
-      constexpr int64_t kLeapLdsTiles = 4096;
+      // scan: at most kLeapLdsTiles tiles per workgroup (more workgroups than resident ones for huge plans).  Room for
+      // the longest run of any launch of the plan, weighted by CU slot or not (scan_leap_tiles, tile_split.h); the
+      // weights of a launch whose runs would not fit are declined (set_slot_weights).  The occupancy above was
+      // queried without these bytes, as it always was.
       const int64_t need = (tile_base + kLeapLdsTiles - 4) / (kLeapLdsTiles - 3);
       if (P->grid < need) P->grid = (int)((need + 7) & ~int64_t(7));
-      const int64_t per_wg = (tile_base + P->grid - 1) / std::max(P->grid, 1) + 3;
-      P->lds_bytes += (size_t)((per_wg * (kBlock / 64) + 15) & ~int64_t(15));
+      P->leap_tiles = scan_leap_tiles(tile_base, P->grid, t->num_cus, P->cfg.slot_weight_step);
+      P->lds_bytes += (size_t)scan_lds_maps_bytes(P->leap_tiles);
     }
     // Large dense tables: partitioned group-by (partition.h) instead of random global atomics; sparse hash key
     // spaces below 2^31: the same passes over hashed partitions (K8h) instead of the global hash table.

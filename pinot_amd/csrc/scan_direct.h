@@ -67,13 +67,16 @@ __global__ __launch_bounds__(kBlock, DENSE ? (SIMPLE ? PGPU_SIMPLE_MIN_WAVES : P
   // MODE_LDS with KParams.pack_slot: no COUNT row in LDS (slot s at row s - 1; the COUNT rides in the pack slot)
   const int lds_row0 = (MODE == MODE_LDS && p.pack_slot >= 0) ? 1 : 0;
   const int64_t table_words = (MODE == MODE_LDS) ? (int64_t)(p.num_slots - lds_row0) * G : 0;
-  uint32_t* stack = reinterpret_cast<uint32_t*>(lds + table_words);
-  // per-wave queue of sparse matches ((doc, segment) pairs), after the filter stack
-  uint32_t* wq = stack + (p.pure_and ? 0 : kMaxStack * kBlock) + wave * 2 * kWaveQ;
+  // the block's layout (tile_split.h, shared with the plan's lds_bytes): filter stack, per-wave queues of sparse
+  // matches ((doc, segment) pairs), then the STATS_LEAP2 bytes of this workgroup's tiles, [tile k of its run][wave] --
+  // the plan reserves the longest run of any of its launches (scan_leap_tiles), so kk needs no bound here
+  const ScanLds L = scan_lds_layout(table_words, p.pure_and != 0);
+  uint8_t* const lds8 = reinterpret_cast<uint8_t*>(lds);
+  uint32_t* stack = reinterpret_cast<uint32_t*>(lds8 + L.stack);
+  uint32_t* wq = reinterpret_cast<uint32_t*>(lds8 + L.queues) + wave * 2 * kWaveQ;
   uint32_t* wqs = wq + kWaveQ;
   uint32_t qn = 0;  // wave-uniform fill
-  // STATS_LEAP2 bytes of this workgroup's tiles, [tile k of the workgroup][wave], after the match queues
-  uint8_t* lmaps = reinterpret_cast<uint8_t*>(stack + (p.pure_and ? 0 : kMaxStack * kBlock) + (kBlock / 64) * 2 * kWaveQ);
+  uint8_t* lmaps = lds8 + L.maps;
   int kk = 0;  // tiles of this workgroup so far
   // The query's end time had passed when the launch came up (expand_tiles_kernel, run just before on the stream,
   // read the device clock and set stats[5]): take no tile.  No clock read in this kernel -- even one outside the
@@ -112,7 +115,6 @@ __global__ __launch_bounds__(kBlock, DENSE ? (SIMPLE ? PGPU_SIMPLE_MIN_WAVES : P
   unsigned long long matched = 0;
   uint32_t in_filter = 0;  // STATS_CHAIN entries of this lane (< 2^32: at most 4 leaves x 32 docs x tiles)
   const int64_t T = p.num_tiles;
-  int64_t t_begin, t_end, t_step;
   // run-time claims (chunked plans): the static runs end at claim_base, the rest goes claim_tiles at a time to the
   // workgroups that finish first.  The next claim is issued before the run it follows, so its atomic's round trip
   // overlaps that run's loads; one barrier per run hands it to the other waves.
@@ -124,40 +126,11 @@ __global__ __launch_bounds__(kBlock, DENSE ? (SIMPLE ? PGPU_SIMPLE_MIN_WAVES : P
   __shared__ uint32_t claim_at[2];
   uint32_t next_claim = 0;
   if (dyn && tid == 0) next_claim = atomicAdd(p.claim, (uint32_t)p.claim_tiles);
-  if (gridDim.x >= 64 && (gridDim.x & 7) == 0 && p.tile_chunks) {
-    // chunked: each workgroup a contiguous run of its XCD's eighth -- consecutive tiles of one segment, so the
-    // segment's records are read once per run instead of once per tile (plans without per-doc gathers)
-    const int64_t TS = dyn ? p.claim_base : T;
-    const int64_t x = blockIdx.x & 7, i = blockIdx.x >> 3, nx = gridDim.x >> 3;
-    const int64_t lo = x * TS / 8, len = (x + 1) * TS / 8 - lo;
-    if (p.slot_n > 1) {
-      // weighted by CU slot (KParams.slot_w): the XCD's workgroups i of slot s are i in [nx s / n, nx (s+1) / n)
-      auto cum = [&](int64_t j) {  // total weight of the XCD's workgroups [0, j)
-        int64_t c = 0;
-        for (int s = 0; s < p.slot_n; ++s) {
-          const int64_t a = nx * s / p.slot_n, e = nx * (s + 1) / p.slot_n;
-          c += (j <= a ? 0 : j < e ? j - a : e - a) * (int64_t)p.slot_w[s];
-        }
-        return c;
-      };
-      const int64_t tot = cum(nx);
-      t_begin = lo + len * cum(i) / tot;
-      t_end = lo + len * cum(i + 1) / tot;
-    } else {
-      t_begin = lo + i * len / nx;
-      t_end = lo + (i + 1) * len / nx;
-    }
-    t_step = 1;
-  } else if (gridDim.x >= 64 && (gridDim.x & 7) == 0) {
-    const int64_t x = blockIdx.x & 7;
-    t_begin = x * T / 8 + (blockIdx.x >> 3);
-    t_end = (x + 1) * T / 8;
-    t_step = gridDim.x >> 3;
-  } else {
-    t_begin = (int64_t)blockIdx.x * T / gridDim.x;
-    t_end = (int64_t)(blockIdx.x + 1) * T / gridDim.x;
-    t_step = 1;
-  }
+  // chunked (each workgroup a contiguous run of its XCD's eighth -- consecutive tiles of one segment, so the segment's
+  // records are read once per run instead of once per tile: plans without per-doc gathers; weighted by CU slot with
+  // KParams.slot_w), XCD-interleaved, or plain equal runs: tile_split.h
+  const TileRun run0 = tile_split(blockIdx.x, gridDim.x, T, p.tile_chunks, p.slot_n, p.slot_w, dyn ? p.claim_base : T);
+  int64_t t_begin = run0.begin, t_end = run0.end, t_step = run0.step;
   // FAST: an instance for plans whose filter is a pure AND of at most kFastLeaves leaves (the general program
   // evaluator compiled out)
   const bool fast = FAST || (p.pure_and && p.num_leaves <= kFastLeaves);

@@ -594,6 +594,18 @@ class Plan:
         L.check(self.lib.pgpu_plan_star_work(self.handle, out))
         return out[0], out[1], out[2]
 
+    def scan_geometry(self):
+        """The scan's geometry (pgpu_plan_scan_geometry): of the plan `grid`, `lds_bytes`, `leap_tiles` (tiles per
+        workgroup its LDS reserves for the STATS_LEAP2 bytes, 0 = none) and `tiles`; of its last scan launch
+        `tile_chunks`, `slot_weights` (a tuple, empty = equal shares), `longest_run`, `launch_grid`, `launch_tiles`,
+        `alone` and `weights_declined` (refused for the LDS the plan reserved)."""
+        out = (ctypes.c_int64 * 16)()
+        L.check(self.lib.pgpu_plan_scan_geometry(self.handle, out))
+        return {"grid": out[0], "lds_bytes": out[1], "leap_tiles": out[2], "tiles": out[3],
+                "tile_chunks": out[4], "slot_weights": tuple(out[6 + s] for s in range(out[5])),
+                "longest_run": out[10], "launch_grid": out[11], "launch_tiles": out[12],
+                "alone": bool(out[13]), "weights_declined": bool(out[14])}
+
     def finalize(self, stream=None, d_table=None):
         """Waits for the execution, compacts the group table and returns the decoded result.  `finalize_us`
         holds (C ABI finalize incl. the wait for the kernels, decode into numpy) in microseconds."""

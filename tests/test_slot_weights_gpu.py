@@ -1,7 +1,16 @@
 """Chunked scans weighted by CU slot (pgpu_config.slot_weight_step, r06): the weights only move tiles between the
-workgroups of a launch, so every weighting -- none, the default, an extreme one -- returns the same groups, values and
-statistics.  300 C3 segments of 1 M rows (36 900 tiles, >= 32 per workgroup of the 1 024-workgroup grid, so the
-weighted split runs when the launch is alone on the table)."""
+workgroups of a launch, so every weighting -- none, the default, an extreme one, the configuration's maximum --
+returns the same groups, values and statistics.  300 C3 segments of 1 M rows (36 900 tiles, >= 32 per workgroup of
+the 1 024-workgroup grid, so the weighted split runs when the launch is alone on the table; the smallest shape at
+which it does).
+
+The scan's geometry (Plan.scan_geometry) says whether the weights really were in effect -- a launch beside another
+one, or one whose weights the plan's LDS reservation declined, would make the comparison one of identical launches, so
+the test fails there instead of passing -- and that no workgroup took more tiles than the LDS reserves for its
+STATS_LEAP2 bytes (the exhaustive form of that bound: tests/test_tile_split_cpu.py).  numDocsScanned and
+numEntriesScannedInFilter are also held against a reference of another geometry: they add over segments, so the sum
+over 12 executions of 25 segments each (3 075 tiles: below the weights' threshold, another grid-to-tile ratio; plans
+of that size are pinned to the oracle by tests/test_workloads_gpu.py)."""
 import pytest
 
 from pinot_amd.executor import GpuTable
@@ -12,6 +21,8 @@ pytestmark = pytest.mark.gpu
 
 DOCS = 1_000_000
 SEGS = 300
+PART = 25
+STEPS = (0.0, 0.11, 3.0, 4.0)  # 4.0: the configuration's maximum
 
 
 @pytest.fixture(scope="module")
@@ -23,6 +34,17 @@ def c3_table(gpu_lib):
     t.close()
 
 
+def _execute(t, handles, q):
+    with t.plan_execute(handles, q) as p:
+        r = p.finalize()
+        return r, p.scan_geometry()
+
+
+def _weights(step, slots):
+    """pgpu_config.slot_weight_step in the kernel's 1/256ths: slot s of S weighs 1 + step (S - 1 - s), at most 16."""
+    return tuple(min(4096, int((1.0 + step * (slots - 1 - s)) * 256.0 + 0.5)) for s in range(slots))
+
+
 @pytest.mark.parametrize("sql", [
     None,  # the workload's query (two scan leaves in leap-frog, LEAP2 statistics)
     "SELECT COUNT(*), SUM(clicks), MAX(impressions) FROM t WHERE accountId IN (123456789, 4242) GROUP BY daysSinceEpoch",
@@ -32,9 +54,42 @@ def test_weights_change_nothing_but_the_split(c3_table, sql):
     t, handles, w = c3_table
     q = parse_query(sql or w.sql, num_groups_limit=w.num_groups_limit)
     out = []
-    for step in (0.0, 0.11, 3.0):
-        t.set_config(slot_weight_step=step)
-        r = t.execute_groupby(handles, q)
-        out.append((r.as_dict(), r.stats.as_tuple()))
-    t.set_config(slot_weight_step=0.11)
-    assert out[0][0] and out[0] == out[1] == out[2]
+    try:
+        for step in STEPS:
+            t.set_config(slot_weight_step=step)
+            r, geo = _execute(t, handles, q)
+            print("step %.2f: %s stats %s" % (step, geo, r.stats.as_tuple()))
+            out.append((r.as_dict(), r.stats.as_tuple()))
+            assert geo["launch_tiles"] == geo["tiles"] == SEGS * 123 and geo["launch_grid"] == geo["grid"], geo
+            if sql is None:
+                assert geo["leap_tiles"] > 0, "the workload's plan keeps LEAP2 bytes in LDS: %s" % (geo,)
+            if geo["leap_tiles"]:
+                assert geo["longest_run"] <= geo["leap_tiles"], "a run longer than the LDS reserves: %s" % (geo,)
+            if step == 0.0:
+                assert geo["slot_weights"] == (), geo
+                continue
+            if not geo["slot_weights"]:
+                why = ("another execution of the table was in flight" if not geo["alone"] else
+                       "declined: the longest weighted run would pass the plan's LDS reservation"
+                       if geo["weights_declined"] else
+                       "the plan's tiles are XCD-interleaved, not chunked" if not geo["tile_chunks"] else
+                       "fewer than 32 tiles per workgroup, or a grid that is no whole number (2-4) of workgroups per CU")
+                pytest.fail("step %.2f ran with equal shares (%s): %s" % (step, why, geo))
+            assert geo["slot_weights"] == _weights(step, len(geo["slot_weights"])), geo
+            # the weighted launch is not the equal one: its longest run is longer
+            assert geo["longest_run"] > -(-geo["launch_tiles"] // geo["launch_grid"]), geo
+        # additive over segments: the same table and query in 12 plans below the weights' threshold
+        docs = entries = 0
+        for i in range(0, SEGS, PART):
+            r, geo = _execute(t, handles[i:i + PART], q)
+            assert geo["slot_weights"] == () and geo["launch_tiles"] == PART * 123, geo
+            docs += r.stats.num_docs_scanned
+            entries += r.stats.num_entries_scanned_in_filter
+    finally:
+        t.set_config(slot_weight_step=0.11)
+    for step, o in zip(STEPS, out):
+        assert o == out[0], "step %.2f differs from equal shares, whose statistics are %s" % (step, out[0][1])
+        assert (o[1][0], o[1][1]) == (docs, entries), \
+            "step %.2f: (numDocsScanned, numEntriesScannedInFilter) %s, summed over %d-segment plans %s" % (
+                step, (o[1][0], o[1][1]), PART, (docs, entries))
+    assert out[0][0]
