@@ -243,6 +243,26 @@ typedef struct {
  * marker packet between two dependent dispatches of the stream (about 10 us per query of gaps at 125 segments,
  * measured), so a serving query carries none.  Not part of the plan-cache key. */
 #define PGPU_OPT_TIMING 8
+/* Bit-reproducible SUM / AVG over FLOAT / DOUBLE columns (and over integer columns whose sums could pass int64 and
+ * are therefore summed as doubles).  Without it such a sum is accumulated with floating-point atomics in whatever
+ * order the scan's workgroups reach a group, and its last bits can differ between two runs of one query.  With it
+ * every operand is split into W = 2 or 3 fixed-point digits of K bits below 2^E, the digits are summed as integers
+ * (any order gives the same sums) and the result is rounded to a double once: the same bits in every run, for every
+ * segment layout, accumulator mode and tile order.  The plan picks (E, K, W) from the values it can read -- the
+ * segments' dictionaries, raw columns and star-tree metrics -- and the docs it covers (pgpu_plan_fp_sum_format):
+ *   exact      the digits hold every bit of every operand: the result is the correctly rounded exact sum;
+ *   quantised  operands span more than W K bits: each is truncated toward zero to a multiple of 2^(E - W K) first,
+ *              an error below 2^-(W K) of the largest operand per doc -- less than one rounding of a running double
+ *              sum costs; the result is the correctly rounded sum of the truncated operands, still order-independent.
+ * A column with a NaN or an infinity among its values keeps the floating-point accumulator (mode 0).
+ * Limits: a plan with such sums takes the scan kernel's LDS / global / hash tables, not the radix- or hash-partitioned
+ * pipelines (planned as with pgpu_config.partitioned_group_by = 0 and hash_partitions = 0), runs as one launch from
+ * pgpu_plan_create_execute, takes W accumulator slots per summed column (the limit of 24 counts them), and is
+ * declined with PGPU_ERR_UNSUPPORTED by the cross-GPU entry points (pgpu_plan_combine*, pgpu_plan_exchange_*,
+ * pgpu_result_exchange_rows / merge_rows / combine_rows, pgpu_plan_finalize_range, an external d_table): the ranks
+ * would first have to agree on (E, K, W).  Part of the plan-cache key.  Queries without such a sum plan and run
+ * exactly as without the option. */
+#define PGPU_OPT_EXACT_FP_SUM 16
 
 /* A query compiled against a list of pinned segments (InstancePlanMakerImplV2.makeInstancePlan +
  * per-segment AggregationGroupByPlanNode: predicate evaluators per segment, group-key layout, accumulators). */
@@ -402,6 +422,11 @@ int pgpu_plan_create_execute(pgpu_table table, const int64_t* segment_handles, i
  * (traversal + pre-aggregated document scan; 0 without star-tree segments).  out holds 4 doubles. */
 int pgpu_plan_timing(pgpu_plan plan, double* out4);
 
+/* The fixed-point format of aggregation `agg` of a plan made with PGPU_OPT_EXACT_FP_SUM: out = {mode, E, K, W}, mode
+ * 0 = none (not a FLOAT / DOUBLE sum, the option is off, or the column holds a non-finite value: E = K = W = 0),
+ * 1 = exact, 2 = quantised; K is the digit width the kernels use. */
+int pgpu_plan_fp_sum_format(pgpu_plan plan, int agg, int32_t out[4]);
+
 /* Star-tree work of the last execution (after finalize): [0] segments answered from their star-tree, [1] their
  * tree nodes (28 bytes each, OffHeapStarTreeNode), [2] star-tree documents the residual scan read. */
 int pgpu_plan_star_work(pgpu_plan plan, int64_t* out3);
@@ -413,7 +438,9 @@ int pgpu_plan_star_work(pgpu_plan plan, int64_t* out3);
  * weighted by (0 = equal shares), [6..9] their weights in 1/256ths (pgpu_config.slot_weight_step), [10] the most
  * tiles any of its workgroups took, [11] its workgroups, [12] its tiles, [13] 1 = no other execution of the table
  * was in flight (weights are for such launches only), [14] 1 = weights were declined because the longest weighted
- * run could pass [2]; [15] 0. */
+ * run could pass [2]; [15] the scan kernel's instance: 0 sparse, 1 dense, 2 dense without gathers, 3 - 5 the sparse
+ * specialisations (index + scan pair, pure AND, pure AND with 4-doc batches), 6 / 7 the sparse / dense instance of
+ * plans with fixed-point sums (PGPU_OPT_EXACT_FP_SUM). */
 int pgpu_plan_scan_geometry(pgpu_plan plan, int64_t* out16);
 /* Bytes of the star-tree metric arrays the last execution's document scan read (after finalize): the 64-byte
  * sectors holding at least one matched document, summed over the arrays read; -1 where finalize did not read the

@@ -11,7 +11,7 @@ from .segment import ColumnData, SegmentBuffers, load_v1_segment_dir  # noqa: F4
 
 def __getattr__(name):
     # Lazily import the pieces that load the shared library.
-    if name in ("GpuTable", "Plan", "GroupByResult", "ExecutionStatistics", "AvgPair"):
+    if name in ("GpuTable", "Plan", "GpuPlan", "GroupByResult", "ExecutionStatistics", "AvgPair"):
         from . import executor
         return getattr(executor, name)
     if name in ("GpuAggregationGroupByOperator", "GpuGroupByCombineOperator", "IntermediateResultsBlock"):

@@ -67,6 +67,8 @@ OPT_NO_STAR_TREE = 1
 OPT_SQL_GROUP_BY = 2
 OPT_NO_PLAN_CACHE = 4
 OPT_TIMING = 8
+OPT_EXACT_FP_SUM = 16
+FP_SUM_MODE_NAMES = ("none", "exact", "quantised")  # pgpu_plan_fp_sum_format mode
 LEAF_EMPTY, LEAF_MATCH_ALL, LEAF_SCAN, LEAF_SORTED, LEAF_BITMAP, LEAF_RANGE_INDEX = 0, 1, 2, 3, 4, 5
 
 
@@ -189,6 +191,7 @@ _PROTOS = {
     "pgpu_execute_groupby": (c_int, [c_voidp, c_i64p, c_i32, ctypes.POINTER(QueryC), c_voidp,
                                      ctypes.POINTER(c_voidp)]),
     "pgpu_plan_timing": (c_int, [c_voidp, c_f64p]),
+    "pgpu_plan_fp_sum_format": (c_int, [c_voidp, c_int, c_i32p]),
     "pgpu_plan_star_work": (c_int, [c_voidp, c_i64p]),
     "pgpu_plan_scan_geometry": (c_int, [c_voidp, c_i64p]),
     "pgpu_plan_star_metric_bytes": (c_int, [c_voidp, c_i64p]),

@@ -18,10 +18,12 @@ SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTI
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
            ("k_partition.hip", [], "k_partition"), ("k_hashfinal.hip", [], "k_hashfinal")] + \
     [("k_direct.hip", ["-DPGPU_MODE=%d" % m], "k_direct_%d" % m) for m in range(3)] + \
-    [("k_startree.hip", ["-DPGPU_MODE=%d" % m], "k_startree_%d" % m) for m in range(3)]
+    [("k_startree.hip", ["-DPGPU_MODE=%d" % m], "k_startree_%d" % m) for m in range(3)] + \
+    [("k_direct_fx.hip", ["-DPGPU_MODE=%d" % m], "k_direct_fx_%d" % m) for m in range(3)] + \
+    [("k_startree_fx.hip", ["-DPGPU_MODE=%d" % m], "k_startree_fx_%d" % m) for m in range(3)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h"]
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "scan_direct_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
 
@@ -177,6 +179,31 @@ def build_tile_split_check(force=False):
             raise RuntimeError("hipcc (tile_split_check) failed:\n" + res.stdout[-6000:])
     os.replace(SPLIT_CHECK_PATH + ".tmp", SPLIT_CHECK_PATH)
     return SPLIT_CHECK_PATH
+
+
+FX_CHECK_PATH = os.path.join(ROOT, "build", "fx_sum_check")
+
+
+def build_fx_sum_check(force=False):
+    """build/fx_sum_check: tools/fx_sum_check.cpp, which includes csrc/fx_sum.h and nothing else of the library, under
+    AddressSanitizer + UndefinedBehaviorSanitizer.  One compile, no library linked."""
+    src = os.path.join(ROOT, "tools", "fx_sum_check.cpp")
+    hdr = os.path.join(CSRC, "fx_sum.h")
+    if not force and os.path.exists(FX_CHECK_PATH) and \
+            all(os.path.getmtime(f) <= os.path.getmtime(FX_CHECK_PATH) for f in (src, hdr)):
+        return FX_CHECK_PATH
+    os.makedirs(os.path.dirname(FX_CHECK_PATH), exist_ok=True)
+    hipcc = _hipcc()
+    obj = os.path.join(ROOT, "build", "fx_sum_check.o")
+    for cmd in ([hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS +
+                ["-c", src, "-o", obj],
+                [hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined", obj,
+                 "-o", FX_CHECK_PATH + ".tmp"]):
+        res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if res.returncode != 0:
+            raise RuntimeError("hipcc (fx_sum_check) failed:\n" + res.stdout[-6000:])
+    os.replace(FX_CHECK_PATH + ".tmp", FX_CHECK_PATH)
+    return FX_CHECK_PATH
 
 
 if __name__ == "__main__":

@@ -84,6 +84,7 @@ extern "C" {
 int pgpu_plan_exchange_counts(pgpu_plan P, void* stream, int32_t nparts, int64_t* counts) try {
   PGPU_ABI_GUARD;
   TRY(exchangeable(P));
+  if (plan_has_fx(P)) return fx_decline("a cross-GPU exchange");
   if (nparts < 1 || nparts > 64 || !counts) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (P->merged_records >= 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "the table already holds merged records");
   DeviceGuard g(P->table->device);
@@ -110,6 +111,7 @@ int pgpu_plan_exchange_export(pgpu_plan P, void* stream, int32_t nparts, const i
                               int64_t cap) try {
   PGPU_ABI_GUARD;
   TRY(exchangeable(P));
+  if (plan_has_fx(P)) return fx_decline("a cross-GPU exchange");
   if ((int32_t)P->xchg_counts.size() != nparts || nparts < 1)
     return fail(PGPU_ERR_INVALID_ARGUMENT, "pgpu_plan_exchange_counts with %d parts first", nparts);
   int64_t total = 0;
@@ -140,6 +142,7 @@ int pgpu_plan_exchange_export(pgpu_plan P, void* stream, int32_t nparts, const i
 int pgpu_plan_exchange_merge(pgpu_plan P, void* stream, const int32_t* kinds, const void* d_records, int64_t n) try {
   PGPU_ABI_GUARD;
   TRY(exchangeable(P));
+  if (plan_has_fx(P)) return fx_decline("a cross-GPU exchange");
   P->exported = false;
   P->k8d_counts = false;
   if (n < 0 || (n > 0 && !d_records) || n > (INT64_C(1) << 40))  // the table below holds >= 2n slots
@@ -179,6 +182,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
   PGPU_ABI_GUARD;
   if (!r || nparts < 1 || nparts > (1 << 20) || !counts || (r->n > 0 && !rows))
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_has_fx(r)) return fx_decline("a cross-GPU exchange of rows");
   if ((int)r->slot_kind.size() != r->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
   uint32_t conv = 0;
   TRY(check_kinds(r->slot_kind, kinds, &conv));
@@ -210,6 +214,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
 int pgpu_result_merge_rows(pgpu_result tmpl, const int64_t* rows, int64_t n, const int32_t* kinds, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!tmpl || !out || n < 0 || (n > 0 && !rows)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_has_fx(tmpl)) return fx_decline("a cross-GPU merge of rows");
   if ((int)tmpl->slot_kind.size() != tmpl->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
   uint32_t conv = 0;
   TRY(check_kinds(tmpl->slot_kind, kinds, &conv));
@@ -472,6 +477,7 @@ int agree_status(pgpu::Comm* C, int rc) {
 int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_t* mode, int32_t* kinds) try {
   PGPU_ABI_GUARD;
   if (!P || !c || !mode) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (plan_has_fx(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
   pgpu::CommWaitScope wait_limits(P->end_time_ms, &P->cancel);
   const int N = c->impl->nranks;
   int local;
@@ -532,6 +538,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
                       void* d_shard, int64_t* key_begin, int64_t* key_count) try {
   PGPU_ABI_GUARD;
   if (!P || !c) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (plan_has_fx(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
   P->exported = false;  // the table changes: finalize reads it from the device
   P->k8d_counts = false;
   if (mode == PGPU_COMBINE_LOCAL) {
@@ -663,6 +670,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
 int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!r || !c || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_has_fx(r)) return fx_decline("a cross-GPU combine of rows");  // every rank's query carries the option
   pgpu::Comm* C = c->impl.get();
   const int N = C->nranks, me = C->rank;
   TRY(C->usable());

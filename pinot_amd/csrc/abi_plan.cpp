@@ -121,6 +121,10 @@ int pgpu_attach_startree(pgpu_table t, int64_t h, const pgpu_startree_desc* d) t
     st->metrics.push_back(a);
     st->mf_narrow.push_back(needs_f && ints32_f(d->metric_f64[m], d->num_docs));
     st->mc_narrow.push_back(needs_c && ints32_c(d->metric_i64[m], d->num_docs));
+    pgpu::FxRange fr;  // the pre-aggregated doubles as SUM operands (plans with PGPU_OPT_EXACT_FP_SUM, fx_sum.h)
+    if (needs_f && (a.fn == PGPU_AGG_SUM || a.fn == PGPU_AGG_AVG))
+      for (int64_t i = 0; i < d->num_docs; ++i) fx_range_add(&fr, d->metric_f64[m][i]);
+    st->mf_fx.push_back(fr);
     bytes += (needs_f ? (int64_t)d->num_docs * (st->mf_narrow.back() ? 4 : 8) : 0) +
              (needs_c ? (int64_t)d->num_docs * (st->mc_narrow.back() ? 4 : 8) : 0) + 32;
   }
@@ -367,6 +371,23 @@ int pgpu_plan_group_path(pgpu_plan P, int32_t* path) try {
   return 0;
 } PGPU_ABI_CATCH
 
+int pgpu_plan_fp_sum_format(pgpu_plan P, int agg, int32_t out[4]) try {
+  PGPU_ABI_GUARD;
+  if (!P || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  const pgpu_plan_s* K = P->composite && !P->parts.empty() ? P->parts[0].plan.get() : P;
+  if (agg < 0 || agg >= (int)K->agg_slot.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d of %zu", agg, K->agg_slot.size());
+  out[0] = out[1] = out[2] = out[3] = 0;
+  const int sl = K->agg_slot[agg];
+  if (K->fx && K->agg_fn[agg] != PGPU_AGG_COUNT && sl > 0 && sl < (int)K->slot_fx.size() && K->slot_fx[sl] == 0) {
+    const pgpu::FxFormat& f = K->slot_fmt[sl];
+    out[0] = f.mode;
+    out[1] = f.E;
+    out[2] = f.K;
+    out[3] = f.W;
+  }
+  return 0;
+} PGPU_ABI_CATCH
+
 int pgpu_plan_layout(pgpu_plan P, int32_t* num_slots, int64_t* num_keys, int32_t* kinds) try {
   PGPU_ABI_GUARD;
   if (!P) return fail(PGPU_ERR_INVALID_ARGUMENT, "null plan");
@@ -399,6 +420,8 @@ int pgpu_plan_create_execute(pgpu_table t, const int64_t* handles, int32_t nsegs
       return 0;
     }
   }
+  if (d_table && (q->options & PGPU_OPT_EXACT_FP_SUM))
+    return fail(PGPU_ERR_UNSUPPORTED, "external table with PGPU_OPT_EXACT_FP_SUM: ranks would have to agree on the fixed-point format first");
   StreamExec se;
   se.stream = stream ? reinterpret_cast<hipStream_t>(stream) : t->stream;
   se.d_table = d_table;
@@ -443,6 +466,7 @@ int pgpu_plan_execute(pgpu_plan P, void* stream, void* d_table) try {
     return 0;
   }
   if (P->hash && d_table) return fail(PGPU_ERR_UNSUPPORTED, "external table with a hash-mode plan");
+  if (d_table && plan_has_fx(P)) return fx_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
   return plan_execute_impl(P, s, d_table);
@@ -451,6 +475,7 @@ int pgpu_plan_execute(pgpu_plan P, void* stream, void* d_table) try {
 int pgpu_plan_finalize(pgpu_plan P, void* stream, const void* d_table, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!P || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (d_table && plan_has_fx(P)) return fx_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
   auto R = std::make_unique<pgpu_result_s>();
@@ -473,6 +498,7 @@ int pgpu_plan_finalize_range(pgpu_plan P, void* stream, const void* d_table_shar
   if (!P || !out || !d_table_shard || key_begin < 0 || key_count < 0 || key_begin + key_count > P->num_keys)
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (P->hash) return fail(PGPU_ERR_UNSUPPORTED, "hash-mode group tables are not key-range shardable");
+  if (plan_has_fx(P)) return fx_decline("a key-range shard");
   if (P->composite)
     return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit below the key space: finalize the whole table");
   DeviceGuard g(P->table->device);

@@ -50,7 +50,7 @@ int pgpu_plan_scan_geometry(pgpu_plan P, int64_t* out16) try {
   out16[12] = L.tiles;
   out16[13] = L.alone ? 1 : 0;
   out16[14] = L.declined ? 1 : 0;
-  out16[15] = 0;
+  out16[15] = scan_variant(P);
   return 0;
 } PGPU_ABI_CATCH
 
@@ -162,6 +162,7 @@ int pgpu_result_words_view(pgpu_result r, int agg, const uint64_t** out, int32_t
   PGPU_ABI_GUARD;
   if (!r || agg < -1 || agg >= r->num_aggs || !out || !form) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (r->compact.load(std::memory_order_acquire)) TRY(pgpu::result_expand(r));  // compact: columnar form first
+  if (r->fx_pending.load(std::memory_order_acquire)) pgpu::result_resolve_fx(r);  // RCONV_FX -> one double per group
   if (agg == -1) {  // the COUNT slot (AvgPair.count of every AVG)
     *out = r->slot(0);
     *form = RCONV_I64;
@@ -175,9 +176,12 @@ int pgpu_result_values(pgpu_result r, int agg, double* out) try {
   PGPU_ABI_GUARD;
   if (!r || agg < 0 || agg >= r->num_aggs || (!out && r->n)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (r->compact.load(std::memory_order_acquire)) TRY(pgpu::result_expand(r));  // compact: columnar form first
+  if (r->fx_pending.load(std::memory_order_acquire)) pgpu::result_resolve_fx(r);  // RCONV_FX -> one double per group
   const uint64_t* w = r->slot(r->agg_slot[agg]);
   switch (r->agg_conv[agg]) {
     case RCONV_I64: for (int64_t i = 0; i < r->n; ++i) out[i] = (double)(int64_t)w[i]; break;
+    case RCONV_FX:  // (digits left unresolved: a part of a composite plan is never handed out)
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d holds unmerged fixed-point digits", agg);
     case RCONV_F64: if (r->n) memcpy(out, w, (size_t)r->n * 8); break;
     default: for (int64_t i = 0; i < r->n; ++i) out[i] = key_double((int64_t)w[i]); break;
   }
@@ -194,6 +198,7 @@ int pgpu_result_values_i64(pgpu_result r, int agg, int64_t* out) try {
   PGPU_ABI_GUARD;
   if (!r || agg < 0 || agg >= r->num_aggs || (!out && r->n)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (r->compact.load(std::memory_order_acquire)) TRY(pgpu::result_expand(r));  // compact: columnar form first
+  if (r->fx_pending.load(std::memory_order_acquire)) pgpu::result_resolve_fx(r);  // RCONV_FX -> one double per group
   if (r->agg_conv[agg] != RCONV_I64) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d is floating point", agg);
   if (r->n) memcpy(out, r->slot(r->agg_slot[agg]), (size_t)r->n * 8);
   return 0;

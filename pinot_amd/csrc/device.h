@@ -7,6 +7,7 @@
 
 #include <utility>
 
+#include "fx_sum.h"
 #include "internal.h"
 
 namespace pgpu {
@@ -468,6 +469,9 @@ __device__ __forceinline__ int64_t hash_slot(unsigned long long* __restrict__ ke
   return -1;
 }
 
+// The split of the SLOT_SUM_FX slots: p is the KParamsFx of an FX instance (the only callers).
+__device__ __forceinline__ const KFxSplit& fx_split(const KParams& p) { return static_cast<const KParamsFx&>(p).fx; }
+
 template <int MODE>
 __device__ __forceinline__ void accumulate(uint64_t* __restrict__ base, int64_t idx, int kind, int64_t ikey,
                                            double dval) {
@@ -572,7 +576,9 @@ __device__ __forceinline__ int64_t slot_fold(int kind, int64_t a, int64_t v) {
 // SIMPLE (KParams of a "simple" dense plan, plan_create_impl): every group-by column's dictionary is a contiguous run of
 // the global one in every segment (no LUT), every aggregated column is an integer of consecutive values (no
 // dictionary lookup) and no slot sums doubles -- the gathers compile away, and with them their registers.
-template <int MODE, int NB, bool SIMPLE = false>
+// FX (instances of plans with PGPU_OPT_EXACT_FP_SUM): SLOT_SUM_FX slots -- the operand's double is split into its
+// fixed-point digit (fx_sum.h, KParams.fx_*) and added as an integer SUM.
+template <int MODE, int NB, bool SIMPLE = false, bool FX = false>
 __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView (&S)[NB], const int64_t (&doc)[NB],
                                                 const bool (&ok)[NB], uint64_t* __restrict__ tbl, int64_t G) {
   int64_t key[NB];
@@ -645,6 +651,11 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
       if (!SIMPLE && kind == SLOT_SUM_F64) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) dval[b] = gp(S[b].cols[col].dval)[vi[b]];
+      } else if (FX && kind == SLOT_SUM_FX) {
+        const KFxSplit& fx = fx_split(p);
+        const int sh = fx.sh[s], K = fx.k[s], j = fx.j[s];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) ikey[b] = fx_digit(gp(S[b].cols[col].dval)[vi[b]], sh, K, j);
       } else {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
@@ -653,13 +664,15 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
         }
       }
     }
+    // an FX digit accumulates as an integer SUM from here on
+    const int akind = FX && kind == SLOT_SUM_FX ? (int)SLOT_SUM_I64 : kind;
     if (G == 1) {  // single row: fold the lane's docs, then the wave
-      int64_t cnt = 0, iacc = slot_identity(kind);
+      int64_t cnt = 0, iacc = slot_identity(akind);
       double facc = 0.0;
 #pragma unroll
       for (int b = 0; b < NB; ++b)
-        if (ok[b]) { ++cnt; iacc = slot_fold(kind, iacc, ikey[b]); facc += dval[b]; }
-      accumulate_wave(tbl + s, kind, cnt, iacc, facc);
+        if (ok[b]) { ++cnt; iacc = slot_fold(akind, iacc, ikey[b]); facc += dval[b]; }
+      accumulate_wave(tbl + s, akind, cnt, iacc, facc);
       continue;
     }
     if ((MODE == MODE_LDS || MODE == MODE_HASH) && p.pack_slot >= 0) {  // KParams.pack_slot: the pack slot adds both
@@ -675,7 +688,7 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b)
-      if (live[b]) accumulate<MODE>(tbl, (int64_t)s * G + idx[b], kind, ikey[b], dval[b]);
+      if (live[b]) accumulate<MODE>(tbl, (int64_t)s * G + idx[b], akind, ikey[b], dval[b]);
   }
 }
 
@@ -813,7 +826,7 @@ __device__ __forceinline__ void accumulate16_f(uint64_t* __restrict__ row, const
 }
 
 // One half (docs H..H+15 of the lane's group) of aggregate_group.
-template <int MODE, int H, bool SIMPLE = false>
+template <int MODE, int H, bool SIMPLE = false, bool FX = false>
 __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
                                                uint64_t* __restrict__ tbl, int64_t G) {
   const uint32_t m = (mask >> H) & 0xFFFFu;
@@ -855,10 +868,12 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
     }
     const int col = p.slot_col[s];
     int e = s + 1;
-    bool need_i = kind != SLOT_SUM_F64, need_f = kind == SLOT_SUM_F64;
+    // (FX: a SLOT_SUM_FX slot reads the doubles as a float64 SUM does)
+    auto is_f = [](int k) { return k == SLOT_SUM_F64 || (FX && k == SLOT_SUM_FX); };
+    bool need_i = !is_f(kind), need_f = is_f(kind);
     while (e < p.num_slots && p.slot_kind[e] != SLOT_COUNT && p.slot_col[e] == col) {
-      need_i |= p.slot_kind[e] != SLOT_SUM_F64;
-      need_f |= p.slot_kind[e] == SLOT_SUM_F64;
+      need_i |= !is_f(p.slot_kind[e]);
+      need_f |= is_f(p.slot_kind[e]);
       ++e;
     }
     KColC& c = S.cols[col];
@@ -882,7 +897,7 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
       }
       for (int r = s; r < e; ++r) {
         const int kr = p.slot_kind[r];
-        if (kr == SLOT_SUM_F64) continue;
+        if (is_f(kr)) continue;
         uint64_t* __restrict__ row = tbl + (int64_t)r * G;
         if (G == 1) {
           int64_t acc = slot_identity(kr);
@@ -921,8 +936,24 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
 #endif
 #endif
       for (int r = s; r < e; ++r) {
-        if (p.slot_kind[r] != SLOT_SUM_F64) continue;
+        if (!is_f(p.slot_kind[r])) continue;
         uint64_t* __restrict__ row = tbl + (int64_t)r * G;
+        if (FX && p.slot_kind[r] == SLOT_SUM_FX) {  // the 16 doubles' digits of this slot, added as an integer SUM
+          const KFxSplit& fx = fx_split(p);
+          const int sh = fx.sh[r], K = fx.k[r], j = fx.j[r];
+          int64_t d[16];
+#pragma unroll
+          for (int i = 0; i < 16; ++i) d[i] = fx_digit(v[i], sh, K, j);  // unmatched docs: v = 0, digit 0
+          if (G == 1) {
+            int64_t acc = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc += d[i];
+            accumulate_wave(row, SLOT_SUM_I64, __popc(m), acc, 0.0);
+          } else {
+            accumulate16_i<MODE>(row, key, m, SLOT_SUM_I64, d);
+          }
+          continue;
+        }
         if (G == 1) {
           double acc = 0.0;
 #pragma unroll
@@ -941,16 +972,16 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
 // Aggregates the matched docs (bits of `mask`) of this lane's 32-doc group `group` of segment S, 16 docs at a
 // time.  Dense key spaces only (MODE_LDS / MODE_GLOBAL: composite keys < 2^31).  Docs beyond numDocs decode from
 // the zero padding to dictId 0 (in bounds) and are never in `mask`.
-template <int MODE, bool SIMPLE = false>
+template <int MODE, bool SIMPLE = false, bool FX = false>
 __device__ __forceinline__ void aggregate_group(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
                                                 uint64_t* __restrict__ tbl, int64_t G) {
   // wave-uniform conditions: the single-row (G == 1) fold inside uses cross-lane shuffles
-  if (__any((mask & 0xFFFFu) != 0u)) aggregate_half<MODE, 0, SIMPLE>(p, S, group, mask, tbl, G);
-  if (__any((mask >> 16) != 0u)) aggregate_half<MODE, 16, SIMPLE>(p, S, group, mask, tbl, G);
+  if (__any((mask & 0xFFFFu) != 0u)) aggregate_half<MODE, 0, SIMPLE, FX>(p, S, group, mask, tbl, G);
+  if (__any((mask >> 16) != 0u)) aggregate_half<MODE, 16, SIMPLE, FX>(p, S, group, mask, tbl, G);
 }
 
 // Drains a wave's queue of matched (segment, doc) entries: 2 per lane per batch.
-template <int MODE, bool SIMPLE = false>
+template <int MODE, bool SIMPLE = false, bool FX = false>
 __device__ __forceinline__ void flush_wave_queue(const KParams& p, const uint32_t* qd, const uint32_t* qs, uint32_t qn,
                                                  int lane, uint64_t* __restrict__ tbl, int64_t G) {
   for (uint32_t base = 0; base < qn; base += 128) {
@@ -962,7 +993,7 @@ __device__ __forceinline__ void flush_wave_queue(const KParams& p, const uint32_
     doc[0] = ok[0] ? qd[i0] : 0;
     doc[1] = ok[1] ? qd[i1] : 0;
     const SegView S[2] = {seg_view(p, ok[0] ? (int)qs[i0] : (int)qs[0]), seg_view(p, ok[1] ? (int)qs[i1] : (int)qs[0])};
-    aggregate_batch<MODE, 2, SIMPLE>(p, S, doc, ok, tbl, G);
+    aggregate_batch<MODE, 2, SIMPLE, FX>(p, S, doc, ok, tbl, G);
   }
 }
 

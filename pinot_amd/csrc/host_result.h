@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/pinotgpu.h"
+#include "fx_sum.h"
 #include "host_common.h"
 
 namespace pgpu {
@@ -71,6 +72,9 @@ struct pgpu_result_s;
 namespace pgpu {
 // Builds the columnar form of a result held in compact form (rt_exec.cpp); 0 or a PGPU_ERR_* status.
 int result_expand(pgpu_result_s* r);
+// Converts the RCONV_FX aggregations of a result in columnar form (rt_exec.cpp): the W digit sums of each group become
+// its one double, stored in the first digit's slot, and the aggregation reads as RCONV_F64 from then on.
+void result_resolve_fx(pgpu_result_s* r);
 }  // namespace pgpu
 
 struct pgpu_result_s {
@@ -86,6 +90,11 @@ struct pgpu_result_s {
   std::vector<int32_t> agg_slot;          // per aggregation: its slot
   std::vector<int32_t> slot_kind;         // per slot: how its words accumulate (internal.h SLOT_*)
   std::vector<uint8_t> agg_conv;          // per aggregation: how the slot word reads (RCONV_*)
+  // RCONV_FX aggregations (plans with PGPU_OPT_EXACT_FP_SUM): the format of the W digit sums in the W slots from
+  // agg_slot on (fx_sum.h).  fx_pending: they are converted on the first access to slot() (the parts of a composite
+  // plan stay digits until their rows are merged).
+  std::vector<pgpu::FxFormat> agg_fx;
+  std::atomic<bool> fx_pending{false};
   int64_t stats[6] = {0, 0, 0, 0, 0, 0};
   // what the rows are (DataTable / trimming): table columns and types of the group-by keys, per aggregation its
   // function and table column (-1: COUNT(*)), and numGroupsLimitReached
@@ -132,10 +141,12 @@ struct pgpu_result_s {
   }
   uint64_t* slot(int s) {
     if (compact.load(std::memory_order_acquire)) pgpu::result_expand(this);
+    if (fx_pending.load(std::memory_order_acquire)) pgpu::result_resolve_fx(this);
     return slot_raw(s);
   }
 };
-enum { RCONV_I64 = 0, RCONV_F64 = 1, RCONV_KEY_F64 = 2 };
+// RCONV_FX: fixed-point digit sums (agg_fx), one double per group once resolved (then RCONV_F64).
+enum { RCONV_I64 = 0, RCONV_F64 = 1, RCONV_KEY_F64 = 2, RCONV_FX = 3 };
 
 namespace pgpu {
 

@@ -47,7 +47,12 @@ enum LeafKind : int32_t { LEAF_NONE = 0, LEAF_ALL = 1, LEAF_RANGE = 2, LEAF_SET 
                           LEAF_RAW_RANGE = 6, LEAF_RAW_IN = 7, LEAF_BITDIR = 8 };
 constexpr int kLeafKinds = 9;
 enum OpCode : int32_t { OP_LEAF = 0, OP_AND = 1, OP_OR = 2, OP_NOT = 3 };
-enum SlotKind : int32_t { SLOT_COUNT = 0, SLOT_SUM_I64 = 1, SLOT_SUM_F64 = 2, SLOT_MIN_KEY = 3, SLOT_MAX_KEY = 4 };
+// SLOT_SUM_FX (plans with PGPU_OPT_EXACT_FP_SUM): one fixed-point digit of a FLOAT / DOUBLE sum (fx_sum.h).  Only the
+// scan kernels' FX instances see the kind (KParams / KStarParams.slot_kind): they split the operand and add the digit
+// as an integer.  To everything after the accumulate -- table init, slab fold, compactions, widths, merges -- the
+// word is an int64 SUM, and the plan's own slot_kind says SLOT_SUM_I64 (pgpu_plan_s::slot_fx tells the digits apart).
+enum SlotKind : int32_t { SLOT_COUNT = 0, SLOT_SUM_I64 = 1, SLOT_SUM_F64 = 2, SLOT_MIN_KEY = 3, SLOT_MAX_KEY = 4,
+                          SLOT_SUM_FX = 5 };
 enum Mode : int32_t { MODE_LDS = 0, MODE_GLOBAL = 1, MODE_HASH = 2 };
 
 // One predicate leaf evaluated against one segment: dictId in [lo, lo + span) (RANGE), bit set in `set`
@@ -167,6 +172,19 @@ struct KParams {
   int32_t claim_tiles;
 };
 
+// SLOT_SUM_FX slots (fx_sum.h): slot s holds digit j[s] of its column's operands in a format of k[s]-bit digits;
+// sh[s] = K - E, the first ldexp of the split.
+struct KFxSplit {
+  int16_t sh[kMaxSlots];
+  int8_t k[kMaxSlots];
+  int8_t j[kMaxSlots];
+};
+// The parameters of the scan's FX instances (filter_groupby_fx_kernel): KParams and the split.  A type of its own, so
+// that the kernel arguments of every other instance stay what they were.
+struct KParamsFx : KParams {
+  KFxSplit fx;
+};
+
 // leaf_masks_kernel work item: groups [group0, group0 + 256) of plan record `rec`; its leaves' masks go to
 // out + out_word + leaf * ceil(numDocs / 32) (STATS_GENERIC segments, replayed on the host).
 struct KMaskJob {
@@ -225,6 +243,7 @@ struct KStarParams {
   unsigned long long* stats;              // [0] docs matched, [1] entries scanned in filter, [3] star-tree
                                           // documents read (positions of the emitted ranges), [5] timed out
   uint64_t deadline;                      // as KParams.deadline
+  KFxSplit fx;                            // SLOT_SUM_FX slots (the FX instance alone reads it)
 };
 
 // ---------------------------------------------------------------------------------------------- partitioned
@@ -366,8 +385,13 @@ int launch_table_init(uint64_t* table, const int32_t* slot_kind, int32_t num_slo
 // 0 = none) has passed.
 int launch_expand_tiles(const uint8_t* segs, int32_t seg_stride, int32_t num_segs, int32_t* tile_seg,
                         uint64_t deadline, unsigned long long* stats, void* stream);
-// variant: 0 sparse instance, 1 dense, 2 dense "simple" (no LUT / dictionary gathers, no double sums)
+// variant: 0 sparse instance, 1 dense, 2 dense "simple" (no LUT / dictionary gathers, no double sums), 3 - 5 the
+// sparse specialisations (k_direct.hip); 6 / 7: the sparse / dense instance of plans with SLOT_SUM_FX slots
+// (k_direct_fx.hip)
+constexpr int kVariantFxSparse = 6, kVariantFxDense = 7;
 int launch_filter_groupby(const KParams& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
+// The FX instances (variant kVariantFxSparse / kVariantFxDense).
+int launch_filter_groupby_fx(const KParamsFx& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
 // Resident workgroups per CU of the direct kernel instance (< 0: query failed).
 int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes);
 int launch_reduce_slabs(const uint64_t* slab, const int32_t* slot_kind_dev, int32_t num_slots, int64_t num_keys,
@@ -448,7 +472,8 @@ constexpr int kStarMaxSegs = 4096;  // star-tree segments per K6 launch (their g
 int launch_deadline_gate(uint64_t deadline, unsigned long long* stats, void* stream);
 int launch_startree_traverse(const KStarSeg* segs, int32_t num_segs, int64_t* seg_total, uint64_t deadline,
                              unsigned long long* stats, void* stream);
-int launch_startree_scan(const KStarParams& p, int mode, size_t lds_bytes, void* stream);
+// fx: the instance for plans with SLOT_SUM_FX slots (k_startree_fx.hip)
+int launch_startree_scan(const KStarParams& p, int mode, bool fx, size_t lds_bytes, void* stream);
 // Synthetic generator (bench): positions of generated values in the sorted domain + presence bitmap, then pack.
 int launch_gen_positions(int32_t kind, uint64_t seed, int64_t lo, int64_t span, const double* cdf,
                          const int32_t* code_to_pos, int32_t n_codes, int64_t row0, int32_t num_docs,

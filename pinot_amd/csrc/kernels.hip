@@ -90,8 +90,10 @@ struct SlotKinds {
   int32_t k[kMaxSlots];
 };
 // Each block folds 8 table words; the 32 lanes of a word take every 32nd slab and their partials are combined
-// in lane order: the fold itself has a fixed order, but the LDS slabs it reads were summed with atomicAdd(double),
-// so FLOAT/DOUBLE sums vary in their last bits from run to run (integer slots are exact).
+// in lane order: the fold itself has a fixed order, but the SLOT_SUM_F64 words it reads were summed with
+// atomicAdd(double) in the order the scan's atomics landed, so those sums can differ in their last bits between runs.
+// Integer slots are exact -- among them the fixed-point digits of FLOAT/DOUBLE sums of plans with
+// PGPU_OPT_EXACT_FP_SUM (fx_sum.h), whose results are therefore bit-reproducible.
 __device__ __forceinline__ void reduce_slabs_block(int64_t blk, const uint64_t* __restrict__ slab,
                                                    const SlotKinds& kinds, int64_t num_keys, int32_t num_slots,
                                                    int32_t num_blocks, uint64_t* __restrict__ out) {
@@ -837,27 +839,30 @@ int launch_hash_unpack(uint64_t* table, const unsigned long long* hash_keys, int
   return PGPU_HIP_OK(hipGetLastError());
 }
 
-// One object per (kernel family, mode): k_direct.hip / k_startree.hip compiled with -DPGPU_MODE=0,1,2.
-int launch_direct_mode0(const KParams& p, int variant, int grid, size_t lds_bytes, void* stream);
-int launch_direct_mode1(const KParams& p, int variant, int grid, size_t lds_bytes, void* stream);
-int launch_direct_mode2(const KParams& p, int variant, int grid, size_t lds_bytes, void* stream);
-int occupancy_direct_mode0(int variant, size_t lds_bytes);
-int occupancy_direct_mode1(int variant, size_t lds_bytes);
-int occupancy_direct_mode2(int variant, size_t lds_bytes);
+// One object per (kernel family, mode): k_direct.hip / k_startree.hip compiled with -DPGPU_MODE=0,1,2, and the
+// instances for plans with SLOT_SUM_FX slots beside them (k_direct_fx.hip / k_startree_fx.hip).
+#define PGPU_MODE_DECLS(M)                                                                                   \
+  int launch_direct_mode##M(const KParams& p, int variant, int grid, size_t lds_bytes, void* stream);        \
+  int occupancy_direct_mode##M(int variant, size_t lds_bytes);                                               \
+  int launch_direct_fx_mode##M(const KParamsFx& p, int variant, int grid, size_t lds_bytes, void* stream);   \
+  int occupancy_direct_fx_mode##M(int variant, size_t lds_bytes);                                            \
+  int launch_startree_scan_mode##M(const KStarParams& p, size_t lds_bytes, void* stream);                    \
+  int launch_startree_scan_fx_mode##M(const KStarParams& p, size_t lds_bytes, void* stream);
+PGPU_MODE_DECLS(0)
+PGPU_MODE_DECLS(1)
+PGPU_MODE_DECLS(2)
+#undef PGPU_MODE_DECLS
 
-int launch_startree_scan_mode0(const KStarParams& p, size_t lds_bytes, void* stream);
-int launch_startree_scan_mode1(const KStarParams& p, size_t lds_bytes, void* stream);
-int launch_startree_scan_mode2(const KStarParams& p, size_t lds_bytes, void* stream);
-
-int launch_startree_scan(const KStarParams& p, int mode, size_t lds_bytes, void* stream) {
+int launch_startree_scan(const KStarParams& p, int mode, bool fx, size_t lds_bytes, void* stream) {
   switch (mode) {
-    case MODE_LDS: return launch_startree_scan_mode0(p, lds_bytes, stream);
-    case MODE_GLOBAL: return launch_startree_scan_mode1(p, lds_bytes, stream);
-    default: return launch_startree_scan_mode2(p, lds_bytes, stream);
+    case MODE_LDS: return fx ? launch_startree_scan_fx_mode0(p, lds_bytes, stream) : launch_startree_scan_mode0(p, lds_bytes, stream);
+    case MODE_GLOBAL: return fx ? launch_startree_scan_fx_mode1(p, lds_bytes, stream) : launch_startree_scan_mode1(p, lds_bytes, stream);
+    default: return fx ? launch_startree_scan_fx_mode2(p, lds_bytes, stream) : launch_startree_scan_mode2(p, lds_bytes, stream);
   }
 }
 
 int launch_filter_groupby(const KParams& p, int mode, int variant, int grid, size_t lds_bytes, void* stream) {
+  if (variant >= kVariantFxSparse) return -1;  // the FX instances take a KParamsFx (launch_filter_groupby_fx)
   switch (mode) {
     case MODE_LDS: return launch_direct_mode0(p, variant, grid, lds_bytes, stream);
     case MODE_GLOBAL: return launch_direct_mode1(p, variant, grid, lds_bytes, stream);
@@ -865,11 +870,20 @@ int launch_filter_groupby(const KParams& p, int mode, int variant, int grid, siz
   }
 }
 
-int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes) {
+int launch_filter_groupby_fx(const KParamsFx& p, int mode, int variant, int grid, size_t lds_bytes, void* stream) {
   switch (mode) {
-    case MODE_LDS: return occupancy_direct_mode0(variant, lds_bytes);
-    case MODE_GLOBAL: return occupancy_direct_mode1(variant, lds_bytes);
-    default: return occupancy_direct_mode2(variant, lds_bytes);
+    case MODE_LDS: return launch_direct_fx_mode0(p, variant, grid, lds_bytes, stream);
+    case MODE_GLOBAL: return launch_direct_fx_mode1(p, variant, grid, lds_bytes, stream);
+    default: return launch_direct_fx_mode2(p, variant, grid, lds_bytes, stream);
+  }
+}
+
+int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes) {
+  const bool fx = variant >= kVariantFxSparse;
+  switch (mode) {
+    case MODE_LDS: return fx ? occupancy_direct_fx_mode0(variant, lds_bytes) : occupancy_direct_mode0(variant, lds_bytes);
+    case MODE_GLOBAL: return fx ? occupancy_direct_fx_mode1(variant, lds_bytes) : occupancy_direct_mode1(variant, lds_bytes);
+    default: return fx ? occupancy_direct_fx_mode2(variant, lds_bytes) : occupancy_direct_mode2(variant, lds_bytes);
   }
 }
 

@@ -370,6 +370,10 @@ struct Column {
   // forward index), raw_min / raw_max bound integer sums
   bool raw = false;
   int64_t raw_min = 0, raw_max = 0;
+  // the range of the column's values as SUM operands (fx_sum.h: E, L, all finite): of a raw FLOAT / DOUBLE column's
+  // docs, taken when they are decoded at pin time; of a dictionary on first use (fx_known, under the table mutex)
+  pgpu::FxRange fx;
+  bool fx_known = false;
 };
 
 // A pinned star-tree (pgpu_attach_startree): one device block holding the nodes, the star-tree documents'
@@ -387,6 +391,7 @@ struct StarTreeDev {
   // per metric: its device array holds int32 values (every pre-aggregated value an integer of int32 range; the
   // kernel widens them exactly) -- half the bytes per star-tree document
   std::vector<uint8_t> mf_narrow, mc_narrow;
+  std::vector<pgpu::FxRange> mf_fx;  // per metric: the range of its pre-aggregated doubles (fx_sum.h), taken at attach
   int dim_of(int col) const {
     for (int d = 0; d < num_dims; ++d) if (dim_cols[d] == col) return d;
     return -1;
@@ -665,6 +670,16 @@ struct pgpu_plan_s {
   int64_t num_keys = 0;                   // dense G or hash capacity
   int mode = MODE_LDS;
   std::vector<int32_t> slot_kind, slot_col, slot_tcol;
+  // PGPU_OPT_EXACT_FP_SUM: the FLOAT / DOUBLE sums of the plan are W adjacent slots of fixed-point digits (fx_sum.h).
+  // slot_fx: per slot its digit index, -1 for every other slot; slot_fmt: the digit's format.  slot_kind says
+  // SLOT_SUM_I64 for a digit -- that is what its word is to everything after the scan's accumulate; the scan kernels
+  // alone see SLOT_SUM_FX (exec_prologue).  fx: the plan has such slots.  fx_part: a part of a composite plan (its
+  // result keeps the digits for the merge).  fx_scope: the segments whose operands and docs the formats cover when
+  // they are more than the plan's own (the parts of a composite plan share their formats).
+  bool fx = false, fx_part = false;
+  std::vector<int32_t> slot_fx;
+  std::vector<pgpu::FxFormat> slot_fmt;
+  std::vector<Segment*> fx_scope;
   std::vector<int32_t> agg_fn, agg_slot, agg_col;   // per aggregation: fn, value slot (or -1), table column
   int num_projected = 0;
   // per-segment compiled data
@@ -807,6 +822,24 @@ struct pgpu_plan_s {
   int64_t star_metric_bytes = -1;  // K6's metric-array sectors (64 B) holding a matched doc, x 64 (small tables)
   int64_t star_docs_read = 0;                                // star-tree documents K6 read (after finalize)
 };
+
+// Plans / results carrying fixed-point FLOAT / DOUBLE sums (PGPU_OPT_EXACT_FP_SUM): the cross-GPU entry points decline
+// them -- the ranks' formats (E, K, W) come from their own segments and would have to be agreed on first.
+inline bool plan_has_fx(const pgpu_plan_s* P) {
+  if (P->fx) return true;
+  for (const auto& part : P->parts)
+    if (part.plan && part.plan->fx) return true;
+  return false;
+}
+inline bool result_has_fx(const pgpu_result_s* r) {
+  for (const pgpu::FxFormat& f : r->agg_fx)
+    if (f.mode != pgpu::FX_NONE) return true;
+  return false;
+}
+inline int fx_decline(const char* what) {
+  return fail(PGPU_ERR_UNSUPPORTED, "%s with PGPU_OPT_EXACT_FP_SUM: the ranks would have to agree on the "
+                         "fixed-point format (E, K, W) first", what);
+}
 
 namespace pgpu {
 

@@ -412,6 +412,8 @@ int parse_raw_column(int type, const pgpu_column_buffers& cb, int32_t num_docs, 
   col->fwd_bytes = cb.fwd_len;
   col->raw_min = out->lo;
   col->raw_max = out->hi;
+  for (double v : out->val) fx_range_add(&col->fx, v);  // the docs' values as SUM operands (fx_sum.h)
+  col->fx_known = true;
   return 0;
 }
 

@@ -342,6 +342,8 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
 #endif
   kp.num_slots = nslots;
   for (int sl = 0; sl < nslots; ++sl) { kp.slot_kind[sl] = P->slot_kind[sl]; kp.slot_col[sl] = P->slot_col[sl]; }
+  for (int sl = 0; sl < nslots && P->fx; ++sl)  // the scan's view of the fixed-point digits (fx_split has the rest)
+    if (P->slot_fx[sl] >= 0) kp.slot_kind[sl] = SLOT_SUM_FX;
   kp.pair_leaves = 1;
   dense_lds_forms(P, &kp.pack_slot, &kp.narrow);
   kp.pack_shift = P->pack_shift;
@@ -452,7 +454,22 @@ int check_launch_inputs(const pgpu_plan_s* P, hipStream_t stream, const ExecCtx&
 
 // The scan instance a plan launches (k_direct.hip): 2 dense "simple", 1 dense, 3 index + scan pair, 5 / 4 pure-AND
 // sparse with 4 / 2-doc lane batches, 0 the general sparse one.
+// The split parameters of the plan's SLOT_SUM_FX slots (KParamsFx / KStarParams.fx).
+KFxSplit fx_split(const pgpu_plan_s* P) {
+  KFxSplit x;
+  memset(&x, 0, sizeof x);
+  for (size_t sl = 0; sl < P->slot_fx.size() && sl < (size_t)kMaxSlots && P->fx; ++sl) {
+    if (P->slot_fx[sl] < 0) continue;
+    const FxFormat& f = P->slot_fmt[sl];
+    x.sh[sl] = (int16_t)(f.K - f.E);
+    x.k[sl] = (int8_t)f.K;
+    x.j[sl] = (int8_t)P->slot_fx[sl];
+  }
+  return x;
+}
+
 int scan_variant(const pgpu_plan_s* P) {
+  if (P->fx) return P->dense ? kVariantFxDense : kVariantFxSparse;  // plans with SLOT_SUM_FX slots: their own instances
   return P->dense_simple ? 2 : P->dense ? 1 : P->pair_variant ? 3 : P->fast_wide ? 5 : P->fast_variant ? 4 : 0;
 }
 
@@ -700,9 +717,17 @@ int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const Laun
     for (int s = 0; s < kMaxCuSlots; ++s) P->last_scan.slot_w[s] = kp.slot_n ? kp.slot_w[s] : 0;
     P->last_scan.alone = P->alone;
     P->last_scan.declined = !fits;
-    const int rc = launch_filter_groupby(kp, P->mode,
-                                         scan_variant(P),
-                                         grid, P->lds_bytes, stream);
+    int rc;
+    if (P->fx) {  // the FX instances: the launch's parameters and the split of the fixed-point slots
+      KParamsFx kf;
+      static_cast<KParams&>(kf) = kp;
+      kf.fx = fx_split(P);
+      rc = launch_filter_groupby_fx(kf, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
+    } else {
+      rc = launch_filter_groupby(kp, P->mode,
+                                 scan_variant(P),
+                                 grid, P->lds_bytes, stream);
+    }
     if (rc) return fail(PGPU_ERR_DEVICE, "scan launch failed: %s", hipGetErrorString(hipGetLastError()));
     X.mark("scan launched");
     if (wg_times) TRY(diag_wg_times_report(P->table, kp, grid, stream));
@@ -776,9 +801,10 @@ int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
     sp.num_keys_total = P->num_keys;
     sp.num_slots = nslots;
     for (int sl = 0; sl < nslots; ++sl) {
-      sp.slot_kind[sl] = P->slot_kind[sl];
+      sp.slot_kind[sl] = X.kp.slot_kind[sl];  // (SLOT_SUM_FX where the plan has fixed-point digits)
       sp.slot_int[sl] = sl > 0 && P->slot_tcol[sl] >= 0 && is_int_type(P->table->types[P->slot_tcol[sl]]) ? 1 : 0;
     }
+    sp.fx = fx_split(P);
     sp.table = kp.table;
     sp.slab = P->mode == MODE_LDS ? kp.slab + X.slabs_used * words : nullptr;
     sp.hash_keys = kp.hash_keys;
@@ -791,7 +817,7 @@ int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
       sp.num_segs = (int)std::min<int64_t>(kStarMaxSegs, (int64_t)recs.size() - s0);
       sp.seg_total = seg_total + s0;
       if (P->mode == MODE_LDS) sp.slab = kp.slab + (X.slabs_used + (int64_t)b * P->star_chunks) * words;
-      if (launch_startree_scan(sp, P->mode, P->star_lds_bytes, stream))
+      if (launch_startree_scan(sp, P->mode, P->fx, P->star_lds_bytes, stream))
         return fail(PGPU_ERR_DEVICE, "star-tree scan launch failed: %s", hipGetErrorString(hipGetLastError()));
       X.mark("K6 launched");
     }
@@ -1208,6 +1234,21 @@ int plan_finalize_impl(pgpu_plan_s* P, hipStream_t stream, const void* d_table, 
     else
       R->agg_conv[a] = is_int_type(P->table->types[P->agg_col[a]]) ? RCONV_I64 : RCONV_KEY_F64;
   }
+  // fixed-point FLOAT / DOUBLE sums (PGPU_OPT_EXACT_FP_SUM): W digit sums from the aggregation's slot on, converted to
+  // the one double on the result's first read -- after the merge for the parts of a composite plan
+  R->agg_fx.clear();
+  if (P->fx) {
+    R->agg_fx.assign(na, FxFormat{});
+    bool any = false;
+    for (int a = 0; a < na; ++a) {
+      const int sl = P->agg_slot[a];
+      if (P->agg_fn[a] == PGPU_AGG_COUNT || sl < 0 || P->slot_fx[sl] < 0) continue;
+      R->agg_fx[a] = P->slot_fmt[sl];
+      R->agg_conv[a] = RCONV_FX;
+      any = true;
+    }
+    R->fx_pending.store(any && !P->fx_part, std::memory_order_release);
+  }
   int64_t generic_entries = 0;
   if (!P->generic.empty()) {  // the leaves' bitmaps were copied into maskstage by the (synchronised) stream
     const uint32_t* words = reinterpret_cast<const uint32_t*>(P->scratch->maskstage.p);
@@ -1238,6 +1279,34 @@ int plan_finalize_impl(pgpu_plan_s* P, hipStream_t stream, const void* d_table, 
 }
 
 }  // namespace pgpu
+
+void pgpu::result_resolve_fx(pgpu_result_s* R) {
+  if (R->compact.load(std::memory_order_acquire) && result_expand(R)) return;
+  std::lock_guard<std::mutex> g(R->expand_mu);
+  if (!R->fx_pending.load(std::memory_order_acquire)) return;
+  for (int a = 0; a < R->num_aggs && a < (int)R->agg_fx.size(); ++a) {
+    if (R->agg_conv[a] != RCONV_FX) continue;
+    const FxFormat f = R->agg_fx[a];
+    const int s0 = R->agg_slot[a];
+    bool done = false;  // SUM and AVG of a column share their digit slots: converted once
+    for (int b = 0; b < a; ++b) done |= R->agg_slot[b] == s0 && b < (int)R->agg_fx.size() && R->agg_fx[b].mode != FX_NONE;
+    if (done) {
+      R->agg_conv[a] = RCONV_F64;
+      continue;
+    }
+    uint64_t* out = R->slot_raw(s0);
+    const uint64_t* d1 = R->slot_raw(s0 + 1);
+    const uint64_t* d2 = f.W > 2 ? R->slot_raw(s0 + 2) : nullptr;
+    for (int64_t i = 0; i < R->n; ++i) {
+      const int64_t digits[kFxMaxDigits] = {(int64_t)out[i], (int64_t)d1[i], d2 ? (int64_t)d2[i] : 0};
+      const double v = fx_result(digits, f);
+      memcpy(&out[i], &v, 8);
+    }
+    R->agg_conv[a] = RCONV_F64;
+    if (s0 < (int)R->slot_kind.size()) R->slot_kind[s0] = SLOT_SUM_F64;
+  }
+  R->fx_pending.store(false, std::memory_order_release);
+}
 
 // Columnar form of a compact result: rows are the bitmap's set bits in key order; each block of 4096 bitmap words is
 // decoded by one task of the host pool (a prefix of its popcounts gives its first row).

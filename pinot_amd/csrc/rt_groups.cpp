@@ -61,6 +61,15 @@ int split_for_groups_limit(pgpu_table_s* t, const int64_t* handles, int32_t nseg
     part.truncate = truncate;
     std::vector<int64_t> hs;
     for (int32_t i : idx) hs.push_back(handles[i]);
+    if (q->options & PGPU_OPT_EXACT_FP_SUM) {
+      // the parts' digit sums are merged as integers: one fixed-point format over the segments and docs of them all
+      part.plan->fx_part = true;
+      std::lock_guard<std::mutex> g(t->mu);
+      for (int i = 0; i < nsegs; ++i) {
+        const int64_t h = handles[i];
+        if (h > 0 && h < (int64_t)t->by_handle.size() && t->by_handle[h]) part.plan->fx_scope.push_back(t->by_handle[h].get());
+      }
+    }
     TRY(plan_create_impl(t, hs.data(), (int32_t)hs.size(), q, part.plan.get()));
     P->parts.push_back(std::move(part));
     return 0;
@@ -216,6 +225,10 @@ int composite_finalize(pgpu_plan_s* P, hipStream_t stream, pgpu_result_s* R) {
   for (int a = 0; a < R->num_aggs; ++a)
     if ((R->agg_fn[a] == PGPU_AGG_SUM || R->agg_fn[a] == PGPU_AGG_AVG) && kind[R->agg_slot[a]] == SLOT_SUM_F64)
       R->agg_conv[a] = RCONV_F64;
+  // fixed-point sums: the parts share their formats (fx_scope) and their digits were merged as integers above
+  R->agg_fx = R0->agg_fx;
+  R->fx_pending.store(std::find(R->agg_conv.begin(), R->agg_conv.end(), (uint8_t)RCONV_FX) != R->agg_conv.end(),
+                      std::memory_order_release);
   for (const auto& Ri : rs)
     for (int k = 0; k < 6; ++k) R->stats[k] += Ri->stats[k];
   R->groups_limit_reached = P->pql_cap && n >= L;

@@ -562,6 +562,7 @@ int32_t pack_slot_for(const pgpu_table_s* t, const pgpu_plan_s* P, const pgpu_qu
   for (size_t sl = 1; sl < P->slot_kind.size(); ++sl) {
     const int c = P->slot_tcol[sl];
     if (P->slot_kind[sl] != SLOT_SUM_I64 || c < 0 || c == kDocIdColumn || !is_int_type(t->types[c])) continue;
+    if (P->slot_fx[sl] >= 0) continue;  // a fixed-point digit (of an integer column past int_sum_fits): signed
     int64_t lo = INT64_MAX, hi = INT64_MIN;
     bool known = true;
     for (const Segment* seg : P->segs) {
@@ -771,13 +772,57 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
   P->slot_kind.push_back(SLOT_COUNT);
   P->slot_col.push_back(0);
   P->slot_tcol.push_back(-1);
+  P->slot_fx.assign(1, -1);
+  P->slot_fmt.assign(1, FxFormat{});
   auto add_slot = [&](int kind, int tcol) -> int {
     for (size_t s = 1; s < P->slot_kind.size(); ++s)
-      if (P->slot_kind[s] == kind && P->slot_tcol[s] == tcol) return (int)s;
+      if (P->slot_kind[s] == kind && P->slot_tcol[s] == tcol && P->slot_fx[s] < 0) return (int)s;
     P->slot_kind.push_back(kind);
     P->slot_tcol.push_back(tcol);
     P->slot_col.push_back(slot_of(tcol));
+    P->slot_fx.push_back(-1);
+    P->slot_fmt.push_back(FxFormat{});
     return (int)P->slot_kind.size() - 1;
+  };
+  // PGPU_OPT_EXACT_FP_SUM: the fixed-point format of SUM / AVG over table column tcol (fx_sum.h) -- E and L over every
+  // operand the plan can read (the segments' dictionaries or raw docs, and the pre-aggregated doubles of the star-trees
+  // that may answer the query), the headroom from the docs of the same segments.  Mode 0 when an operand is not
+  // finite: the sum keeps its float64 slot.
+  auto fx_format_for = [&](int tcol) -> FxFormat {
+    const std::vector<Segment*>& scope = P->fx_scope.empty() ? P->segs : P->fx_scope;
+    FxRange r;
+    int64_t docs = 0;
+    std::lock_guard<std::mutex> g(t->mu);  // Column.fx is filled on first use
+    for (Segment* s : scope) {
+      docs += s->num_docs;
+      Column& c = s->cols[tcol];
+      if (!c.fx_known) {
+        if (is_int_type(c.dict.type)) for (int64_t v : c.dict.iv) fx_range_add(&c.fx, (double)v);
+        else for (double v : c.dict.dv) fx_range_add(&c.fx, v);
+        c.fx_known = true;
+      }
+      fx_range_merge(&r, c.fx);
+      if (s->star && !(q->options & PGPU_OPT_NO_STAR_TREE))
+        for (int fn : {PGPU_AGG_SUM, PGPU_AGG_AVG}) {
+          const int m = s->star->pair(fn, tcol);
+          if (m >= 0 && m < (int)s->star->mf_fx.size()) fx_range_merge(&r, s->star->mf_fx[m]);
+        }
+    }
+    return fx_format(r, docs);
+  };
+  // its W digit slots: adjacent, of the one column, shared by SUM and AVG of the column
+  auto add_fx_slots = [&](int tcol, const FxFormat& f) -> int {
+    for (size_t s = 1; s < P->slot_kind.size(); ++s)
+      if (P->slot_fx[s] == 0 && P->slot_tcol[s] == tcol) return (int)s;
+    for (int j = 0; j < f.W; ++j) {
+      P->slot_kind.push_back(SLOT_SUM_I64);  // what the digit's word is after the scan's accumulate (rt.h slot_fx)
+      P->slot_tcol.push_back(tcol);
+      P->slot_col.push_back(slot_of(tcol));
+      P->slot_fx.push_back(j);
+      P->slot_fmt.push_back(f);
+    }
+    P->fx = true;
+    return (int)P->slot_kind.size() - f.W;
   };
   for (int i = 0; i < q->num_aggs; ++i) {
     const pgpu_agg& a = q->aggs[i];
@@ -793,11 +838,21 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
         // Integer columns sum exactly in int64 unless the plan could overflow it: |sum| <= sum over segments of
         // numDocs x max |value| (the sorted dictionary's ends).  Past 2^62 the slot accumulates the doubles of
         // the values (Pinot's own arithmetic, SumAggregationFunction.java:66-73) instead of wrapping.
-        kind = is_int_type(type) && int_sum_fits(P->segs, a.column) ? SLOT_SUM_I64 : SLOT_SUM_F64;
+        // (fx_scope: the parts of a composite plan with fixed-point sums decide over the segments of them all, so
+        // their slots line up)
+        kind = is_int_type(type) && int_sum_fits(P->fx_scope.empty() ? P->segs : P->fx_scope, a.column) ? SLOT_SUM_I64
+                                                                                                         : SLOT_SUM_F64;
         break;
       case PGPU_AGG_MIN: kind = SLOT_MIN_KEY; break;
       case PGPU_AGG_MAX: kind = SLOT_MAX_KEY; break;
       default: return fail(PGPU_ERR_UNSUPPORTED, "aggregation function %d", a.fn);
+    }
+    if (kind == SLOT_SUM_F64 && (q->options & PGPU_OPT_EXACT_FP_SUM)) {
+      const FxFormat f = fx_format_for(a.column);
+      if (f.mode != FX_NONE) {
+        P->agg_slot.push_back(add_fx_slots(a.column, f));
+        continue;
+      }
     }
     P->agg_slot.push_back(add_slot(kind, a.column));
   }
@@ -805,6 +860,16 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
     P->slot_kind.push_back(SLOT_MIN_KEY);
     P->slot_tcol.push_back(kDocIdColumn);
     P->slot_col.push_back(slot_of(kDocIdColumn));
+    P->slot_fx.push_back(-1);
+    P->slot_fmt.push_back(FxFormat{});
+  }
+  if (P->fx) {
+    // The record passes of the partitioned pipelines (K8a-K8h) carry one 8-byte stream per operand, not digit streams,
+    // and a streamed plan configures before its later chunks are planned: a plan with fixed-point sums takes the
+    // scan kernel's global / hash tables, in one launch.
+    P->cfg.partitioned_group_by = 0;
+    P->cfg.hash_partitions = 0;
+    P->cfg.stream_chunks = 1;
   }
   if ((int)P->slot_kind.size() > kMaxSlots) return fail(PGPU_ERR_UNSUPPORTED, "too many accumulators");
   if ((int)P->query_cols.size() > kMaxQueryCols) return fail(PGPU_ERR_UNSUPPORTED, "too many columns");
@@ -1418,7 +1483,7 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
       bool f64 = false;
       for (int k : P->slot_kind) f64 |= k == SLOT_SUM_F64;
       // (a streamed plan configures before its later chunks are planned: never simple)
-      P->dense_simple = P->dense && !P->gathers && !f64 && P->tile_bound == 0;
+      P->dense_simple = P->dense && !P->gathers && !f64 && !P->fx && P->tile_bound == 0;
     }
     // the sparse instance with the index + scan pair: two-leaf AND plans with an in-place index leaf
     P->pair_variant = !P->dense && P->pure_and && P->num_leaves == 2 && P->leaf_kinds[LEAF_BITDIR] > 0;

@@ -23,7 +23,7 @@ __device__ __forceinline__ int64_t double_key_dev(double d) {  // order-preservi
   return b >= 0 ? b : (b ^ INT64_MAX);
 }
 
-#if PGPU_MODE == 0  // one definition: the mode-0 object
+#if PGPU_MODE == 0 && !defined(PGPU_STAR_SCAN_ONLY)  // one definition: the mode-0 object of k_startree.hip
 __global__ __launch_bounds__(256) void startree_traverse_kernel(const KStarSeg* __restrict__ segs,
                                                                 int64_t* __restrict__ seg_total, uint64_t deadline,
                                                                 unsigned long long* __restrict__ stats) {
@@ -172,7 +172,8 @@ __device__ __forceinline__ void star_decode(const uint32_t* __restrict__ fwd, in
 
 // Aggregates the docs of `mask` (bits H..H+15 of the lane's group g) of star-tree segment S.
 // sectors: 64-byte sectors of the metric arrays holding a matched doc, for the bytes model (statistics word 7).
-template <int MODE, int H>
+// FX: the instance of plans with SLOT_SUM_FX slots (the pre-aggregated double is split into its digit, fx_sum.h).
+template <int MODE, int H, bool FX>
 __device__ __forceinline__ void star_aggregate_half(const KStarParams& p, const KStarSeg& S, int64_t g, uint32_t mask,
                                                     const int32_t* __restrict__ cache, bool cached,
                                                     uint64_t* __restrict__ tbl, int64_t G,
@@ -261,8 +262,9 @@ __device__ __forceinline__ void star_aggregate_half(const KStarParams& p, const 
       double dval = 0.0;
       if (kind == SLOT_SUM_F64) dval = v[i];
       else if (kind == SLOT_SUM_I64) ikey = (int64_t)v[i];  // sums of integers are exact in double (< 2^53)
+      else if (FX && kind == SLOT_SUM_FX) ikey = fx_digit(v[i], p.fx.sh[s], p.fx.k[s], p.fx.j[s]);
       else ikey = p.slot_int[s] ? (int64_t)v[i] : double_key_dev(v[i]);
-      accumulate<MODE>(row, key[i], kind, ikey, dval);
+      accumulate<MODE>(row, key[i], FX && kind == SLOT_SUM_FX ? (int)SLOT_SUM_I64 : kind, ikey, dval);
     }
   }
 }
@@ -293,8 +295,8 @@ __device__ __forceinline__ uint32_t star_match_half(const KStarSeg& S, int d, in
 // workgroup stages the key LUTs, residual match sets and the ranges with their group prefix in LDS; each lane then
 // takes one group at a time, decodes the residual dims into a 32-bit match mask, decodes the group-by dims of the
 // matching docs 16 at a time and adds their pre-aggregated metrics.
-template <int MODE>
-__global__ __launch_bounds__(StarBlock<MODE>::value) void startree_scan_kernel(const KStarParams p) {
+template <int MODE, bool FX>
+__device__ __forceinline__ void startree_scan_body(const KStarParams& p) {
   constexpr int BLOCK = StarBlock<MODE>::value;
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   __shared__ int64_t wsum[BLOCK / 64];
@@ -433,8 +435,8 @@ __global__ __launch_bounds__(StarBlock<MODE>::value) void startree_scan_kernel(c
         moff += (S.dim_card[d] + 31) >> 5;
       }
       matched += __popc(mask);
-      if (__any((mask & 0xFFFFu) != 0u)) star_aggregate_half<MODE, 0>(p, S, g, mask, cache, cached, tbl, G, sectors);
-      if (__any((mask >> 16) != 0u)) star_aggregate_half<MODE, 16>(p, S, g, mask, cache, cached, tbl, G, sectors);
+      if (__any((mask & 0xFFFFu) != 0u)) star_aggregate_half<MODE, 0, FX>(p, S, g, mask, cache, cached, tbl, G, sectors);
+      if (__any((mask >> 16) != 0u)) star_aggregate_half<MODE, 16, FX>(p, S, g, mask, cache, cached, tbl, G, sectors);
     }
   }
   {
@@ -448,6 +450,16 @@ __global__ __launch_bounds__(StarBlock<MODE>::value) void startree_scan_kernel(c
     uint64_t* o = p.slab + (int64_t)blockIdx.x * words;
     for (int64_t i = tid; i < words; i += BLOCK) o[i] = lds[i];
   }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(StarBlock<MODE>::value) void startree_scan_kernel(const KStarParams p) {
+  startree_scan_body<MODE, false>(p);
+}
+// The instance for plans with SLOT_SUM_FX slots (k_startree_fx.hip).
+template <int MODE>
+__global__ __launch_bounds__(StarBlock<MODE>::value) void startree_scan_fx_kernel(const KStarParams p) {
+  startree_scan_body<MODE, true>(p);
 }
 
 }  // namespace pgpu

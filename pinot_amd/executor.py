@@ -578,6 +578,15 @@ class Plan:
         L.check(self.lib.pgpu_plan_timing(self.handle, out))
         return out[0], out[1], out[2], out[3]
 
+    def fp_sum_format(self, agg):
+        """The fixed-point format of aggregation `agg` (its position in the query's aggregations) of a plan whose
+        query carried exact_fp_sum=True (pgpu_plan_fp_sum_format): {"mode": "none" | "exact" | "quantised", "E", "K",
+        "W"} -- "none" (all zero) for anything but a FLOAT / DOUBLE SUM / AVG, without the option, or when the column
+        holds a NaN or an infinity."""
+        out = (ctypes.c_int32 * 4)()
+        L.check(self.lib.pgpu_plan_fp_sum_format(self.handle, int(agg), out))
+        return {"mode": L.FP_SUM_MODE_NAMES[out[0]], "E": out[1], "K": out[2], "W": out[3]}
+
     def star_metric_bytes(self):
         """Bytes of the star-tree metric arrays the last execution read: 64-B sectors holding a matched document
         (-1: not read back for this plan's table size)."""
@@ -598,13 +607,15 @@ class Plan:
         """The scan's geometry (pgpu_plan_scan_geometry): of the plan `grid`, `lds_bytes`, `leap_tiles` (tiles per
         workgroup its LDS reserves for the STATS_LEAP2 bytes, 0 = none) and `tiles`; of its last scan launch
         `tile_chunks`, `slot_weights` (a tuple, empty = equal shares), `longest_run`, `launch_grid`, `launch_tiles`,
-        `alone` and `weights_declined` (refused for the LDS the plan reserved)."""
+        `alone` and `weights_declined` (refused for the LDS the plan reserved); `variant`, the scan kernel's instance
+        (0 sparse, 1 dense, 2 dense without gathers, 3-5 sparse specialisations, 6 / 7 sparse / dense with fixed-point
+        sums)."""
         out = (ctypes.c_int64 * 16)()
         L.check(self.lib.pgpu_plan_scan_geometry(self.handle, out))
         return {"grid": out[0], "lds_bytes": out[1], "leap_tiles": out[2], "tiles": out[3],
                 "tile_chunks": out[4], "slot_weights": tuple(out[6 + s] for s in range(out[5])),
                 "longest_run": out[10], "launch_grid": out[11], "launch_tiles": out[12],
-                "alone": bool(out[13]), "weights_declined": bool(out[14])}
+                "alone": bool(out[13]), "weights_declined": bool(out[14]), "variant": out[15]}
 
     def finalize(self, stream=None, d_table=None):
         """Waits for the execution, compacts the group table and returns the decoded result.  `finalize_us`
@@ -642,6 +653,9 @@ class Plan:
         """Finalize of this rank's key-range shard of the merged dense table (combine.reduce_scatter_group_table):
         the groups with keys in [key_begin, key_begin + key_count)."""
         return _finalize_range(self, stream, d_shard, key_begin, key_count)
+
+
+GpuPlan = Plan
 
 
 def _finalize_range(plan, stream, d_shard, key_begin, key_count):

@@ -100,8 +100,11 @@ class QueryContext:
     def __init__(self, group_by, aggregations, filter=None, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT,
                  use_star_tree=True, select=None, order_by=None, limit=DEFAULT_LIMIT,
                  min_server_group_trim_size=DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE,
-                 group_trim_threshold=DEFAULT_GROUP_TRIM_THRESHOLD, sql_group_by=False):
+                 group_trim_threshold=DEFAULT_GROUP_TRIM_THRESHOLD, sql_group_by=False, exact_fp_sum=False):
         self.filter = filter
+        # bit-reproducible FLOAT / DOUBLE SUM / AVG (PGPU_OPT_EXACT_FP_SUM): fixed-point digits summed as integers,
+        # rounded once -- the same bits in every run, segment layout and accumulator mode (GpuPlan.fp_sum_format)
+        self.exact_fp_sum = exact_fp_sum
         # queryOptions groupByMode=sql: GroupByOrderByCombineOperator (no 2 x numGroupsLimit inter-segment cap)
         self.sql_group_by = sql_group_by
         self.use_star_tree = use_star_tree  # debug option useStarTree (StarTreeUtils.java:51-59)
@@ -198,7 +201,8 @@ class QueryContext:
         return (0 if getattr(self, "use_star_tree", True) else L.OPT_NO_STAR_TREE) | \
             (L.OPT_SQL_GROUP_BY if getattr(self, "sql_group_by", False) else 0) | \
             (L.OPT_NO_PLAN_CACHE if getattr(self, "no_plan_cache", False) else 0) | \
-            (L.OPT_TIMING if getattr(self, "timing", False) else 0)
+            (L.OPT_TIMING if getattr(self, "timing", False) else 0) | \
+            (L.OPT_EXACT_FP_SUM if getattr(self, "exact_fp_sum", False) else 0)
 
     def _build_c(self, column_index):
         keep = []
@@ -378,10 +382,10 @@ class _Parser:
         raise ValueError("unsupported operator %s" % op)
 
 
-def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT):
+def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=False):
     """Parses `SELECT cols / aggs FROM t [WHERE ...] [GROUP BY cols] [ORDER BY expr [ASC|DESC], ...]
     [TOP n | LIMIT n]`.  Aggregations that appear only in ORDER BY are computed as well (Pinot's hidden
-    aggregations) but not selected."""
+    aggregations) but not selected.  exact_fp_sum: the query option of the same name (QueryContext)."""
     p = _Parser(sql)
     p.take("id", "SELECT")
     items = p.select_list()
@@ -420,4 +424,5 @@ def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT):
     for e in [x for x in select if x[0] == "agg"] + [e for e, _ in order_by if e[0] == "agg"]:
         if (e[1], e[2]) not in aggs:
             aggs.append((e[1], e[2]))
-    return QueryContext(group_by, aggs, flt, num_groups_limit, select=select, order_by=order_by, limit=limit)
+    return QueryContext(group_by, aggs, flt, num_groups_limit, select=select, order_by=order_by, limit=limit,
+                        exact_fp_sum=exact_fp_sum)
