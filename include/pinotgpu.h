@@ -255,13 +255,18 @@ typedef struct {
  *              an error below 2^-(W K) of the largest operand per doc -- less than one rounding of a running double
  *              sum costs; the result is the correctly rounded sum of the truncated operands, still order-independent.
  * A column with a NaN or an infinity among its values keeps the floating-point accumulator (mode 0).
- * Limits: a plan with such sums takes the scan kernel's LDS / global / hash tables, not the radix- or hash-partitioned
- * pipelines (planned as with pgpu_config.partitioned_group_by = 0 and hash_partitions = 0), runs as one launch from
- * pgpu_plan_create_execute, takes W accumulator slots per summed column (the limit of 24 counts them), and is
- * declined with PGPU_ERR_UNSUPPORTED by the cross-GPU entry points (pgpu_plan_combine*, pgpu_plan_exchange_*,
- * pgpu_result_exchange_rows / merge_rows / combine_rows, pgpu_plan_finalize_range, an external d_table): the ranks
- * would first have to agree on (E, K, W).  Part of the plan-cache key.  Queries without such a sum plan and run
- * exactly as without the option. */
+ * A plan with such sums takes W accumulator slots per summed column (the limit of 24 counts them) and runs as one
+ * launch from pgpu_plan_create_execute.  Part of the plan-cache key.  Queries without such a sum plan and run exactly
+ * as without the option.
+ * Plain plans (pgpu_plan_create / pgpu_plan_create_execute) derive (E, K, W) from this rank's segments alone.  They
+ * take the scan kernel's LDS / global / hash tables, not the radix- or hash-partitioned pipelines (planned as with
+ * pgpu_config.partitioned_group_by = 0 and hash_partitions = 0), and are declined with PGPU_ERR_UNSUPPORTED by the
+ * cross-GPU entry points (pgpu_plan_combine*, pgpu_plan_exchange_*, pgpu_result_exchange_rows / merge_rows /
+ * combine_rows, pgpu_plan_finalize_range, an external d_table): digit sums of different formats do not add.
+ * Agreed plans (pgpu_plan_create_agreed, below) take their formats from ranges every rank agreed on: they pass all of
+ * those entry points -- after the scan their digits are int64 SUM rows, merged by the collectives as such, and the
+ * merged result is the same bits for every rank count, segment-to-rank assignment and collective algorithm -- and
+ * they take the partitioned pipelines, whose aggregate kernels split the records' operands (K8d / K8h FX). */
 #define PGPU_OPT_EXACT_FP_SUM 16
 
 /* A query compiled against a list of pinned segments (InstancePlanMakerImplV2.makeInstancePlan +
@@ -426,6 +431,36 @@ int pgpu_plan_timing(pgpu_plan plan, double* out4);
  * 0 = none (not a FLOAT / DOUBLE sum, the option is off, or the column holds a non-finite value: E = K = W = 0),
  * 1 = exact, 2 = quantised; K is the digit width the kernels use. */
 int pgpu_plan_fp_sum_format(pgpu_plan plan, int agg, int32_t out[4]);
+
+/* Agreement on the fixed-point formats of PGPU_OPT_EXACT_FP_SUM across ranks (GroupByDataTableReducer merges the
+ * servers' partial sums by AggregationFunction.merge, SumAggregationFunction.java:120-123, in arrival order: the
+ * reproducible counterpart needs one format on every server).  One pgpu_fp_sum_range per aggregation of the query:
+ * what this rank's plan could read for it. */
+typedef struct {
+  int32_t is_sum;        /* 1: SUM / AVG over a numeric column; 0: COUNT / MIN / MAX (other fields 0) */
+  int32_t any, finite;   /* any: a finite non-zero operand exists; finite: no operand is a NaN or an infinity */
+  int32_t E, L;          /* valid when any: |v| < 2^E, lowest set mantissa bit >= 2^L over those operands */
+  int32_t reserved;
+  int64_t docs;          /* documents of this rank's segments (the digits' headroom counts them) */
+  double  int_sum_bound; /* integer columns: sum over segments of numDocs x max|value|, rounded up; else 0 */
+} pgpu_fp_sum_range;
+/* Local, no device work beyond what planning needs: out[a] for each of q's num_aggs aggregations, read from what a
+ * plan of q over these segments reads -- their dictionaries, raw columns' values and the pre-aggregated doubles of
+ * star-trees that may answer q (SumAggregationFunction.java:66-73 is the operand: the value as a double). */
+int pgpu_query_fp_sum_ranges(pgpu_table table, const int64_t* segment_handles, int32_t num_segments,
+                             const pgpu_query* q, pgpu_fp_sum_range* out);
+/* Pure host: all[r * num_aggs + a] of nranks ranks -> out[a].  finite: AND; any: OR; E: max and L: min over the ranks
+ * with any; docs and int_sum_bound: sums.  PGPU_ERR_INVALID_ARGUMENT when ranks differ on an aggregation's is_sum. */
+int pgpu_fp_sum_ranges_merge(const pgpu_fp_sum_range* all, int32_t nranks, int32_t num_aggs, pgpu_fp_sum_range* out);
+/* Collective: pgpu_comm_allgather of every rank's ranges and the merge, in place. */
+int pgpu_comm_agree_fp_sum_ranges(pgpu_comm comm, pgpu_fp_sum_range* ranges, int32_t num_aggs);
+/* pgpu_plan_create over agreed ranges, one per aggregation (a single rank passes its own: the plan then has the
+ * formats of its plain plan).  q carries PGPU_OPT_EXACT_FP_SUM, else PGPU_ERR_INVALID_ARGUMENT.  An integer column's
+ * sum is an int64 slot iff the agreed int_sum_bound is below 2^62, on every rank alike; every other sum has the
+ * format of the agreed {E, L, any, finite} and the agreed docs, or the float64 slot when finite is 0.  The agreed
+ * ranges are part of the plan-cache key; a numGroupsLimit plan hands them to its parts. */
+int pgpu_plan_create_agreed(pgpu_table table, const int64_t* segment_handles, int32_t num_segments,
+                            const pgpu_query* q, const pgpu_fp_sum_range* agreed, pgpu_plan* out);
 
 /* Star-tree work of the last execution (after finalize): [0] segments answered from their star-tree, [1] their
  * tree nodes (28 bytes each, OffHeapStarTreeNode), [2] star-tree documents the residual scan read. */

@@ -126,6 +126,40 @@ class ConfigC(ctypes.Structure):
 CONFIG_FIELDS = [f for f, _ in ConfigC._fields_ if f != "struct_size"]
 
 
+class FpSumRangeC(ctypes.Structure):
+    """pgpu_fp_sum_range (include/pinotgpu.h): what one rank's plan could read for one aggregation -- the ranks merge
+    theirs (pgpu_fp_sum_ranges_merge) and plan with the result (pgpu_plan_create_agreed)."""
+    _fields_ = [("is_sum", c_i32), ("any", c_i32), ("finite", c_i32), ("E", c_i32), ("L", c_i32), ("reserved", c_i32),
+                ("docs", c_i64), ("int_sum_bound", ctypes.c_double)]
+
+    def as_tuple(self):
+        return (self.is_sum, self.any, self.finite, self.E, self.L, self.docs, self.int_sum_bound)
+
+    @classmethod
+    def from_tuple(cls, t):
+        return cls(int(t[0]), int(t[1]), int(t[2]), int(t[3]), int(t[4]), 0, int(t[5]), float(t[6]))
+
+
+def fp_sum_range_array(ranges):
+    """A C array of FpSumRangeC from FpSumRangeC objects or their as_tuple() forms."""
+    items = [r if isinstance(r, FpSumRangeC) else FpSumRangeC.from_tuple(r) for r in ranges]
+    arr = (FpSumRangeC * max(len(items), 1))()
+    for i, r in enumerate(items):
+        arr[i] = r
+    return arr
+
+
+def merge_fp_sum_ranges(per_rank):
+    """pgpu_fp_sum_ranges_merge: per_rank[r][a] (FpSumRangeC or tuples) -> the agreed [a] list of FpSumRangeC."""
+    nranks, na = len(per_rank), len(per_rank[0])
+    if any(len(r) != na for r in per_rank):
+        raise ValueError("ranks report different numbers of aggregations")
+    flat = fp_sum_range_array([x for r in per_rank for x in r])
+    out = (FpSumRangeC * max(na, 1))()
+    check(load().pgpu_fp_sum_ranges_merge(flat, nranks, na, out))
+    return [FpSumRangeC.from_tuple(out[a].as_tuple()) for a in range(na)]
+
+
 class PinotGpuError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("pgpu error %d: %s" % (code, message))
@@ -192,6 +226,11 @@ _PROTOS = {
                                      ctypes.POINTER(c_voidp)]),
     "pgpu_plan_timing": (c_int, [c_voidp, c_f64p]),
     "pgpu_plan_fp_sum_format": (c_int, [c_voidp, c_int, c_i32p]),
+    "pgpu_query_fp_sum_ranges": (c_int, [c_voidp, c_i64p, c_i32, ctypes.POINTER(QueryC), ctypes.POINTER(FpSumRangeC)]),
+    "pgpu_fp_sum_ranges_merge": (c_int, [ctypes.POINTER(FpSumRangeC), c_i32, c_i32, ctypes.POINTER(FpSumRangeC)]),
+    "pgpu_comm_agree_fp_sum_ranges": (c_int, [c_voidp, ctypes.POINTER(FpSumRangeC), c_i32]),
+    "pgpu_plan_create_agreed": (c_int, [c_voidp, c_i64p, c_i32, ctypes.POINTER(QueryC), ctypes.POINTER(FpSumRangeC),
+                                        ctypes.POINTER(c_voidp)]),
     "pgpu_plan_star_work": (c_int, [c_voidp, c_i64p]),
     "pgpu_plan_scan_geometry": (c_int, [c_voidp, c_i64p]),
     "pgpu_plan_star_metric_bytes": (c_int, [c_voidp, c_i64p]),

@@ -16,14 +16,16 @@ RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_exec", "rt_groups", "abi_table",
            "abi_result"]
 SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTIME] + [("startree.cpp", [], "startree"),
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
-           ("k_partition.hip", [], "k_partition"), ("k_hashfinal.hip", [], "k_hashfinal")] + \
+           ("k_partition.hip", [], "k_partition"), ("k_partition_fx.hip", [], "k_partition_fx"),
+           ("k_hashfinal.hip", [], "k_hashfinal")] + \
     [("k_direct.hip", ["-DPGPU_MODE=%d" % m], "k_direct_%d" % m) for m in range(3)] + \
     [("k_startree.hip", ["-DPGPU_MODE=%d" % m], "k_startree_%d" % m) for m in range(3)] + \
     [("k_direct_fx.hip", ["-DPGPU_MODE=%d" % m], "k_direct_fx_%d" % m) for m in range(3)] + \
     [("k_startree_fx.hip", ["-DPGPU_MODE=%d" % m], "k_startree_fx_%d" % m) for m in range(3)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "scan_direct_body.inc"]
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
 
@@ -204,6 +206,32 @@ def build_fx_sum_check(force=False):
             raise RuntimeError("hipcc (fx_sum_check) failed:\n" + res.stdout[-6000:])
     os.replace(FX_CHECK_PATH + ".tmp", FX_CHECK_PATH)
     return FX_CHECK_PATH
+
+
+AGREE_CHECK_PATH = os.path.join(ROOT, "build", "fx_agree_check")
+
+
+def build_fx_agree_check(force=False):
+    """build/fx_agree_check: tools/fx_agree_check.cpp (the cross-rank agreement on the fixed-point format), which
+    includes csrc/fx_sum.h and nothing else of the library, under AddressSanitizer + UndefinedBehaviorSanitizer.  One
+    compile, no library linked."""
+    src = os.path.join(ROOT, "tools", "fx_agree_check.cpp")
+    hdr = os.path.join(CSRC, "fx_sum.h")
+    if not force and os.path.exists(AGREE_CHECK_PATH) and \
+            all(os.path.getmtime(f) <= os.path.getmtime(AGREE_CHECK_PATH) for f in (src, hdr)):
+        return AGREE_CHECK_PATH
+    os.makedirs(os.path.dirname(AGREE_CHECK_PATH), exist_ok=True)
+    hipcc = _hipcc()
+    obj = os.path.join(ROOT, "build", "fx_agree_check.o")
+    for cmd in ([hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS +
+                ["-c", src, "-o", obj],
+                [hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined", obj,
+                 "-o", AGREE_CHECK_PATH + ".tmp"]):
+        res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if res.returncode != 0:
+            raise RuntimeError("hipcc (fx_agree_check) failed:\n" + res.stdout[-6000:])
+    os.replace(AGREE_CHECK_PATH + ".tmp", AGREE_CHECK_PATH)
+    return AGREE_CHECK_PATH
 
 
 if __name__ == "__main__":

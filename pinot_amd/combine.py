@@ -208,15 +208,36 @@ def exchange_result(table, res, group=None):
     return _decode_result(table, res._query, _ResultHolder(lib, out))
 
 
-def plan_combine_mode(table, handles, query, group=None):
+def agree_fp_sum_ranges_group(ranges, group=None):
+    """The fixed-point formats' agreement over torch.distributed: every rank's table.fp_sum_ranges(...) gathered
+    (all_gather_object) and merged by pgpu_fp_sum_ranges_merge -- the same list on every rank, for
+    table.plan(..., fp_sum_ranges=...)."""
+    world = dist.get_world_size(group)
+    gathered = [None] * world
+    dist.all_gather_object(gathered, [r.as_tuple() for r in ranges], group=group)
+    return L.merge_fp_sum_ranges(gathered)
+
+
+def agree_fp_sum_ranges(ranges, comm):
+    """The same over the C ABI communicator (pgpu_comm_agree_fp_sum_ranges, a collective)."""
+    arr = L.fp_sum_range_array(ranges)
+    L.check(comm.lib.pgpu_comm_agree_fp_sum_ranges(comm.handle, arr, len(ranges)))
+    return [L.FpSumRangeC.from_tuple(arr[a].as_tuple()) for a in range(len(ranges))]
+
+
+def plan_combine_mode(table, handles, query, group=None, fp_sum_ranges=None):
     """How this query's per-rank results merge, agreed by every rank: "dense" (element-wise all-reduce /
     reduce-scatter of the dense tables), "hash" (device all-to-all of hash-mode tables) or "rows" (host rows of the
     finalized results: numGroupsLimit plans and ARRAY_MAP key stages).  A rank whose segments make the query a
-    numGroupsLimit plan puts every rank on the row path (the modes must match for the collectives to pair up)."""
+    numGroupsLimit plan puts every rank on the row path (the modes must match for the collectives to pair up).
+    fp_sum_ranges: the agreed ranges of a query with exact_fp_sum=True (agree_fp_sum_ranges_group) -- the probe, like
+    the plan that runs, is an agreed plan; a plain plan with fixed-point sums is declined by the merges."""
     from . import _lib
     world = dist.get_world_size(group)
-    probe = table.plan(handles, query)
+    probe = table.plan(handles, query, fp_sum_ranges=fp_sum_ranges)
     try:
+        # (fixed-point sums: digit rows of different formats must not meet -- pgpu_plan_combine_mode's digest)
+        formats = [probe.fp_sum_format(a) for a in range(len(probe.query.aggregations))]
         try:
             nslots, nkeys, kinds = probe.layout()
             mode = "dense" if nkeys > 0 else "hash"
@@ -233,10 +254,14 @@ def plan_combine_mode(table, handles, query, group=None):
     finally:
         probe.close()
     gathered = [None] * world
-    dist.all_gather_object(gathered, mode, group=group)
+    dist.all_gather_object(gathered, (mode, formats), group=group)
+    if any(g[1] != formats for g in gathered):
+        raise ValueError("ranks' fixed-point formats (E, K, W) differ: plan with the ranges every rank agreed on "
+                         "(agree_fp_sum_ranges_group)")
     # one mode on every rank, or the row exchange, which merges plans of any kind (a dense rank could not take part
     # in a hash exchange: its collectives would not pair up)
-    return gathered[0] if len(set(gathered)) == 1 else "rows"
+    modes = [g[0] for g in gathered]
+    return modes[0] if len(set(modes)) == 1 else "rows"
 
 
 # ------------------------------------------------------------------------------------- the C ABI combine (pgpu_comm)

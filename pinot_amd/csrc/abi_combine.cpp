@@ -25,6 +25,16 @@ int check_kinds(const std::vector<int32_t>& mine, const int32_t* kinds, uint32_t
   }
   return 0;
 }
+// A result with agreed fixed-point sums travels as its digit rows (int64 sums): it must still hold them -- the first
+// read of its values converts them to doubles in place.
+int fx_rows_ready(pgpu_result r, const char* what) {
+  if (!result_has_fx(r)) return 0;
+  if (result_fx_local(r)) return fx_decline(what);
+  if (!r->fx_pending.load(std::memory_order_acquire))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "the result's fixed-point sums were already read (converted to doubles): "
+                "exchange a result before reading its values");
+  return 0;
+}
 // Owner rank of a finalized group (its dictId tuple): the same on every rank.
 int32_t row_owner(const int64_t* ids, int nk, int32_t nparts) {
   uint64_t h = 0x9E3779B97F4A7C15ull;
@@ -84,7 +94,7 @@ extern "C" {
 int pgpu_plan_exchange_counts(pgpu_plan P, void* stream, int32_t nparts, int64_t* counts) try {
   PGPU_ABI_GUARD;
   TRY(exchangeable(P));
-  if (plan_has_fx(P)) return fx_decline("a cross-GPU exchange");
+  if (plan_fx_local(P)) return fx_decline("a cross-GPU exchange");
   if (nparts < 1 || nparts > 64 || !counts) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (P->merged_records >= 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "the table already holds merged records");
   DeviceGuard g(P->table->device);
@@ -111,7 +121,7 @@ int pgpu_plan_exchange_export(pgpu_plan P, void* stream, int32_t nparts, const i
                               int64_t cap) try {
   PGPU_ABI_GUARD;
   TRY(exchangeable(P));
-  if (plan_has_fx(P)) return fx_decline("a cross-GPU exchange");
+  if (plan_fx_local(P)) return fx_decline("a cross-GPU exchange");
   if ((int32_t)P->xchg_counts.size() != nparts || nparts < 1)
     return fail(PGPU_ERR_INVALID_ARGUMENT, "pgpu_plan_exchange_counts with %d parts first", nparts);
   int64_t total = 0;
@@ -142,7 +152,7 @@ int pgpu_plan_exchange_export(pgpu_plan P, void* stream, int32_t nparts, const i
 int pgpu_plan_exchange_merge(pgpu_plan P, void* stream, const int32_t* kinds, const void* d_records, int64_t n) try {
   PGPU_ABI_GUARD;
   TRY(exchangeable(P));
-  if (plan_has_fx(P)) return fx_decline("a cross-GPU exchange");
+  if (plan_fx_local(P)) return fx_decline("a cross-GPU exchange");
   P->exported = false;
   P->k8d_counts = false;
   if (n < 0 || (n > 0 && !d_records) || n > (INT64_C(1) << 40))  // the table below holds >= 2n slots
@@ -182,11 +192,13 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
   PGPU_ABI_GUARD;
   if (!r || nparts < 1 || nparts > (1 << 20) || !counts || (r->n > 0 && !rows))
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  if (result_has_fx(r)) return fx_decline("a cross-GPU exchange of rows");
+  TRY(fx_rows_ready(r, "a cross-GPU exchange of rows"));
   if ((int)r->slot_kind.size() != r->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
   uint32_t conv = 0;
   TRY(check_kinds(r->slot_kind, kinds, &conv));
   if (r->compact.load(std::memory_order_acquire)) TRY(pgpu::result_expand(r));
+  // (slot_raw: slot() would convert pending digit rows)
+  auto words = [r](int k) { return r->fx_pending.load(std::memory_order_acquire) ? r->slot_raw(k) : r->slot(k); };
   const int nk = r->num_keys, ns = r->num_slots, w = nk + ns;
   std::vector<int32_t> owner((size_t)r->n);
   std::vector<int64_t> off(nparts + 1, 0), ids(std::max(nk, 1));
@@ -200,7 +212,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
     int64_t* o = rows + off[owner[i]]++ * w;
     for (int j = 0; j < nk; ++j) o[j] = r->gid(j)[i];
     for (int k = 0; k < ns; ++k) {
-      uint64_t v = r->slot(k)[i];
+      uint64_t v = words(k)[i];
       if ((conv >> k) & 1u) {
         const double d = (double)(int64_t)v;
         memcpy(&v, &d, 8);
@@ -214,10 +226,15 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
 int pgpu_result_merge_rows(pgpu_result tmpl, const int64_t* rows, int64_t n, const int32_t* kinds, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!tmpl || !out || n < 0 || (n > 0 && !rows)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  if (result_has_fx(tmpl)) return fx_decline("a cross-GPU merge of rows");
+  TRY(fx_rows_ready(tmpl, "a cross-GPU merge of rows"));
   if ((int)tmpl->slot_kind.size() != tmpl->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
   uint32_t conv = 0;
   TRY(check_kinds(tmpl->slot_kind, kinds, &conv));
+  if (conv && result_has_fx(tmpl))  // (an agreed plan has the slot kinds of every other rank's)
+    for (int a = 0; a < tmpl->num_aggs && a < (int)tmpl->agg_fx.size(); ++a)
+      for (int j = 0; j < tmpl->agg_fx[a].W; ++j)
+        if ((conv >> (tmpl->agg_slot[a] + j)) & 1u)
+          return fail(PGPU_ERR_INVALID_ARGUMENT, "slot %d: a fixed-point digit row cannot become float64", tmpl->agg_slot[a] + j);
   const int nk = tmpl->num_keys, ns = tmpl->num_slots, w = nk + ns;
   std::vector<int32_t> kind(tmpl->slot_kind);
   if (kinds) kind.assign(kinds, kinds + ns);
@@ -291,6 +308,10 @@ int pgpu_result_merge_rows(pgpu_result tmpl, const int64_t* rows, int64_t n, con
   for (int a = 0; a < R->num_aggs; ++a)
     if ((tmpl->agg_fn[a] == PGPU_AGG_SUM || tmpl->agg_fn[a] == PGPU_AGG_AVG) && kind[R->agg_slot[a]] == SLOT_SUM_F64)
       R->agg_conv[a] = RCONV_F64;
+  // agreed fixed-point sums: the merged digit rows are converted on the merged result's first read
+  R->agg_fx = tmpl->agg_fx;
+  R->fx_agreed = tmpl->fx_agreed;
+  R->fx_pending.store(result_has_fx(tmpl), std::memory_order_release);
   R->key_cols = tmpl->key_cols;
   R->key_types = tmpl->key_types;
   R->key_dicts = tmpl->key_dicts;
@@ -376,6 +397,19 @@ int pgpu_comm_allgather(pgpu_comm c, const void* send, int64_t bytes, void* recv
   return c->impl->allgather_host(send, (size_t)bytes, recv);
 } PGPU_ABI_CATCH
 
+int pgpu_comm_agree_fp_sum_ranges(pgpu_comm c, pgpu_fp_sum_range* ranges, int32_t num_aggs) try {
+  PGPU_ABI_GUARD;
+  if (!c || num_aggs < 0 || (num_aggs > 0 && !ranges)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (num_aggs == 0) return 0;
+  const int N = c->impl->nranks;
+  std::vector<pgpu_fp_sum_range> all((size_t)N * num_aggs);
+  {
+    DeviceGuard g(c->impl->device);
+    TRY(c->impl->allgather_host(ranges, sizeof(pgpu_fp_sum_range) * (size_t)num_aggs, all.data()));
+  }
+  return pgpu_fp_sum_ranges_merge(all.data(), N, num_aggs, ranges);
+} PGPU_ABI_CATCH
+
 namespace {
 // Content hash of a dictionary snapshot (computed once per snapshot): ranks compare their key spaces with it.
 uint64_t dict_digest(const Dict& d) {
@@ -425,8 +459,32 @@ uint64_t key_space_digest(const pgpu_plan_s* P, bool layout) {
   return h;
 }
 
+// The fixed-point formats of a plan's / a result's aggregations (PGPU_OPT_EXACT_FP_SUM): per aggregation its slot and
+// {mode, E, K, W}.  Ranks whose digests differ would add unlike digits.
+uint64_t fx_digest(const std::vector<int32_t>& agg_slot, const std::vector<pgpu::FxFormat>& agg_fx) {
+  uint64_t h = 0x2325cbf29ce48422ull;
+  auto mix = [&h](uint64_t v) { h = (h ^ v) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; };
+  for (size_t a = 0; a < agg_slot.size(); ++a) {
+    const pgpu::FxFormat f = a < agg_fx.size() ? agg_fx[a] : pgpu::FxFormat{};
+    if (f.mode == pgpu::FX_NONE) continue;
+    mix(a);
+    mix((uint64_t)agg_slot[a]);
+    mix((uint64_t)(uint32_t)f.mode | (uint64_t)(uint32_t)f.W << 32);
+    mix((uint64_t)(uint32_t)f.E | (uint64_t)(uint32_t)f.K << 32);
+  }
+  return h;
+}
+uint64_t plan_fx_digest(const pgpu_plan_s* K) {
+  std::vector<pgpu::FxFormat> fx(K->agg_slot.size());
+  for (size_t a = 0; a < K->agg_slot.size() && K->fx; ++a) {
+    const int sl = K->agg_slot[a];
+    if (K->agg_fn[a] != PGPU_AGG_COUNT && sl > 0 && sl < (int)K->slot_fx.size() && K->slot_fx[sl] == 0) fx[a] = K->slot_fmt[sl];
+  }
+  return fx_digest(K->agg_slot, fx);
+}
+
 // One rank's part of the mode agreement (int64 words).
-enum { CI_MODE = 0, CI_KEYS, CI_SLOTS, CI_DIGEST, CI_KINDS, CI_WORDS = CI_KINDS + kMaxSlots };
+enum { CI_MODE = 0, CI_KEYS, CI_SLOTS, CI_DIGEST, CI_FX, CI_KINDS, CI_WORDS = CI_KINDS + kMaxSlots };
 
 // Agreed kinds of ranks' slots: equal, or int64 / float64 sums of one slot meeting as float64.
 int agree_kinds(const std::vector<int64_t>& all, int nranks, int ns, int32_t* kinds) {
@@ -477,7 +535,7 @@ int agree_status(pgpu::Comm* C, int rc) {
 int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_t* mode, int32_t* kinds) try {
   PGPU_ABI_GUARD;
   if (!P || !c || !mode) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  if (plan_has_fx(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
+  if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
   pgpu::CommWaitScope wait_limits(P->end_time_ms, &P->cancel);
   const int N = c->impl->nranks;
   int local;
@@ -496,6 +554,7 @@ int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_
   mine[CI_KEYS] = local == PGPU_COMBINE_ALL_REDUCE || local == PGPU_COMBINE_REDUCE_SCATTER ? P->num_keys : 0;
   mine[CI_SLOTS] = (int64_t)K->slot_kind.size();
   mine[CI_DIGEST] = (int64_t)key_space_digest(K, local != PGPU_COMBINE_ROWS);
+  mine[CI_FX] = (int64_t)plan_fx_digest(K);
   for (size_t s = 0; s < K->slot_kind.size() && s < (size_t)kMaxSlots; ++s) mine[CI_KINDS + s] = K->slot_kind[s];
   {
     DeviceGuard g(c->impl->device);
@@ -517,6 +576,10 @@ int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_
     if (same && w[CI_DIGEST] != mine[CI_DIGEST])
       return fail(PGPU_ERR_INVALID_ARGUMENT, "rank %d's group-key space differs from rank %d's: union the group-by "
                   "dictionaries (pgpu_table_add_dictionary_values) before the query", r, c->impl->rank);
+    if (w[CI_FX] != mine[CI_FX])
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "rank %d's fixed-point formats (E, K, W) differ from rank %d's: plan with "
+                  "the ranges every rank agreed on (pgpu_comm_agree_fp_sum_ranges, pgpu_plan_create_agreed)", r,
+                  c->impl->rank);
   }
   (void)any_rows;
   if (!same) {
@@ -538,7 +601,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
                       void* d_shard, int64_t* key_begin, int64_t* key_count) try {
   PGPU_ABI_GUARD;
   if (!P || !c) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  if (plan_has_fx(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
+  if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
   P->exported = false;  // the table changes: finalize reads it from the device
   P->k8d_counts = false;
   if (mode == PGPU_COMBINE_LOCAL) {
@@ -670,7 +733,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
 int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!r || !c || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  if (result_has_fx(r)) return fx_decline("a cross-GPU combine of rows");  // every rank's query carries the option
+  if (result_fx_local(r)) return fx_decline("a cross-GPU combine of rows");  // every rank's query carries the option
   pgpu::Comm* C = c->impl.get();
   const int N = C->nranks, me = C->rank;
   TRY(C->usable());
@@ -678,6 +741,7 @@ int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
   // fails together
   int pre = 0;
   if ((int)r->slot_kind.size() != r->num_slots) pre = fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
+  else if ((pre = fx_rows_ready(r, "a cross-GPU combine of rows")) != 0) {}
   else if (r->compact.load(std::memory_order_acquire)) pre = pgpu::result_expand(r);
   // agree on the slot kinds; the group ids index the ranks' dictionary snapshots, which must be the same
   std::vector<int64_t> mine(CI_WORDS, 0), all((size_t)N * CI_WORDS, 0);
@@ -688,6 +752,7 @@ int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
   mine[CI_KEYS] = r->num_keys;
   mine[CI_SLOTS] = r->num_slots;
   mine[CI_DIGEST] = (int64_t)h;
+  mine[CI_FX] = (int64_t)fx_digest(r->agg_slot, r->agg_fx);
   for (int s = 0; s < r->num_slots && s < kMaxSlots && s < (int)r->slot_kind.size(); ++s)
     mine[CI_KINDS + s] = r->slot_kind[s];
   mine[CI_MODE] = pre;  // the status word
@@ -700,6 +765,8 @@ int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
     if (w[CI_DIGEST] != mine[CI_DIGEST])
       return fail(PGPU_ERR_INVALID_ARGUMENT, "rank %d's group-by dictionaries differ from rank %d's: union them "
                   "(pgpu_table_add_dictionary_values) before the query", p, me);
+    if (w[CI_FX] != mine[CI_FX])
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "rank %d's fixed-point formats (E, K, W) differ from rank %d's", p, me);
   }
   std::vector<int32_t> kinds(std::max(r->num_slots, 1));
   TRY(agree_kinds(all, N, r->num_slots, kinds.data()));

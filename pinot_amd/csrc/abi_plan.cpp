@@ -303,21 +303,35 @@ int pgpu_unpack_fixed_bit_device(const void* d_fwd, int64_t fwd_len, int32_t bit
   return 0;
 } PGPU_ABI_CATCH
 
-int pgpu_plan_create(pgpu_table t, const int64_t* handles, int32_t nsegs, const pgpu_query* q, pgpu_plan* out) try {
-  PGPU_ABI_GUARD;
-  if (!t || !out || (nsegs > 0 && !handles) || nsegs < 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+namespace {
+static_assert(sizeof(pgpu_fp_sum_range) == sizeof(pgpu::FxAgree) && offsetof(pgpu_fp_sum_range, docs) == offsetof(pgpu::FxAgree, docs) &&
+                  offsetof(pgpu_fp_sum_range, int_sum_bound) == offsetof(pgpu::FxAgree, int_sum_bound) &&
+                  offsetof(pgpu_fp_sum_range, L) == offsetof(pgpu::FxAgree, L),
+              "pgpu_fp_sum_range is fx_sum.h's FxAgree");
+const pgpu::FxAgree* as_agree_c(const pgpu_fp_sum_range* r) { return reinterpret_cast<const pgpu::FxAgree*>(r); }
+pgpu::FxAgree* as_agree(pgpu_fp_sum_range* r) { return reinterpret_cast<pgpu::FxAgree*>(r); }
+
+// pgpu_plan_create (agreed = null) / pgpu_plan_create_agreed
+int plan_create_common(pgpu_table t, const int64_t* handles, int32_t nsegs, const pgpu_query* q,
+                       const pgpu_fp_sum_range* agreed, pgpu_plan* out) {
   DeviceGuard g(t->device);
   auto P = std::make_unique<pgpu_plan_s>();
   // A cached plan is never a numGroupsLimit split (composite plans are not cached) and the split decision is a
   // function of the cache key (query, segments, pinned-state version): a hit skips it.
   const bool cache = plan_cache_enabled(t, q);
-  const std::string key = cache ? plan_cache_key(t, handles, nsegs, q) : std::string();
+  std::string key = cache ? plan_cache_key(t, handles, nsegs, q) : std::string();
+  if (cache && agreed)  // the agreed ranges decide slots and formats: part of the key
+    key.append("A").append(reinterpret_cast<const char*>(agreed), sizeof(pgpu_fp_sum_range) * (size_t)std::max(q->num_aggs, 0));
   if (!cache || !plan_cache_get(t, key, P.get())) {
     bool composite = false;
-    TRY(split_for_groups_limit(t, handles, nsegs, q, P.get(), &composite));
+    TRY(split_for_groups_limit(t, handles, nsegs, q, P.get(), &composite, agreed ? as_agree_c(agreed) : nullptr));
     if (composite) {
       *out = P.release();
       return 0;
+    }
+    if (agreed) {
+      P->fx_agreed = true;
+      P->fx_ranges.assign(as_agree_c(agreed), as_agree_c(agreed) + std::max(q->num_aggs, 0));
     }
     TRY(plan_create_impl(t, handles, nsegs, q, P.get()));
     if (cache) plan_cache_put(t, key, *P);
@@ -326,6 +340,53 @@ int pgpu_plan_create(pgpu_table t, const int64_t* handles, int32_t nsegs, const 
   P->timed = (q->options & PGPU_OPT_TIMING) != 0;
   P->scratch = acquire_scratch(t);
   *out = P.release();
+  return 0;
+}
+}  // namespace
+
+int pgpu_plan_create(pgpu_table t, const int64_t* handles, int32_t nsegs, const pgpu_query* q, pgpu_plan* out) try {
+  PGPU_ABI_GUARD;
+  if (!t || !out || (nsegs > 0 && !handles) || nsegs < 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  return plan_create_common(t, handles, nsegs, q, nullptr, out);
+} PGPU_ABI_CATCH
+
+int pgpu_plan_create_agreed(pgpu_table t, const int64_t* handles, int32_t nsegs, const pgpu_query* q,
+                            const pgpu_fp_sum_range* agreed, pgpu_plan* out) try {
+  PGPU_ABI_GUARD;
+  if (!t || !out || !q || (nsegs > 0 && !handles) || nsegs < 0 || (q->num_aggs > 0 && !agreed))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (!(q->options & PGPU_OPT_EXACT_FP_SUM))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "pgpu_plan_create_agreed: the query does not carry PGPU_OPT_EXACT_FP_SUM");
+  for (int i = 0; i < q->num_aggs; ++i)
+    if ((agreed[i].is_sum != 0) != (q->aggs[i].fn == PGPU_AGG_SUM || q->aggs[i].fn == PGPU_AGG_AVG))
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: the agreed range is not of this aggregation", i);
+  return plan_create_common(t, handles, nsegs, q, agreed, out);
+} PGPU_ABI_CATCH
+
+int pgpu_query_fp_sum_ranges(pgpu_table t, const int64_t* handles, int32_t nsegs, const pgpu_query* q,
+                             pgpu_fp_sum_range* out) try {
+  PGPU_ABI_GUARD;
+  if (!t || !q || (nsegs > 0 && !handles) || nsegs < 0 || q->num_aggs < 0 || (q->num_aggs > 0 && (!out || !q->aggs)))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  std::vector<std::shared_ptr<Segment>> refs;
+  std::vector<Segment*> segs;
+  {
+    std::lock_guard<std::mutex> lk(t->mu);
+    for (int i = 0; i < nsegs; ++i) {
+      const int64_t h = handles[i];
+      const std::shared_ptr<Segment>* sp = h > 0 && h < (int64_t)t->by_handle.size() ? &t->by_handle[h] : nullptr;
+      if (!sp || !*sp) return fail(PGPU_ERR_NOT_FOUND, "unknown segment handle %lld", (long long)h);
+      refs.push_back(*sp);
+      segs.push_back(sp->get());
+    }
+  }
+  return query_fp_sum_ranges(t, segs, q, as_agree(out));
+} PGPU_ABI_CATCH
+
+int pgpu_fp_sum_ranges_merge(const pgpu_fp_sum_range* all, int32_t nranks, int32_t num_aggs, pgpu_fp_sum_range* out) try {
+  if (nranks < 1 || num_aggs < 0 || (num_aggs > 0 && (!all || !out))) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  const int rc = pgpu::fx_agree_merge(as_agree_c(all), nranks, num_aggs, as_agree(out));
+  if (rc) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: ranks disagree on whether it is a SUM / AVG", -1 - rc);
   return 0;
 } PGPU_ABI_CATCH
 
@@ -466,7 +527,7 @@ int pgpu_plan_execute(pgpu_plan P, void* stream, void* d_table) try {
     return 0;
   }
   if (P->hash && d_table) return fail(PGPU_ERR_UNSUPPORTED, "external table with a hash-mode plan");
-  if (d_table && plan_has_fx(P)) return fx_decline("external table");
+  if (d_table && plan_fx_local(P)) return fx_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
   return plan_execute_impl(P, s, d_table);
@@ -475,7 +536,7 @@ int pgpu_plan_execute(pgpu_plan P, void* stream, void* d_table) try {
 int pgpu_plan_finalize(pgpu_plan P, void* stream, const void* d_table, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!P || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  if (d_table && plan_has_fx(P)) return fx_decline("external table");
+  if (d_table && plan_fx_local(P)) return fx_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
   auto R = std::make_unique<pgpu_result_s>();
@@ -498,7 +559,7 @@ int pgpu_plan_finalize_range(pgpu_plan P, void* stream, const void* d_table_shar
   if (!P || !out || !d_table_shard || key_begin < 0 || key_count < 0 || key_begin + key_count > P->num_keys)
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (P->hash) return fail(PGPU_ERR_UNSUPPORTED, "hash-mode group tables are not key-range shardable");
-  if (plan_has_fx(P)) return fx_decline("a key-range shard");
+  if (plan_fx_local(P)) return fx_decline("a key-range shard");
   if (P->composite)
     return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit below the key space: finalize the whole table");
   DeviceGuard g(P->table->device);

@@ -61,6 +61,58 @@ inline void fx_range_merge(FxRange* r, const FxRange& o) {
   if (o.L < r->L) r->L = o.L;
 }
 
+// ---- agreement across ranks (pgpu_fp_sum_range, include/pinotgpu.h: the same layout).  Digit sums of different
+// formats do not add, so before a cross-GPU query every rank reports, per aggregation, the range of its own operands
+// and its docs, the ranks merge what they gathered by the rule below, and every rank plans with the merged ranges
+// (pgpu_plan_create_agreed): one (E, K, W) per summed column on every rank, K's headroom over the docs of them all.
+struct FxAgree {
+  int32_t is_sum = 0;        // 1: SUM / AVG over a numeric column; 0: COUNT / MIN / MAX (the other fields 0)
+  int32_t any = 0, finite = 0;  // FxRange.any / .finite
+  int32_t E = 0, L = 0;      // FxRange.E / .L (valid when any)
+  int32_t reserved = 0;
+  int64_t docs = 0;          // documents of the rank's segments
+  double int_sum_bound = 0;  // integer columns: sum over segments of numDocs x max |value|, rounded up; else 0
+};
+// A long double bound as a double that is not below it.
+inline double fx_round_up(long double b) {
+  double d = (double)b;
+  if ((long double)d < b) d = nextafter(d, INFINITY);
+  return d;
+}
+// all[r * num_aggs + a]: rank r's range of aggregation a.  finite: AND; any: OR; E: max, L: min over the ranks with
+// any; docs and int_sum_bound: sums.  Returns -1 - a when the ranks differ on is_sum of aggregation a, else 0.
+inline int fx_agree_merge(const FxAgree* all, int nranks, int num_aggs, FxAgree* out) {
+  for (int a = 0; a < num_aggs; ++a) {
+    FxAgree m;
+    m.is_sum = all[a].is_sum;
+    FxRange r;
+    long double bound = 0;
+    for (int k = 0; k < nranks; ++k) {
+      const FxAgree& x = all[(int64_t)k * num_aggs + a];
+      if ((x.is_sum != 0) != (m.is_sum != 0)) return -1 - a;
+      if (!x.is_sum) continue;
+      FxRange o;
+      o.E = x.E;
+      o.L = x.L;
+      o.any = x.any != 0;
+      o.finite = x.finite != 0;
+      fx_range_merge(&r, o);
+      m.docs += x.docs;
+      bound += (long double)x.int_sum_bound;
+    }
+    if (m.is_sum) {
+      m.is_sum = 1;
+      m.any = r.any ? 1 : 0;
+      m.finite = r.finite ? 1 : 0;
+      m.E = r.any ? r.E : 0;
+      m.L = r.any ? r.L : 0;
+      m.int_sum_bound = fx_round_up(bound);
+    }
+    out[a] = m;
+  }
+  return 0;
+}
+
 inline int fx_bit_length(int64_t n) {
   int b = 0;
   while (n > 0) { ++b; n >>= 1; }

@@ -93,8 +93,11 @@ struct pgpu_result_s {
   // RCONV_FX aggregations (plans with PGPU_OPT_EXACT_FP_SUM): the format of the W digit sums in the W slots from
   // agg_slot on (fx_sum.h).  fx_pending: they are converted on the first access to slot() (the parts of a composite
   // plan stay digits until their rows are merged).
+  // fx_agreed: the formats are ones every rank agreed on (pgpu_plan_create_agreed): while fx_pending, the digit rows
+  // may be exchanged and merged across ranks as int64 sums, and the owner's merged result converts them.
   std::vector<pgpu::FxFormat> agg_fx;
   std::atomic<bool> fx_pending{false};
+  bool fx_agreed = false;
   int64_t stats[6] = {0, 0, 0, 0, 0, 0};
   // what the rows are (DataTable / trimming): table columns and types of the group-by keys, per aggregation its
   // function and table column (-1: COUNT(*)), and numGroupsLimitReached

@@ -48,7 +48,8 @@ enum LeafKind : int32_t { LEAF_NONE = 0, LEAF_ALL = 1, LEAF_RANGE = 2, LEAF_SET 
 constexpr int kLeafKinds = 9;
 enum OpCode : int32_t { OP_LEAF = 0, OP_AND = 1, OP_OR = 2, OP_NOT = 3 };
 // SLOT_SUM_FX (plans with PGPU_OPT_EXACT_FP_SUM): one fixed-point digit of a FLOAT / DOUBLE sum (fx_sum.h).  Only the
-// scan kernels' FX instances see the kind (KParams / KStarParams.slot_kind): they split the operand and add the digit
+// FX instances of the accumulating kernels see the kind (KParams / KStarParams.slot_kind: the scans, and K8d / K8h of
+// the partitioned pipelines for agreed plans): they split the operand and add the digit
 // as an integer.  To everything after the accumulate -- table init, slab fold, compactions, widths, merges -- the
 // word is an int64 SUM, and the plan's own slot_kind says SLOT_SUM_I64 (pgpu_plan_s::slot_fx tells the digits apart).
 enum SlotKind : int32_t { SLOT_COUNT = 0, SLOT_SUM_I64 = 1, SLOT_SUM_F64 = 2, SLOT_MIN_KEY = 3, SLOT_MAX_KEY = 4,
@@ -316,6 +317,11 @@ struct KPartParams {
   uint32_t* chunk_cnt;
   long long* chunk_mm;
 };
+// The parameters of K8d's / K8h's FX instances (part_aggregate_fx_kernel, part_hash_aggregate_fx_kernel): KPartParams
+// and the split of the SLOT_SUM_FX slots.  A type of its own, as KParamsFx is: the other kernels keep their arguments.
+struct KPartParamsFx : KPartParams {
+  KFxSplit fx;
+};
 // K8h: value streams a record carries in registers (plans with more use the global hash table).
 constexpr int kHashPartStreams = 4;
 // K8h: linear probes of the LDS hash table before a record is left for the partition's next round.
@@ -449,7 +455,11 @@ int launch_compact_ordered_scatter(const uint64_t* table, int32_t num_slots, int
                                    void* stream);
 // Partitioned group-by (k_partition.hip): K8a count, scan, K8c scatter, K8d aggregate into p.base.table.
 int occupancy_part_pass(size_t pass_lds, int num_parts, int num_coarse, int staged);
-int launch_partitioned(const KPartParams& pp, int grid, size_t pass_lds, void* stream);
+// fx: the split of a plan with SLOT_SUM_FX slots -- K8d / K8h run as their FX instances (k_partition_fx.hip); the
+// record passes are the same (the operand's double travels as one stream).
+int launch_partitioned(const KPartParams& pp, int grid, size_t pass_lds, void* stream, const KFxSplit* fx = nullptr);
+int launch_part_aggregate_fx(const KPartParamsFx& pp, size_t lds_bytes, void* stream);
+int launch_part_hash_aggregate_fx(const KPartParamsFx& pp, size_t lds_bytes, void* stream);
 // In-place exclusive prefix sum of n u32 (one workgroup; n up to a few 10^4).
 int launch_exclusive_scan_u32(uint32_t* data, int32_t n, void* stream);
 int launch_filter_bitmap(const KParams& p, uint32_t* out_words, void* stream);

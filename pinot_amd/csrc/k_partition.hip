@@ -23,7 +23,7 @@ int occupancy_part_pass(size_t pass_lds, int num_parts, int num_coarse, int stag
   return e == hipSuccess ? n : -1;
 }
 
-int launch_partitioned(const KPartParams& pp, int grid, size_t pass_lds, void* stream) {
+int launch_partitioned(const KPartParams& pp, int grid, size_t pass_lds, void* stream, const KFxSplit* fx) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(pp.part_start, 0, (size_t)(pp.num_parts + 1) * 4, s) != hipSuccess) return -1;
   if (hipMemsetAsync(pp.coarse_fill, 0, (size_t)pp.num_coarse * 4, s) != hipSuccess) return -1;
@@ -52,6 +52,12 @@ int launch_partitioned(const KPartParams& pp, int grid, size_t pass_lds, void* s
   }
   if (pp.hashed) {
     if (pp.num_streams > kHashPartStreams || pp.sbits < 8 || pp.sbits > 14) return -1;
+    if (fx) {
+      KPartParamsFx pf;
+      static_cast<KPartParams&>(pf) = pp;
+      pf.fx = *fx;
+      return launch_part_hash_aggregate_fx(pf, part_hash_lds(pp.sbits, pp.base.num_slots), stream);
+    }
     hipLaunchKernelGGL(part_hash_aggregate_kernel, dim3(pp.num_parts), dim3(kBlock),
                        part_hash_lds(pp.sbits, pp.base.num_slots), s, pp);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -62,6 +68,12 @@ int launch_partitioned(const KPartParams& pp, int grid, size_t pass_lds, void* s
 #else
   const size_t agg_lds = (size_t)pp.base.num_slots * ((size_t)1 << pp.pshift) * 8;
 #endif
+  if (fx) {
+    KPartParamsFx pf;
+    static_cast<KPartParams&>(pf) = pp;
+    pf.fx = *fx;
+    return launch_part_aggregate_fx(pf, agg_lds, stream);
+  }
   hipLaunchKernelGGL(part_aggregate_kernel, dim3(pp.num_parts), dim3(kBlock), agg_lds, s, pp);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -32,6 +32,12 @@
 // Replaces the same reference code as the direct kernel (DictionaryBasedGroupKeyGenerator INT_MAP holder +
 // aggregateGroupBySV + GroupByCombineOperator merge); results are identical (integer
 // accumulators exact; double sums within the path's 1e-9 relative bound — their order is not fixed).
+//
+// Fixed-point double sums (agreed plans of PGPU_OPT_EXACT_FP_SUM, fx_sum.h): the W digit slots of a summed column map to
+// one f64 stream of that column, so K8a / K8c / K8e move the operand's double exactly as for an f64 SUM (no packed or
+// 32-bit record forms), and the FX instances of K8d / K8h (part_aggregate_fx_kernel, part_hash_aggregate_fx_kernel, built
+// into k_partition_fx.hip) split it into its digits where the records are accumulated: the sums no longer depend on the
+// order of the records.
 #pragma once
 #include <type_traits>
 
@@ -390,6 +396,7 @@ __global__ __launch_bounds__(kBlock, PGPU_PART_PASS_MIN_WAVES) void part_pass_ke
 // values) instead of 64 lanes scattering over 2^cshift open runs.  LDS: counters / cursors / batch histogram /
 // bucket starts [2^cshift each], then the staged batch (pp.split_batch records: a multiple of kBlock, at most
 // kSplitBatch, smaller with many value streams): values u64 per stream, positions u32, keys u16.
+#ifndef PGPU_PARTITION_FX
 __global__ __launch_bounds__(kBlock) void part_split_kernel(const KPartParams pp) {
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   const int tid = threadIdx.x;
@@ -519,6 +526,8 @@ __global__ __launch_bounds__(kBlock) void part_split_kernel(const KPartParams pp
   }
 }
 
+#endif  // PGPU_PARTITION_FX
+
 // K8e, one final u32 word per record (KPartParams.fine_pack: C5's packed records, c5_hash's hashed ones): the same
 // batch sort with the record's final word computed in registers at load time, so the staging holds 8 bytes per record
 // (word, position) instead of 14-16, batches are twice as large (half the reservation round trips per record), and
@@ -625,171 +634,24 @@ __global__ __launch_bounds__(kBlock) void part_split_words_kernel(const KPartPar
   }
 }
 
+// The split of the SLOT_SUM_FX slots: pp is the KPartParamsFx of an FX instance (the only callers).
+__device__ __forceinline__ const KFxSplit& part_fx(const KPartParams& pp) { return static_cast<const KPartParamsFx&>(pp).fx; }
+
 // K8d: partition blockIdx.x -> its key range of every table row.  LDS: [num_slots][1 << pshift] u64.
-__global__ __launch_bounds__(kBlock) void part_aggregate_kernel(const KPartParams pp) {
-  extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
-  const KParams& p = pp.base;
-  const int tid = threadIdx.x;
-  if (p.deadline && p.stats[5]) return;
-  const int PR = 1 << pp.pshift;
-  const int ns = p.num_slots;
-  // cs_pack: one word per key (LDS of PR words, part_aggregate_lds), COUNT + SUM from 0; else every slot's row
-  for (int i = tid; i < (pp.cs_pack ? PR : ns * PR); i += kBlock) lds[i] = pp.cs_pack ? 0ull : slot_init(p.slot_kind[i / PR]);
-  __syncthreads();
-  const uint32_t r0 = pp.part_start[blockIdx.x], r1 = pp.part_start[blockIdx.x + 1];
-  // COUNT + SUM in one LDS word per key (the table is PR words, 32 KB for C5: four workgroups per CU instead of
-  // two), over chunks of records small enough that every key's count stays below 2^24 and its sum of offsets below
-  // 2^40; the first chunk stores the partition's slice of both rows, later ones (a partition of more than ~10^9
-  // offsets' worth of records) add to it -- the partition is this workgroup's alone.
-  if (pp.cs_pack) {
-    constexpr int NB = 16;
-    const uint32_t* __restrict__ r32 = reinterpret_cast<const uint32_t*>(pp.rec_val);
-    const uint32_t low = (1u << pp.pshift) - 1u;
-    unsigned long long* w64 = reinterpret_cast<unsigned long long*>(lds);  // slot 0's words
-    const uint64_t by_sum = (1ull << 40) / (uint64_t)(pp.pack_range > 0 ? pp.pack_range : 1);
-    const uint32_t lim = (uint32_t)(by_sum < (1ull << 24) - 1 ? (by_sum > 0 ? by_sum : 1) : (1ull << 24) - 1);
-    const int64_t G = p.num_keys_total;
-    const int64_t k0 = (int64_t)blockIdx.x * PR;
-    const int n = (int)(G - k0 < PR ? G - k0 : PR);
-    uint32_t c0 = r0;
-    do {
-      const uint32_t c1 = r1 - c0 > lim ? c0 + lim : r1;
-      if (c0 != r0) {
-        for (int i = tid; i < PR; i += kBlock) lds[i] = 0ull;
-        __syncthreads();
-      }
-      for (uint32_t base = c0 + tid; base < c1; base += NB * kBlock) {
-        uint32_t wr[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const uint32_t r = base + b * kBlock;
-          wr[b] = r32[r < c1 ? r : c0];
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-          if (base + b * kBlock < c1)
-            atomicAdd(w64 + (wr[b] & low), (1ull << 40) | (unsigned long long)(wr[b] >> pp.pshift));
-      }
-      __syncthreads();
-      const bool last = c1 >= r1;
-      uint32_t present = 0;
-      long long mn[2] = {INT64_MAX, INT64_MAX}, mx[2] = {INT64_MIN, INT64_MIN};
-      for (int i = tid; i < n; i += kBlock) {
-        const uint64_t w = lds[i];
-        uint64_t cnt = w >> 40;
-        uint64_t sum = (uint64_t)((int64_t)(w & ((1ull << 40) - 1)) + (int64_t)cnt * pp.pack_min);
-        if (c0 == r0) {
-          p.table[k0 + i] = cnt;      // COUNT (slot 0)
-          p.table[G + k0 + i] = sum;  // SUM
-        } else {
-          cnt += p.table[k0 + i];
-          sum += p.table[G + k0 + i];
-          p.table[k0 + i] = cnt;
-          p.table[G + k0 + i] = sum;
-        }
-        if (last && pp.chunk_cnt && cnt) {  // the compaction's count pass, from the words in hand
-          ++present;
-          mn[0] = min(mn[0], (long long)cnt);
-          mx[0] = max(mx[0], (long long)cnt);
-          mn[1] = min(mn[1], (long long)sum);
-          mx[1] = max(mx[1], (long long)sum);
-        }
-      }
-      if (last && pp.chunk_cnt) {  // workgroup-uniform
-        __shared__ unsigned long long red_cnt[kBlock / 64];
-        __shared__ long long red_mm[kBlock / 64][4];
-        const int lane = tid & 63, wv = tid >> 6;
-        unsigned long long c = present;
-        for (int off = 32; off > 0; off >>= 1) {
-          c += __shfl_xor(c, off);
-          for (int s = 0; s < 2; ++s) {
-            mn[s] = min(mn[s], (long long)__shfl_xor(mn[s], off));
-            mx[s] = max(mx[s], (long long)__shfl_xor(mx[s], off));
-          }
-        }
-        if (lane == 0) {
-          red_cnt[wv] = c;
-          red_mm[wv][0] = mn[0];
-          red_mm[wv][1] = mn[1];
-          red_mm[wv][2] = mx[0];
-          red_mm[wv][3] = mx[1];
-        }
-        __syncthreads();
-        if (tid < 4) {
-          long long v = tid < 2 ? INT64_MAX : INT64_MIN;
-          for (int w = 0; w < kBlock / 64; ++w) v = tid < 2 ? min(v, red_mm[w][tid]) : max(v, red_mm[w][tid]);
-          pp.chunk_mm[4 * (int64_t)blockIdx.x + tid] = v;
-        }
-        if (tid == 0) {
-          unsigned long long t = 0;
-          for (int w = 0; w < kBlock / 64; ++w) t += red_cnt[w];
-          pp.chunk_cnt[blockIdx.x] = (uint32_t)t;
-        }
-      }
-      __syncthreads();  // the words are read before the next chunk clears them
-      c0 = c1;
-    } while (c0 < r1);
-    return;
-  }
-  // Two workgroups per CU (the LDS table), so latency is hidden by loads in flight per lane: NB records per lane
-  // per step, every load issued unconditionally (records past r1 re-read record r0 and are not accumulated).
-  constexpr int NB = 16;
-  for (uint32_t base = r0 + tid; base < r1; base += NB * kBlock) {
-    uint32_t ri[NB];
-    int k[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const uint32_t r = base + b * kBlock;
-      ri[b] = r < r1 ? r : r0;
-    }
-    int64_t pv[NB];  // fine_pack: the records' values
-    if (pp.fine_pack) {
-      const uint32_t* __restrict__ r32 = reinterpret_cast<const uint32_t*>(pp.rec_val);
-      const uint32_t low = (1u << pp.pshift) - 1u;
-      uint32_t wr[NB];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) wr[b] = r32[ri[b]];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        k[b] = (int)(wr[b] & low);
-        pv[b] = pp.pack_min + (int64_t)(wr[b] >> pp.pshift);
-      }
-    } else {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) k[b] = pp.rec_key[ri[b]];
-    }
-    for (int s = 0; s < ns; ++s) {
-      const int kind = p.slot_kind[s];
-      const int st = pp.slot_stream[s];
-      uint64_t w[NB];
-      if (st < 0) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) w[b] = 0ull;
-      } else if (pp.fine_pack) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) w[b] = (uint64_t)pv[b];
-      } else if (pp.val32) {
-        const int32_t* __restrict__ r32 = reinterpret_cast<const int32_t*>(pp.rec_val) + (int64_t)st * pp.rec_cap;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) w[b] = (uint64_t)(int64_t)r32[ri[b]];
-      } else {
-        const uint64_t* __restrict__ r64 = pp.rec_val + (int64_t)st * pp.rec_cap;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) w[b] = r64[ri[b]];
-      }
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-        if (base + b * kBlock < r1)
-          accumulate<MODE_LDS>(lds + (int64_t)s * PR, k[b], kind, (int64_t)w[b], __longlong_as_double((long long)w[b]));
-    }
-  }
-  __syncthreads();
-  const int64_t G = p.num_keys_total;
-  const int64_t k0 = (int64_t)blockIdx.x * PR;
-  const int n = (int)(G - k0 < PR ? G - k0 : PR);
-  for (int s = 0; s < ns; ++s)
-    for (int i = tid; i < n; i += kBlock) p.table[(int64_t)s * G + k0 + i] = lds[(int64_t)s * PR + i];
+// The body is part_aggregate_body.inc; the FX instance (plans with SLOT_SUM_FX slots: agreed plans of
+// PGPU_OPT_EXACT_FP_SUM) is a kernel of its own in an object of its own (k_partition_fx.hip defines PGPU_PARTITION_FX
+// and gets the FX kernels instead of the plain ones), so this one keeps its registers and arguments.
+#ifdef PGPU_PARTITION_FX
+__global__ __launch_bounds__(kBlock) void part_aggregate_fx_kernel(const KPartParamsFx pp) {
+  constexpr bool FX = true;
+#include "part_aggregate_body.inc"
 }
+#else
+__global__ __launch_bounds__(kBlock) void part_aggregate_kernel(const KPartParams pp) {
+  constexpr bool FX = false;
+#include "part_aggregate_body.inc"
+}
+#endif
 
 // Slot of hashed key `hk` in an LDS hash table of 2^sbits u32 entries (empty = ~0u), inserted if absent, or -1
 // after kHashPartProbes probes.  Start slot: the sbits of hk below the partition's pbits.
@@ -814,214 +676,16 @@ __device__ __forceinline__ int lds_hash_slot(uint32_t* keys, uint32_t key, int p
 // a record whose key finds no slot is written back at the front of the run (in place: every record of a batch is
 // loaded before any of the batch is written, and the write position never passes the records read) and waits for
 // the next round, so every round places at least one new key and the loop ends.
-__global__ __launch_bounds__(kBlock) void part_hash_aggregate_kernel(const KPartParams pp) {
-  extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
-  const KParams& p = pp.base;
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (p.deadline && p.stats[5]) return;
-  const int S = 1 << pp.sbits;
-  const int ns = p.num_slots, nst = pp.num_streams;
-  uint32_t* keys = reinterpret_cast<uint32_t*>(lds + (size_t)ns * S);
-  __shared__ uint32_t pending;
-  __shared__ uint32_t wave_tot[kBlock / 64];
-  __shared__ unsigned long long blk_base;
-  // this partition's range of every slot's words over all rounds (order-preserving u64: min at [s], max at [ns + s])
-  __shared__ unsigned long long blk_mm[2 * kMaxSlots];
-  if (pp.out_mm)
-    for (int i = tid; i < 2 * ns; i += kBlock) blk_mm[i] = i < ns ? ~0ull : 0ull;
-  const uint32_t r0 = pp.part_start[blockIdx.x];
-  uint32_t n = pp.part_start[blockIdx.x + 1] - r0;
-  const int64_t cap = pp.rec_cap;
-  constexpr int NB = 8;
-  // COUNT + SUM in one LDS word (slot 0's row) when the partition's records bound both halves (uniform per
-  // workgroup): (1 << 40) | (value - pack_min) per record, split when the round's groups are written
-  const bool cs = pp.cs_pack && n < (1u << 24) && (uint64_t)n * (uint64_t)pp.pack_range < (1ull << 40);
-  while (n > 0) {
-    for (int i = tid; i < S; i += kBlock) keys[i] = ~0u;
-    for (int i = tid; i < ns * S; i += kBlock) lds[i] = slot_init(p.slot_kind[i >> pp.sbits]);
-    if (tid == 0) pending = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += NB * kBlock) {
-      uint32_t key[NB];  // hashed keys
-      uint64_t v[NB][kHashPartStreams];
-      uint32_t w32[NB];  // fine_pack: the packed records as read (written back as they are when left pending)
-      if (pp.fine_pack) {
-        const uint32_t* __restrict__ r32 = reinterpret_cast<const uint32_t*>(pp.rec_val);
-        const int lb = 32 - pp.pbits;
-        const uint32_t hi = (uint32_t)blockIdx.x << lb, hlow = (1u << lb) - 1u;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const uint32_t i = base + b * kBlock + tid;
-          w32[b] = r32[r0 + (i < n ? i : 0u)];
-          key[b] = i < n ? hi | (w32[b] & hlow) : ~0u;
-          v[b][0] = (uint64_t)(pp.pack_min + (int64_t)(w32[b] >> lb));
-#pragma unroll
-          for (int st = 1; st < kHashPartStreams; ++st) v[b][st] = 0ull;
-        }
-      } else {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const uint32_t i = base + b * kBlock + tid;
-          const uint32_t r = r0 + (i < n ? i : 0u);
-          w32[b] = 0;
-          key[b] = i < n ? pp.rec_key32[r] : ~0u;
-#pragma unroll
-          for (int st = 0; st < kHashPartStreams; ++st)
-            v[b][st] = st >= nst ? 0ull
-                       : pp.val32 ? (uint64_t)(int64_t)reinterpret_cast<const int32_t*>(pp.rec_val)[st * cap + r]
-                                  : pp.rec_val[st * cap + r];
-        }
-      }
-      __syncthreads();  // the batch is in registers before any record of it is overwritten by a pending one
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        if (key[b] == ~0u) continue;
-        const int slot = lds_hash_slot(keys, key[b], pp.pbits, pp.sbits);
-        if (slot < 0) {
-          const uint32_t at = r0 + atomicAdd(&pending, 1u);
-          if (pp.fine_pack) {
-            reinterpret_cast<uint32_t*>(pp.rec_val)[at] = w32[b];
-            continue;
-          }
-          pp.rec_key32[at] = key[b];
-#pragma unroll
-          for (int st = 0; st < kHashPartStreams; ++st)
-            if (st < nst) {
-              if (pp.val32) reinterpret_cast<uint32_t*>(pp.rec_val)[st * cap + at] = (uint32_t)v[b][st];
-              else pp.rec_val[st * cap + at] = v[b][st];
-            }
-          continue;
-        }
-        if (cs) {
-          atomicAdd(reinterpret_cast<unsigned long long*>(lds) + slot,
-                    (1ull << 40) | (unsigned long long)((int64_t)v[b][0] - pp.pack_min));
-          continue;
-        }
-        for (int s = 0; s < ns; ++s) {
-          const int st = pp.slot_stream[s];
-          uint64_t w = 0;
-#pragma unroll
-          for (int j = 0; j < kHashPartStreams; ++j)
-            if (j == st) w = v[b][j];
-          accumulate<MODE_LDS>(lds + (int64_t)s * S, slot, p.slot_kind[s], (int64_t)w,
-                               __longlong_as_double((long long)w));
-        }
-      }
-    }
-    __syncthreads();
-    // append this round's groups with one reservation per workgroup (a single global counter: per-wave atomics
-    // would queue 4 x 2^sbits / 256 of them per partition at one address): waves count their entries by ballot, the
-    // workgroup reserves their sum, each wave writes a contiguous run
-    uint32_t mine = 0;
-    for (int i0 = 0; i0 < S; i0 += kBlock) {
-      const int i = i0 + tid;
-      mine += (uint32_t)__popcll(__ballot(i < S && keys[i] != ~0u));
-    }
-    if (lane == 0) wave_tot[tid >> 6] = mine;
-    __syncthreads();
-    if (tid == 0) {
-      uint32_t tot = 0;
-      for (int w = 0; w < kBlock / 64; ++w) tot += wave_tot[w];
-      blk_base = tot ? atomicAdd(pp.out_count, (unsigned long long)tot) : 0ull;
-    }
-    __syncthreads();
-    uint64_t at = blk_base;
-    for (int w = 0; w < (tid >> 6); ++w) at += wave_tot[w];
-    // the slot ranges of the groups written, tracked in registers while writing them when there are few slots (the
-    // compact result's widths; order-preserving u64), else by a pass over the table below
-    constexpr int kMmRegs = 4;
-    const bool mm_regs = pp.out_mm && ns <= kMmRegs;
-    unsigned long long rlo[kMmRegs], rhi[kMmRegs];
-#pragma unroll
-    for (int s = 0; s < kMmRegs; ++s) {
-      rlo[s] = ~0ull;
-      rhi[s] = 0ull;
-    }
-    for (int i0 = 0; i0 < S; i0 += kBlock) {
-      const int i = i0 + tid;
-      const bool occ = i < S && keys[i] != ~0u;
-      const uint64_t bal = __ballot(occ);
-      if (occ) {
-        const uint64_t r = at + (uint64_t)__popcll(bal & ((1ull << lane) - 1ull));
-        uint64_t* o = pp.out_rec + r * (uint64_t)(1 + ns);
-        const bool in_cap = r < (uint64_t)pp.out_cap;  // past it: counted, not written; finalize reports the overflow
-        if (in_cap) o[0] = (uint64_t)(keys[i] * kHashInv);  // the composite key back from its hash
-        if (cs) {
-          const uint64_t w = lds[i], c = w >> 40;
-          const uint64_t sum = (uint64_t)((int64_t)(w & ((1ull << 40) - 1)) + (int64_t)c * pp.pack_min);
-          if (in_cap) {
-            o[1] = c;
-            o[2] = sum;
-          }
-          rlo[0] = min(rlo[0], (unsigned long long)(c ^ (1ull << 63)));
-          rhi[0] = max(rhi[0], (unsigned long long)(c ^ (1ull << 63)));
-          rlo[1] = min(rlo[1], (unsigned long long)(sum ^ (1ull << 63)));
-          rhi[1] = max(rhi[1], (unsigned long long)(sum ^ (1ull << 63)));
-        } else if (mm_regs) {
-#pragma unroll
-          for (int s = 0; s < kMmRegs; ++s)
-            if (s < ns) {
-              const uint64_t w = lds[(int64_t)s * S + i];
-              if (in_cap) o[1 + s] = w;
-              rlo[s] = min(rlo[s], (unsigned long long)(w ^ (1ull << 63)));
-              rhi[s] = max(rhi[s], (unsigned long long)(w ^ (1ull << 63)));
-            }
-        } else if (in_cap) {
-          for (int s = 0; s < ns; ++s) o[1 + s] = lds[(int64_t)s * S + i];
-        }
-      }
-      at += (uint64_t)__popcll(bal);
-    }
-    if (mm_regs) {
-#pragma unroll
-      for (int s = 0; s < kMmRegs; ++s) {
-        if (s >= ns) continue;
-        unsigned long long lo = rlo[s], hi = rhi[s];
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long a = (unsigned long long)__shfl_xor((long long)lo, o);
-          const unsigned long long b = (unsigned long long)__shfl_xor((long long)hi, o);
-          lo = a < lo ? a : lo;
-          hi = b > hi ? b : hi;
-        }
-        if (lane == 0) {
-          atomicMin(&blk_mm[s], lo);
-          atomicMax(&blk_mm[ns + s], hi);
-        }
-      }
-    } else if (pp.out_mm) {  // many slots: per slot a pass over the round's entries, per wave one LDS atomic each
-      for (int s = 0; s < ns; ++s) {
-        unsigned long long lo = ~0ull, hi = 0ull;
-        for (int i = tid; i < S; i += kBlock) {
-          if (keys[i] == ~0u) continue;
-          uint64_t w;
-          if (cs) {
-            const uint64_t x = lds[i], c = x >> 40;
-            w = s == 0 ? c : (uint64_t)((int64_t)(x & ((1ull << 40) - 1)) + (int64_t)c * pp.pack_min);
-          } else {
-            w = lds[(int64_t)s * S + i];
-          }
-          const unsigned long long o = w ^ (1ull << 63);
-          lo = o < lo ? o : lo;
-          hi = o > hi ? o : hi;
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long a = (unsigned long long)__shfl_xor((long long)lo, o);
-          const unsigned long long b = (unsigned long long)__shfl_xor((long long)hi, o);
-          lo = a < lo ? a : lo;
-          hi = b > hi ? b : hi;
-        }
-        if (lane == 0) {
-          atomicMin(&blk_mm[s], lo);
-          atomicMax(&blk_mm[ns + s], hi);
-        }
-      }
-    }
-    __syncthreads();
-    n = pending;
-    __syncthreads();
-  }
-  if (pp.out_mm)
-    for (int i = tid; i < 2 * ns; i += kBlock) pp.out_mm[(int64_t)blockIdx.x * 2 * ns + i] = blk_mm[i];
+#ifdef PGPU_PARTITION_FX
+__global__ __launch_bounds__(kBlock) void part_hash_aggregate_fx_kernel(const KPartParamsFx pp) {
+  constexpr bool FX = true;
+#include "part_hash_aggregate_body.inc"
 }
+#else
+__global__ __launch_bounds__(kBlock) void part_hash_aggregate_kernel(const KPartParams pp) {
+  constexpr bool FX = false;
+#include "part_hash_aggregate_body.inc"
+}
+#endif
 
 }  // namespace pgpu

@@ -676,10 +676,14 @@ struct pgpu_plan_s {
   // alone see SLOT_SUM_FX (exec_prologue).  fx: the plan has such slots.  fx_part: a part of a composite plan (its
   // result keeps the digits for the merge).  fx_scope: the segments whose operands and docs the formats cover when
   // they are more than the plan's own (the parts of a composite plan share their formats).
-  bool fx = false, fx_part = false;
+  // fx_agreed: made by pgpu_plan_create_agreed -- fx_ranges[a] is the range every rank agreed on for aggregation a
+  // (fx_sum.h FxAgree) and decides its slots and format in place of this plan's own segments; such a plan passes the
+  // cross-GPU entry points and takes the partitioned pipelines (K8d / K8h FX).
+  bool fx = false, fx_part = false, fx_agreed = false;
   std::vector<int32_t> slot_fx;
   std::vector<pgpu::FxFormat> slot_fmt;
   std::vector<Segment*> fx_scope;
+  std::vector<pgpu::FxAgree> fx_ranges;
   std::vector<int32_t> agg_fn, agg_slot, agg_col;   // per aggregation: fn, value slot (or -1), table column
   int num_projected = 0;
   // per-segment compiled data
@@ -823,19 +827,22 @@ struct pgpu_plan_s {
   int64_t star_docs_read = 0;                                // star-tree documents K6 read (after finalize)
 };
 
-// Plans / results carrying fixed-point FLOAT / DOUBLE sums (PGPU_OPT_EXACT_FP_SUM): the cross-GPU entry points decline
-// them -- the ranks' formats (E, K, W) come from their own segments and would have to be agreed on first.
+// Plans / results carrying fixed-point FLOAT / DOUBLE sums (PGPU_OPT_EXACT_FP_SUM).  The cross-GPU entry points decline
+// those whose formats (E, K, W) come from the rank's own segments (plan_fx_local / result_fx_local): digit sums of
+// different formats do not add.  Agreed plans (pgpu_plan_create_agreed) and the results made from them pass.
 inline bool plan_has_fx(const pgpu_plan_s* P) {
   if (P->fx) return true;
   for (const auto& part : P->parts)
     if (part.plan && part.plan->fx) return true;
   return false;
 }
+inline bool plan_fx_local(const pgpu_plan_s* P) { return !P->fx_agreed && plan_has_fx(P); }
 inline bool result_has_fx(const pgpu_result_s* r) {
   for (const pgpu::FxFormat& f : r->agg_fx)
     if (f.mode != pgpu::FX_NONE) return true;
   return false;
 }
+inline bool result_fx_local(const pgpu_result_s* r) { return !r->fx_agreed && result_has_fx(r); }
 inline int fx_decline(const char* what) {
   return fail(PGPU_ERR_UNSUPPORTED, "%s with PGPU_OPT_EXACT_FP_SUM: the ranks would have to agree on the "
                          "fixed-point format (E, K, W) first", what);

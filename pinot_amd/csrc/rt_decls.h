@@ -51,6 +51,9 @@ int plan_star_segment(pgpu_plan_s* P, size_t seg_index, Segment* s, const pgpu_q
                       const std::vector<std::vector<int>>& comps, const std::vector<LeafHost>& leaves, bool* used);
 SegStats classify_segment_stats(const pgpu_plan_s* P, uint64_t sig);
 bool int_sum_fits(const std::vector<Segment*>& segs, int col);
+long double int_sum_bound(const std::vector<Segment*>& segs, int col);
+FxRange fx_operand_range(pgpu_table_s* t, const std::vector<Segment*>& segs, const pgpu_query* q, int tcol, int64_t* docs);
+int query_fp_sum_ranges(pgpu_table_s* t, const std::vector<Segment*>& segs, const pgpu_query* q, FxAgree* out);
 int32_t pack_slot_for(const pgpu_table_s* t, const pgpu_plan_s* P, const pgpu_query* q, int64_t max_count,
                       int shift);
 int32_t lds_pack_slot(const pgpu_table_s* t, const pgpu_plan_s* P, const pgpu_query* q, int64_t G);
@@ -95,8 +98,9 @@ int plan_finalize_impl(pgpu_plan_s* P, hipStream_t stream, const void* d_table, 
                        pgpu_result_s* R);
 
 // rt_groups.cpp
+// agreed: the ranges of pgpu_plan_create_agreed (one per aggregation), handed to the parts; null for a plain plan
 int split_for_groups_limit(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, const pgpu_query* q,
-                           pgpu_plan_s* P, bool* composite);
+                           pgpu_plan_s* P, bool* composite, const FxAgree* agreed = nullptr);
 int composite_finalize(pgpu_plan_s* P, hipStream_t stream, pgpu_result_s* R);
 bool plan_cache_enabled(const pgpu_table_s* t, const pgpu_query* q);
 std::string plan_cache_key(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, const pgpu_query* q);

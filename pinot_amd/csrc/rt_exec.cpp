@@ -700,7 +700,8 @@ int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const Laun
         P->k8d_counts = true;
       }
     }
-    if (launch_partitioned(pp, grid, P->part_lds, stream))
+    const KFxSplit fxs = fx_split(P);  // (plans with SLOT_SUM_FX slots: K8d / K8h split the records' doubles)
+    if (launch_partitioned(pp, grid, P->part_lds, stream, P->fx ? &fxs : nullptr))
       return fail(PGPU_ERR_DEVICE, "partitioned group-by launch failed: %s", hipGetErrorString(hipGetLastError()));
   } else if (C.num_tiles > 0) {
     static const bool wg_times = diag("wgtimes");
@@ -1248,6 +1249,7 @@ int plan_finalize_impl(pgpu_plan_s* P, hipStream_t stream, const void* d_table, 
       any = true;
     }
     R->fx_pending.store(any && !P->fx_part, std::memory_order_release);
+    R->fx_agreed = P->fx_agreed;
   }
   int64_t generic_entries = 0;
   if (!P->generic.empty()) {  // the leaves' bitmaps were copied into maskstage by the (synchronised) stream

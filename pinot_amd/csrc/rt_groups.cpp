@@ -15,7 +15,7 @@ namespace pgpu {
 // segment, each segment's groups in its holder's order (ArrayBasedHolder: key order; map holders: first-seen
 // order) -- one of the orders Pinot's combine threads can produce, the one its single-threaded run produces.
 int split_for_groups_limit(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, const pgpu_query* q,
-                           pgpu_plan_s* P, bool* composite) {
+                           pgpu_plan_s* P, bool* composite, const FxAgree* agreed) {
   *composite = false;
   if (!q || q->num_group_by <= 0 || q->num_groups_limit <= 0 || nsegs <= 0) return 0;
   const int64_t L = q->num_groups_limit;
@@ -61,7 +61,12 @@ int split_for_groups_limit(pgpu_table_s* t, const int64_t* handles, int32_t nseg
     part.truncate = truncate;
     std::vector<int64_t> hs;
     for (int32_t i : idx) hs.push_back(handles[i]);
-    if (q->options & PGPU_OPT_EXACT_FP_SUM) {
+    if (agreed) {
+      // the parts' digit sums are merged as integers, and with other ranks': the agreed formats in every part
+      part.plan->fx_part = true;
+      part.plan->fx_agreed = true;
+      part.plan->fx_ranges.assign(agreed, agreed + std::max(q->num_aggs, 0));
+    } else if (q->options & PGPU_OPT_EXACT_FP_SUM) {
       // the parts' digit sums are merged as integers: one fixed-point format over the segments and docs of them all
       part.plan->fx_part = true;
       std::lock_guard<std::mutex> g(t->mu);
@@ -81,6 +86,7 @@ int split_for_groups_limit(pgpu_table_s* t, const int64_t* handles, int32_t nseg
   }
   if (!rest.empty()) TRY(add_part(rest, false, false));
   P->composite = true;
+  P->fx_agreed = agreed != nullptr;
   *composite = true;
   P->table = t;
   P->num_groups_limit = L;
@@ -227,6 +233,7 @@ int composite_finalize(pgpu_plan_s* P, hipStream_t stream, pgpu_result_s* R) {
       R->agg_conv[a] = RCONV_F64;
   // fixed-point sums: the parts share their formats (fx_scope) and their digits were merged as integers above
   R->agg_fx = R0->agg_fx;
+  R->fx_agreed = P->fx_agreed;
   R->fx_pending.store(std::find(R->agg_conv.begin(), R->agg_conv.end(), (uint8_t)RCONV_FX) != R->agg_conv.end(),
                       std::memory_order_release);
   for (const auto& Ri : rs)

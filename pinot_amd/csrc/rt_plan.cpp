@@ -531,7 +531,11 @@ SegStats classify_segment_stats(const pgpu_plan_s* P, uint64_t sig) {
 }
 
 // True when an int64 accumulator cannot overflow for SUM / AVG over integer column `col` of these segments.
-bool int_sum_fits(const std::vector<Segment*>& segs, int col) {
+bool int_sum_fits(const std::vector<Segment*>& segs, int col) { return int_sum_bound(segs, col) < 0x1p62L; }
+
+// The bound itself: sum over segments of numDocs x max |value| (what the ranks add up when they agree on one slot
+// layout, pgpu_fp_sum_range.int_sum_bound).
+long double int_sum_bound(const std::vector<Segment*>& segs, int col) {
   long double bound = 0;
   for (const Segment* s : segs) {
     const Column& c = s->cols[col];
@@ -542,7 +546,55 @@ bool int_sum_fits(const std::vector<Segment*>& segs, int col) {
     const long double m = std::max(std::fabs(lo), std::fabs(hi));
     bound += m * (long double)s->num_docs;
   }
-  return bound < 0x1p62L;
+  return bound;
+}
+
+// The range of SUM / AVG operands over table column tcol that a plan of q over `segs` can read (fx_sum.h): the
+// segments' dictionaries or raw docs, and the pre-aggregated doubles of the star-trees that may answer the query;
+// *docs: the documents of the same segments.
+FxRange fx_operand_range(pgpu_table_s* t, const std::vector<Segment*>& segs, const pgpu_query* q, int tcol,
+                         int64_t* docs) {
+  FxRange r;
+  *docs = 0;
+  std::lock_guard<std::mutex> g(t->mu);  // Column.fx is filled on first use
+  for (Segment* s : segs) {
+    *docs += s->num_docs;
+    Column& c = s->cols[tcol];
+    if (!c.fx_known) {
+      if (is_int_type(c.dict.type)) for (int64_t v : c.dict.iv) fx_range_add(&c.fx, (double)v);
+      else for (double v : c.dict.dv) fx_range_add(&c.fx, v);
+      c.fx_known = true;
+    }
+    fx_range_merge(&r, c.fx);
+    if (s->star && !(q->options & PGPU_OPT_NO_STAR_TREE))
+      for (int fn : {PGPU_AGG_SUM, PGPU_AGG_AVG}) {
+        const int m = s->star->pair(fn, tcol);
+        if (m >= 0 && m < (int)s->star->mf_fx.size()) fx_range_merge(&r, s->star->mf_fx[m]);
+      }
+  }
+  return r;
+}
+
+// pgpu_query_fp_sum_ranges: per aggregation of q what this rank reports to the agreement -- the operands' range and
+// the docs exactly as a plain plan's format reads them, and int_sum_fits's own bound.
+int query_fp_sum_ranges(pgpu_table_s* t, const std::vector<Segment*>& segs, const pgpu_query* q, FxAgree* out) {
+  const int ncols = (int)t->names.size();
+  for (int i = 0; i < q->num_aggs; ++i) {
+    const pgpu_agg& a = q->aggs[i];
+    out[i] = FxAgree{};
+    if (a.fn != PGPU_AGG_SUM && a.fn != PGPU_AGG_AVG) continue;
+    if (a.column < 0 || a.column >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: bad column", i);
+    if (t->types[a.column] == PGPU_STRING) return fail(PGPU_ERR_UNSUPPORTED, "numeric aggregation over a STRING column");
+    FxAgree& o = out[i];
+    o.is_sum = 1;
+    const FxRange r = fx_operand_range(t, segs, q, a.column, &o.docs);
+    o.any = r.any ? 1 : 0;
+    o.finite = r.finite ? 1 : 0;
+    o.E = r.any ? r.E : 0;
+    o.L = r.any ? r.L : 0;
+    if (is_int_type(t->types[a.column])) o.int_sum_bound = fx_round_up(int_sum_bound(segs, a.column));
+  }
+  return 0;
 }
 
 int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chunks, ExecCtx& X);
@@ -789,25 +841,8 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
   // that may answer the query), the headroom from the docs of the same segments.  Mode 0 when an operand is not
   // finite: the sum keeps its float64 slot.
   auto fx_format_for = [&](int tcol) -> FxFormat {
-    const std::vector<Segment*>& scope = P->fx_scope.empty() ? P->segs : P->fx_scope;
-    FxRange r;
     int64_t docs = 0;
-    std::lock_guard<std::mutex> g(t->mu);  // Column.fx is filled on first use
-    for (Segment* s : scope) {
-      docs += s->num_docs;
-      Column& c = s->cols[tcol];
-      if (!c.fx_known) {
-        if (is_int_type(c.dict.type)) for (int64_t v : c.dict.iv) fx_range_add(&c.fx, (double)v);
-        else for (double v : c.dict.dv) fx_range_add(&c.fx, v);
-        c.fx_known = true;
-      }
-      fx_range_merge(&r, c.fx);
-      if (s->star && !(q->options & PGPU_OPT_NO_STAR_TREE))
-        for (int fn : {PGPU_AGG_SUM, PGPU_AGG_AVG}) {
-          const int m = s->star->pair(fn, tcol);
-          if (m >= 0 && m < (int)s->star->mf_fx.size()) fx_range_merge(&r, s->star->mf_fx[m]);
-        }
-    }
+    const FxRange r = fx_operand_range(t, P->fx_scope.empty() ? P->segs : P->fx_scope, q, tcol, &docs);
     return fx_format(r, docs);
   };
   // its W digit slots: adjacent, of the one column, shared by SUM and AVG of the column
@@ -824,6 +859,13 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
     P->fx = true;
     return (int)P->slot_kind.size() - f.W;
   };
+  if (P->fx_agreed) {
+    if (!(q->options & PGPU_OPT_EXACT_FP_SUM)) return fail(PGPU_ERR_INVALID_ARGUMENT, "agreed ranges without PGPU_OPT_EXACT_FP_SUM");
+    if ((int)P->fx_ranges.size() != q->num_aggs) return fail(PGPU_ERR_INVALID_ARGUMENT, "one agreed range per aggregation");
+    for (int i = 0; i < q->num_aggs; ++i)
+      if ((P->fx_ranges[i].is_sum != 0) != (q->aggs[i].fn == PGPU_AGG_SUM || q->aggs[i].fn == PGPU_AGG_AVG))
+        return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: the agreed range is not of this aggregation", i);
+  }
   for (int i = 0; i < q->num_aggs; ++i) {
     const pgpu_agg& a = q->aggs[i];
     P->agg_fn.push_back(a.fn);
@@ -840,6 +882,9 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
         // the values (Pinot's own arithmetic, SumAggregationFunction.java:66-73) instead of wrapping.
         // (fx_scope: the parts of a composite plan with fixed-point sums decide over the segments of them all, so
         // their slots line up)
+        // (an agreed plan: the bound summed over every rank's segments, so every rank has the same slots)
+        if (P->fx_agreed) kind = is_int_type(type) && P->fx_ranges[i].int_sum_bound < 0x1p62 ? SLOT_SUM_I64 : SLOT_SUM_F64;
+        else
         kind = is_int_type(type) && int_sum_fits(P->fx_scope.empty() ? P->segs : P->fx_scope, a.column) ? SLOT_SUM_I64
                                                                                                          : SLOT_SUM_F64;
         break;
@@ -848,7 +893,18 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
       default: return fail(PGPU_ERR_UNSUPPORTED, "aggregation function %d", a.fn);
     }
     if (kind == SLOT_SUM_F64 && (q->options & PGPU_OPT_EXACT_FP_SUM)) {
-      const FxFormat f = fx_format_for(a.column);
+      FxFormat f;
+      if (P->fx_agreed) {  // the agreed range and the docs of every rank (fx_sum.h FxAgree)
+        const FxAgree& g = P->fx_ranges[i];
+        FxRange r;
+        r.E = g.E;
+        r.L = g.L;
+        r.any = g.any != 0;
+        r.finite = g.finite != 0;
+        f = fx_format(r, g.docs);
+      } else {
+        f = fx_format_for(a.column);
+      }
       if (f.mode != FX_NONE) {
         P->agg_slot.push_back(add_fx_slots(a.column, f));
         continue;
@@ -864,11 +920,14 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
     P->slot_fmt.push_back(FxFormat{});
   }
   if (P->fx) {
-    // The record passes of the partitioned pipelines (K8a-K8h) carry one 8-byte stream per operand, not digit streams,
-    // and a streamed plan configures before its later chunks are planned: a plan with fixed-point sums takes the
-    // scan kernel's global / hash tables, in one launch.
-    P->cfg.partitioned_group_by = 0;
-    P->cfg.hash_partitions = 0;
+    // A streamed plan configures before its later chunks are planned: a plan with fixed-point sums runs as one launch.
+    // A plain one takes the scan kernel's global / hash tables (pinned by the tests of the option as it shipped); an
+    // agreed one keeps the partitioned pipelines, whose record passes carry the operand's double as one stream and
+    // whose aggregate kernels split it (K8d / K8h FX, partition.h).
+    if (!P->fx_agreed) {
+      P->cfg.partitioned_group_by = 0;
+      P->cfg.hash_partitions = 0;
+    }
     P->cfg.stream_chunks = 1;
   }
   if ((int)P->slot_kind.size() > kMaxSlots) return fail(PGPU_ERR_UNSUPPORTED, "too many accumulators");
@@ -1540,7 +1599,8 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
       }
       std::vector<int32_t> scol, sf64, sstream(nslots, -1);
       for (int sl = 1; sl < nslots; ++sl) {
-        const int f64 = P->slot_kind[sl] == SLOT_SUM_F64 ? 1 : 0;
+        // (the W digit slots of a column: one stream of its doubles, split where the records are accumulated)
+        const int f64 = P->slot_kind[sl] == SLOT_SUM_F64 || P->slot_fx[sl] >= 0 ? 1 : 0;
         int k = -1;
         for (size_t j = 0; j < scol.size(); ++j)
           if (scol[j] == P->slot_col[sl] && sf64[j] == f64) k = (int)j;

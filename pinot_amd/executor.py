@@ -483,22 +483,48 @@ class GpuTable:
         vals = r.values[0] if len(r) else aggregation_defaults(query.aggregations)
         return AggregationResult(list(vals), r.stats)
 
-    def plan(self, handles, query):
-        return Plan(self, handles, query)
+    def fp_sum_ranges(self, handles, query):
+        """pgpu_query_fp_sum_ranges: per aggregation of `query` (exact_fp_sum=True) what a plan over these segments
+        could read -- this rank's share of the cross-GPU format agreement (combine.agree_fp_sum_ranges*).  A list of
+        _lib.FpSumRangeC."""
+        if isinstance(query, str):
+            from .query import parse_query
+            query = parse_query(query)
+        hs = np.ascontiguousarray(list(handles), dtype=np.int64)
+        q, keep = query.to_c(self.index)
+        na = len(query.aggregations)
+        out = (L.FpSumRangeC * max(na, 1))()
+        L.check(self.lib.pgpu_query_fp_sum_ranges(self.handle, L.ptr(hs, ctypes.c_int64), len(hs), ctypes.byref(q), out))
+        return [L.FpSumRangeC.from_tuple(out[a].as_tuple()) for a in range(na)]
+
+    def plan(self, handles, query, fp_sum_ranges=None):
+        """fp_sum_ranges: the agreed ranges (one per aggregation; a single rank passes its own fp_sum_ranges()) -- an
+        agreed plan (pgpu_plan_create_agreed), which the cross-GPU merges accept and the partitioned pipelines run."""
+        return Plan(self, handles, query, fp_sum_ranges=fp_sum_ranges)
 
     def execute_groupby(self, handles, query, stream=None):
         with Plan(self, handles, query, execute=(stream, None)) as p:
             return p.finalize(stream)
 
-    def plan_execute(self, handles, query, stream=None, d_table=None):
+    def plan_execute(self, handles, query, stream=None, d_table=None, fp_sum_ranges=None):
         """Plan + execute, streamed (pgpu_plan_create_execute): chunks of segments are launched while the rest
-        is still being planned.  Returns the executed Plan (finalize it, or merge across GPUs first)."""
+        is still being planned.  Returns the executed Plan (finalize it, or merge across GPUs first).
+        fp_sum_ranges: an agreed plan (see plan()) is created, then executed as one launch."""
+        if fp_sum_ranges is not None:
+            p = Plan(self, handles, query, fp_sum_ranges=fp_sum_ranges)
+            try:
+                p.execute(stream, d_table)
+            except Exception:
+                p.close()
+                raise
+            return p
         return Plan(self, handles, query, execute=(stream, d_table))
 
 
 class Plan:
-    def __init__(self, table, handles, query, execute=None):
-        """execute=(stream, d_table): create and execute in one streamed call (pgpu_plan_create_execute)."""
+    def __init__(self, table, handles, query, execute=None, fp_sum_ranges=None):
+        """execute=(stream, d_table): create and execute in one streamed call (pgpu_plan_create_execute).
+        fp_sum_ranges: the agreed ranges of pgpu_plan_create_agreed (not with execute)."""
         if isinstance(query, str):
             from .query import parse_query
             query = parse_query(query)
@@ -509,7 +535,13 @@ class Plan:
             np.ascontiguousarray(list(handles), dtype=np.int64)
         q, keep = query.to_c(table.index)
         h = ctypes.c_void_p()
-        if execute is None:
+        if fp_sum_ranges is not None:
+            assert execute is None, "an agreed plan is created, then executed"
+            if len(fp_sum_ranges) != len(query.aggregations):
+                raise ValueError("one agreed range per aggregation")
+            L.check(self.lib.pgpu_plan_create_agreed(table.handle, L.ptr(hs, ctypes.c_int64), len(hs), ctypes.byref(q),
+                                                     L.fp_sum_range_array(fp_sum_ranges), ctypes.byref(h)))
+        elif execute is None:
             L.check(self.lib.pgpu_plan_create(table.handle, L.ptr(hs, ctypes.c_int64), len(hs), ctypes.byref(q),
                                               ctypes.byref(h)))
         else:
