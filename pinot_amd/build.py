@@ -12,8 +12,8 @@ LIB_PATH = os.path.join(HERE, "libpinotgpu.so")
 # (source, extra flags, object name): the scan kernels are compiled once per accumulator mode so the objects
 # build in parallel.
 # the host runtime (rt.h): rt_* (core, dictionaries, planning, execution, numGroupsLimit / plan cache) and the C ABI
-RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_exec", "rt_groups", "abi_table", "abi_plan", "abi_combine",
-           "abi_result"]
+RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_plan_create", "rt_exec", "rt_groups", "abi_table", "abi_plan",
+           "abi_combine", "abi_result"]
 SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTIME] + [("startree.cpp", [], "startree"),
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
            ("k_partition.hip", [], "k_partition"), ("k_partition_fx.hip", [], "k_partition_fx"),
@@ -157,81 +157,47 @@ def build_host_fuzz(force=False):
     return FUZZ_PATH
 
 
-SPLIT_CHECK_PATH = os.path.join(ROOT, "build", "tile_split_check")
-
-
-def build_tile_split_check(force=False):
-    """build/tile_split_check: tools/tile_split_check.cpp, which includes csrc/tile_split.h and nothing else of the
-    library, under AddressSanitizer + UndefinedBehaviorSanitizer.  One compile, no library linked."""
-    src = os.path.join(ROOT, "tools", "tile_split_check.cpp")
-    hdr = os.path.join(CSRC, "tile_split.h")
-    if not force and os.path.exists(SPLIT_CHECK_PATH) and \
-            all(os.path.getmtime(f) <= os.path.getmtime(SPLIT_CHECK_PATH) for f in (src, hdr)):
-        return SPLIT_CHECK_PATH
-    os.makedirs(os.path.dirname(SPLIT_CHECK_PATH), exist_ok=True)
+def _build_header_check(name, src, hdr, force=False):
+    """build/<name>: tools/<src>, which includes csrc/<hdr> and nothing else of the library, under AddressSanitizer +
+    UndefinedBehaviorSanitizer.  One compile, no library linked; rebuilt when the source or the header is newer."""
+    out = os.path.join(ROOT, "build", name)
+    src = os.path.join(ROOT, "tools", src)
+    hdr = os.path.join(CSRC, hdr)
+    if not force and os.path.exists(out) and all(os.path.getmtime(f) <= os.path.getmtime(out) for f in (src, hdr)):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     hipcc = _hipcc()
-    obj = os.path.join(ROOT, "build", "tile_split_check.o")
+    obj = out + ".o"
     # (the sanitizers are host-only flags: compiled as the library's sources are, then linked with their runtimes)
     for cmd in ([hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS +
                 ["-c", src, "-o", obj],
                 [hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined", obj,
-                 "-o", SPLIT_CHECK_PATH + ".tmp"]):
+                 "-o", out + ".tmp"]):
         res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if res.returncode != 0:
-            raise RuntimeError("hipcc (tile_split_check) failed:\n" + res.stdout[-6000:])
-    os.replace(SPLIT_CHECK_PATH + ".tmp", SPLIT_CHECK_PATH)
-    return SPLIT_CHECK_PATH
+            raise RuntimeError("hipcc (%s) failed:\n%s" % (name, res.stdout[-6000:]))
+    os.replace(out + ".tmp", out)
+    return out
 
 
+SPLIT_CHECK_PATH = os.path.join(ROOT, "build", "tile_split_check")
 FX_CHECK_PATH = os.path.join(ROOT, "build", "fx_sum_check")
-
-
-def build_fx_sum_check(force=False):
-    """build/fx_sum_check: tools/fx_sum_check.cpp, which includes csrc/fx_sum.h and nothing else of the library, under
-    AddressSanitizer + UndefinedBehaviorSanitizer.  One compile, no library linked."""
-    src = os.path.join(ROOT, "tools", "fx_sum_check.cpp")
-    hdr = os.path.join(CSRC, "fx_sum.h")
-    if not force and os.path.exists(FX_CHECK_PATH) and \
-            all(os.path.getmtime(f) <= os.path.getmtime(FX_CHECK_PATH) for f in (src, hdr)):
-        return FX_CHECK_PATH
-    os.makedirs(os.path.dirname(FX_CHECK_PATH), exist_ok=True)
-    hipcc = _hipcc()
-    obj = os.path.join(ROOT, "build", "fx_sum_check.o")
-    for cmd in ([hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS +
-                ["-c", src, "-o", obj],
-                [hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined", obj,
-                 "-o", FX_CHECK_PATH + ".tmp"]):
-        res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        if res.returncode != 0:
-            raise RuntimeError("hipcc (fx_sum_check) failed:\n" + res.stdout[-6000:])
-    os.replace(FX_CHECK_PATH + ".tmp", FX_CHECK_PATH)
-    return FX_CHECK_PATH
-
-
 AGREE_CHECK_PATH = os.path.join(ROOT, "build", "fx_agree_check")
 
 
+def build_tile_split_check(force=False):
+    """The scan's tile split against its LEAP2 LDS reservation (tile_split.h)."""
+    return _build_header_check("tile_split_check", "tile_split_check.cpp", "tile_split.h", force)
+
+
+def build_fx_sum_check(force=False):
+    """The fixed-point sum formats (fx_sum.h)."""
+    return _build_header_check("fx_sum_check", "fx_sum_check.cpp", "fx_sum.h", force)
+
+
 def build_fx_agree_check(force=False):
-    """build/fx_agree_check: tools/fx_agree_check.cpp (the cross-rank agreement on the fixed-point format), which
-    includes csrc/fx_sum.h and nothing else of the library, under AddressSanitizer + UndefinedBehaviorSanitizer.  One
-    compile, no library linked."""
-    src = os.path.join(ROOT, "tools", "fx_agree_check.cpp")
-    hdr = os.path.join(CSRC, "fx_sum.h")
-    if not force and os.path.exists(AGREE_CHECK_PATH) and \
-            all(os.path.getmtime(f) <= os.path.getmtime(AGREE_CHECK_PATH) for f in (src, hdr)):
-        return AGREE_CHECK_PATH
-    os.makedirs(os.path.dirname(AGREE_CHECK_PATH), exist_ok=True)
-    hipcc = _hipcc()
-    obj = os.path.join(ROOT, "build", "fx_agree_check.o")
-    for cmd in ([hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS +
-                ["-c", src, "-o", obj],
-                [hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined", obj,
-                 "-o", AGREE_CHECK_PATH + ".tmp"]):
-        res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        if res.returncode != 0:
-            raise RuntimeError("hipcc (fx_agree_check) failed:\n" + res.stdout[-6000:])
-    os.replace(AGREE_CHECK_PATH + ".tmp", AGREE_CHECK_PATH)
-    return AGREE_CHECK_PATH
+    """The cross-rank agreement on the fixed-point format (fx_sum.h)."""
+    return _build_header_check("fx_agree_check", "fx_agree_check.cpp", "fx_sum.h", force)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 // rt.h -- the host runtime's model (tables, pinned segments, dictionaries, plans, scratch) and the functions
-// its sources share: rt_core.cpp (errors, diagnostics), rt_dict.cpp (dictionaries), rt_plan.cpp (planning),
-// rt_exec.cpp (execution, finalize), rt_groups.cpp (numGroupsLimit split, plan cache) and the C ABI in
-// abi_table.cpp / abi_plan.cpp / abi_combine.cpp / abi_result.cpp.  Not part of the ABI.
+// its sources share: rt_core.cpp (errors, diagnostics), rt_dict.cpp (dictionaries), rt_plan.cpp (predicates,
+// planning helpers), rt_plan_create.cpp (plan_create_impl's phases), rt_exec.cpp (execution, finalize),
+// rt_groups.cpp (numGroupsLimit split, plan cache) and the C ABI in abi_table.cpp / abi_plan.cpp / abi_combine.cpp /
+// abi_result.cpp.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>

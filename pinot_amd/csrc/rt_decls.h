@@ -50,6 +50,14 @@ void leaf_bitset(const LeafHost& L, int32_t card, std::vector<uint32_t>& w);
 int plan_star_segment(pgpu_plan_s* P, size_t seg_index, Segment* s, const pgpu_query* q,
                       const std::vector<std::vector<int>>& comps, const std::vector<LeafHost>& leaves, bool* used);
 SegStats classify_segment_stats(const pgpu_plan_s* P, uint64_t sig);
+bool column_int_ends(const Column& c, int64_t* lo, int64_t* hi);
+// The integer values of a table column over a segment list lie in [lo, hi] (lo > hi: there are none); `known` is
+// false when a segment has a non-empty dictionary without integer values.
+struct IntRange {
+  int64_t lo = INT64_MAX, hi = INT64_MIN;
+  bool known = true;
+};
+IntRange int_column_range(const std::vector<Segment*>& segs, int col);
 bool int_sum_fits(const std::vector<Segment*>& segs, int col);
 long double int_sum_bound(const std::vector<Segment*>& segs, int col);
 FxRange fx_operand_range(pgpu_table_s* t, const std::vector<Segment*>& segs, const pgpu_query* q, int tcol, int64_t* docs);
@@ -59,12 +67,17 @@ int32_t pack_slot_for(const pgpu_table_s* t, const pgpu_plan_s* P, const pgpu_qu
 int32_t lds_pack_slot(const pgpu_table_s* t, const pgpu_plan_s* P, const pgpu_query* q, int64_t G);
 int32_t hash_pack_slot(const pgpu_table_s* t, const pgpu_plan_s* P, const pgpu_query* q, int* shift);
 bool part_hash_eligible(const pgpu_plan_s* P, int64_t G);
+bool dense_part_eligible(const pgpu_plan_s* P, int nslots, int64_t G);
+bool part_eligible(const pgpu_plan_s* P, int nslots, int64_t G);
 void hash_part_bits(const pgpu_config& cfg, int64_t groups, int nslots, int* pbits, int* sbits);
 int part_coarse_shift(int num_parts);
 int part_coarse_runs(int num_parts);
+bool part_pass_shape(pgpu_plan_s* P, int64_t parts, int64_t tiles);
 void hash_part_resize(pgpu_plan_s* P, int64_t groups);
 int64_t part_hash_out_cap(const pgpu_plan_s* P);
 int part_hash_overflow(const pgpu_plan_s* P, uint64_t groups);
+
+// rt_plan_create.cpp
 int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, const pgpu_query* q, pgpu_plan_s* P,
                      const StreamExec* se = nullptr);
 

@@ -222,9 +222,6 @@ int ensure_value_map(pgpu_table_s* t, Segment& s, int col) {
   return 0;
 }
 
-int64_t padded_fwd_words(int64_t num_docs, int bits);
-int scan_variant(const pgpu_plan_s* P);
-
 // Identity forward index of the virtual $docId column over docs [0, n): Pinot's MSB-first fixed-bit layout of the
 // values 0..n-1 (a sorted "dictionary" of docIds), and the values as int64 (the MIN slot's keys).
 int ensure_docid(pgpu_table_s* t, int64_t n, hipStream_t stream) {
@@ -418,8 +415,6 @@ int parse_raw_column(int type, const pgpu_column_buffers& cb, int32_t num_docs, 
 }
 
 // Registers a segment whose columns have parsed dictionaries and device forward indexes.
-void plan_cache_clear(pgpu_table_s* t);
-
 int64_t register_segment(pgpu_table_s* t, std::unique_ptr<Segment> seg_in) {
   std::shared_ptr<Segment> seg(std::move(seg_in));
   t->version++;
