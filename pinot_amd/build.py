@@ -11,9 +11,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libpinotgpu.so")
 # (source, extra flags, object name): the scan kernels are compiled once per accumulator mode so the objects
 # build in parallel.
-# the host runtime (rt.h): rt_* (core, dictionaries, planning, execution, numGroupsLimit / plan cache) and the C ABI
-RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_plan_create", "rt_exec", "rt_groups", "abi_table", "abi_plan",
-           "abi_combine", "abi_result"]
+# the host runtime (rt.h): rt_* (core, dictionaries, planning, execution, finalize, numGroupsLimit / plan cache)
+# and the C ABI
+RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_plan_create", "rt_exec", "rt_finalize", "rt_groups", "abi_table",
+           "abi_plan", "abi_combine", "abi_result"]
 SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTIME] + [("startree.cpp", [], "startree"),
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
            ("k_partition.hip", [], "k_partition"), ("k_partition_fx.hip", [], "k_partition_fx"),

@@ -72,9 +72,9 @@ int build_hash_table(pgpu_plan_s* P, hipStream_t s, const uint64_t* d_records, i
 int part_hash_materialize(pgpu_plan_s* P, hipStream_t s) {
   if (!P->part_hash_live) return 0;
   Scratch* sc = P->scratch;
-  TRY(sc->stats.ensure(64));
+  TRY(sc->stats.ensure(kStatsBytes));
   if (P->d_stats != sc->stats.as<unsigned long long>()) {
-    HIP_TRY(hipMemcpyAsync(sc->stats.p, P->d_stats, 64, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(sc->stats.p, P->d_stats, kStatsBytes, hipMemcpyDeviceToDevice, s));
     P->d_stats = sc->stats.as<unsigned long long>();
   }
   TRY(sc->xstage.ensure(64));
@@ -109,9 +109,9 @@ int pgpu_plan_exchange_counts(pgpu_plan P, void* stream, int32_t nparts, int64_t
   TRY(sc->xstage.ensure((size_t)nparts * 8 + 64));
   uint64_t* st = reinterpret_cast<uint64_t*>(sc->xstage.p);
   HIP_TRY(hipMemcpyAsync(st, sc->counter.p, (size_t)nparts * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(st + nparts, P->d_stats, 48, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(st + nparts, P->d_stats, kStatsReadBytes, hipMemcpyDeviceToHost, s));
   TRY(wait_plan(P, s));
-  if (st[nparts + 5]) return timeout_fail(P);
+  if (decode_stats(st + nparts, kStatsReadWords).timed_out) return timeout_fail(P);
   P->xchg_counts.assign(nparts, 0);
   for (int p = 0; p < nparts; ++p) counts[p] = P->xchg_counts[p] = (int64_t)st[p];
   return 0;
@@ -153,7 +153,6 @@ int pgpu_plan_exchange_merge(pgpu_plan P, void* stream, const int32_t* kinds, co
   PGPU_ABI_GUARD;
   TRY(exchangeable(P));
   if (plan_fx_local(P)) return fx_decline("a cross-GPU exchange");
-  P->exported = false;
   P->k8d_counts = false;
   if (n < 0 || (n > 0 && !d_records) || n > (INT64_C(1) << 40))  // the table below holds >= 2n slots
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
@@ -168,9 +167,9 @@ int pgpu_plan_exchange_merge(pgpu_plan P, void* stream, const int32_t* kinds, co
     P->slot_kind.assign(kinds, kinds + nslots);
   }
   // the statistics words leave the table buffer (it is resized below)
-  TRY(sc->stats.ensure(64));
+  TRY(sc->stats.ensure(kStatsBytes));
   if (P->d_stats != sc->stats.as<unsigned long long>()) {
-    HIP_TRY(hipMemcpyAsync(sc->stats.p, P->d_stats, 64, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(sc->stats.p, P->d_stats, kStatsBytes, hipMemcpyDeviceToDevice, s));
     P->d_stats = sc->stats.as<unsigned long long>();
   }
   TRY(build_hash_table(P, s, reinterpret_cast<const uint64_t*>(d_records), n));
@@ -602,7 +601,6 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   PGPU_ABI_GUARD;
   if (!P || !c) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
-  P->exported = false;  // the table changes: finalize reads it from the device
   P->k8d_counts = false;
   if (mode == PGPU_COMBINE_LOCAL) {
     if (key_begin) *key_begin = 0;

@@ -61,8 +61,8 @@ __device__ __forceinline__ T load_off(const T* ubase, uint32_t byte_off) {
 __device__ __forceinline__ bool past_deadline(uint64_t deadline) {
   return deadline != 0 && (uint64_t)wall_clock64() > deadline;
 }
-// stats[5] != 0: some workgroup stopped at the deadline (the group table is partial; the host reports the timeout).
-__device__ __forceinline__ void flag_timeout(unsigned long long* stats) { atomicOr(stats + 5, 1ull); }
+// stats[STAT_TIMED_OUT] (5) != 0: some workgroup stopped at the deadline (the group table is partial; the host reports the timeout).
+__device__ __forceinline__ void flag_timeout(unsigned long long* stats) { atomicOr(stats + STAT_TIMED_OUT, 1ull); }
 
 // Value of doc `doc` in a packed column (PinotDataBitSet.readInt semantics).  The two-word window never leaves
 // the allocation thanks to the padding words.
@@ -448,7 +448,7 @@ __device__ __forceinline__ uint32_t eval_filter(const KParams& p, const SegView&
 }
 
 // Slot of `key` in an open-addressing table of `cap` (a power of two) slots, inserted if absent; linear probing,
-// at most `cap` probes: a full table returns -1 and sets *full (stats[4]; the host reports the error) instead of
+// at most `cap` probes: a full table returns -1 and sets *full (stats[STAT_HASH_FULL]; the host reports the error) instead of
 // spinning.  Tables are sized for a load <= 1/2 of the groups the plan can produce, so this never happens in a
 // correct plan -- it only bounds every wave's loop.
 __device__ __forceinline__ int64_t hash_slot(unsigned long long* __restrict__ keys, int64_t cap, uint64_t key,
@@ -610,7 +610,7 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         const int64_t slot = live[b] ? hash_slot(p.stage_keys + p.stage_off[st], p.stage_cap[st], (uint64_t)key[b],
-                                                 p.stats + 4) : 0;
+                                                 p.stats + STAT_HASH_FULL) : 0;
         live[b] = live[b] && slot >= 0;
         key[b] = live[b] ? slot * p.stage_mult[st] : 0;
       }
@@ -622,7 +622,7 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
   for (int b = 0; b < NB; ++b) {
     idx[b] = key[b];
     if (MODE == MODE_HASH && live[b]) {
-      idx[b] = hash_slot(p.hash_keys, G, (uint64_t)key[b], p.stats + 4);
+      idx[b] = hash_slot(p.hash_keys, G, (uint64_t)key[b], p.stats + STAT_HASH_FULL);
       live[b] = idx[b] >= 0;
     }
   }

@@ -70,9 +70,9 @@ struct ResultPool {
 
 struct pgpu_result_s;
 namespace pgpu {
-// Builds the columnar form of a result held in compact form (rt_exec.cpp); 0 or a PGPU_ERR_* status.
+// Builds the columnar form of a result held in compact form (rt_finalize.cpp); 0 or a PGPU_ERR_* status.
 int result_expand(pgpu_result_s* r);
-// Converts the RCONV_FX aggregations of a result in columnar form (rt_exec.cpp): the W digit sums of each group become
+// Converts the RCONV_FX aggregations of a result in columnar form (rt_finalize.cpp): the W digit sums of each group become
 // its one double, stored in the first digit's slot, and the aggregation reads as RCONV_F64 from then on.
 void result_resolve_fx(pgpu_result_s* r);
 }  // namespace pgpu

@@ -56,6 +56,28 @@ enum SlotKind : int32_t { SLOT_COUNT = 0, SLOT_SUM_I64 = 1, SLOT_SUM_F64 = 2, SL
                           SLOT_SUM_FX = 5 };
 enum Mode : int32_t { MODE_LDS = 0, MODE_GLOBAL = 1, MODE_HASH = 2 };
 
+// The statistics block of one execution (KParams.stats / KStarParams.stats): kStatsWords u64, zeroed by the prologue,
+// added to by the kernels and read back by finalize (ExecStats, rt.h).  Right after the group table when the table is
+// the plan's own, so that finalize reads both with one copy.
+enum StatsWord : int {
+  STAT_MATCHED = 0,         // docs matched: the scans, K8a, K6
+  STAT_STAR_ENTRIES = 1,    // entries scanned in filter by K6's residual predicates
+  STAT_SCAN_ENTRIES = 2,    // entries scanned in filter of STATS_CHAIN / LEAP2 segments: the scans, leap2_compose
+  STAT_STAR_DOCS_READ = 3,  // star-tree documents read by K6 (positions of the emitted ranges)
+  STAT_HASH_FULL = 4,       // a probe found no free slot (hash_slot): the table was sized below the plan's groups
+  STAT_TIMED_OUT = 5,       // a kernel saw the deadline pass (flag_timeout); the table is partial
+  // PGPU_TILE_CLAIMS builds only (an A/B): four u32 claim counters, launches 0-3 of a plan, in this word and the
+  // next.  Known alias: the counters of launches 2 and 3 are STAT_STAR_SECTORS' bytes, so in that build a plan with
+  // three or more claimed launches and star-tree segments corrupts both.  The default build leaves this word zero.
+  STAT_TILE_CLAIMS = 6,
+  STAT_STAR_SECTORS = 7,    // 64-byte sectors of pre-aggregated metrics K6 read (star_metric_bytes)
+};
+constexpr int kStatsWords = 8;
+constexpr int kStatsBytes = kStatsWords * 8;
+// what finalize copies back where STAT_STAR_SECTORS is not wanted: the words up to STAT_TIMED_OUT
+constexpr int kStatsReadWords = STAT_TIMED_OUT + 1;
+constexpr int kStatsReadBytes = kStatsReadWords * 8;
+
 // One predicate leaf evaluated against one segment: dictId in [lo, lo + span) (RANGE), bit set in `set`
 // (SET), docId in [lo, lo + span) (DOCRANGE), constant (ALL / NONE); `negate` flips the result (NOT_EQ / NOT_IN).
 struct KLeaf {
@@ -155,12 +177,12 @@ struct KParams {
   int64_t stage_off[kMaxKeys];
   int64_t stage_mult[kMaxKeys];
   unsigned long long* stage_keys;
-  unsigned long long* stats;      // [0] docs matched, [2] entries scanned in filter (STATS_CHAIN / LEAP2 segments)
+  unsigned long long* stats;      // the execution's statistics block (StatsWord)
   // STATS_LEAP2 segments: per (tile, wave) one byte of AndDocIdIterator state over scans A, B: bit 0 = a doc
   // matches, bit 1 = scanner after the wave's docs (1 = B), bits 2-3 = entry difference at its first match + 1
   uint8_t* leap_maps;
   // QueryContext.getEndTimeMs as a wall_clock64() reading of this device (0 = no deadline): past it the persistent
-  // scans stop taking tiles and set stats[5] (BaseCombineOperator.java:79-132 / GroupByCombineOperator.java:193-203
+  // scans stop taking tiles and set stats[STAT_TIMED_OUT] (BaseCombineOperator.java:79-132 / GroupByCombineOperator.java:193-203
   // give up at the same point; the host then reports the timeout instead of a partial result)
   uint64_t deadline;
   // diagnostics build only (PGPU_DIAG_WG_TIMES, PGPU_TRACE=wgtimes): per workgroup {start, tile loop end, end, tiles | first tile << 32, HW_ID, XCC_ID, 0, 0}
@@ -241,8 +263,7 @@ struct KStarParams {
   uint64_t* table;                        // MODE_GLOBAL / MODE_HASH
   uint64_t* slab;                         // MODE_LDS: this kernel's first slab
   unsigned long long* hash_keys;
-  unsigned long long* stats;              // [0] docs matched, [1] entries scanned in filter, [3] star-tree
-                                          // documents read (positions of the emitted ranges), [5] timed out
+  unsigned long long* stats;              // as KParams.stats (StatsWord)
   uint64_t deadline;                      // as KParams.deadline
   KFxSplit fx;                            // SLOT_SUM_FX slots (the FX instance alone reads it)
 };
@@ -387,7 +408,7 @@ int launch_hash_unpack(uint64_t* table, const unsigned long long* hash_keys, int
                        int32_t shift, void* stream);
 int launch_table_init(uint64_t* table, const int32_t* slot_kind, int32_t num_slots, int64_t num_keys,
                       unsigned long long* hash_keys, void* stream);
-// Also the deadline gate of the scan launch that follows it: sets stats[5] when `deadline` (wall_clock64 ticks,
+// Also the deadline gate of the scan launch that follows it: sets stats[STAT_TIMED_OUT] when `deadline` (wall_clock64 ticks,
 // 0 = none) has passed.
 int launch_expand_tiles(const uint8_t* segs, int32_t seg_stride, int32_t num_segs, int32_t* tile_seg,
                         uint64_t deadline, unsigned long long* stats, void* stream);
@@ -464,13 +485,11 @@ int launch_part_hash_aggregate_fx(const KPartParamsFx& pp, size_t lds_bytes, voi
 int launch_exclusive_scan_u32(uint32_t* data, int32_t n, void* stream);
 int launch_filter_bitmap(const KParams& p, uint32_t* out_words, void* stream);
 // Per STATS_LEAP2 record of a launch: composes its (tile, wave) maps in doc order into the segment's count
-// (stats[2] += ...).
-// reduce_slabs + leap2_compose of a one-launch plan as one launch; host_out (pinned, num_slots x num_keys + 6 words;
-// null = none): the table and the statistics words copied there by the last block (done: a zeroed u32 counter).
+// (stats[STAT_SCAN_ENTRIES] += ...).
+// reduce_slabs + leap2_compose of a one-launch plan as one launch.
 int launch_epilogue(const uint64_t* slab, const int32_t* slot_kind, int32_t num_slots, int64_t num_keys,
                     int32_t num_blocks, uint64_t* out, const uint8_t* segs, int32_t seg_stride, int32_t num_segs,
-                    const uint8_t* maps, unsigned long long* stats, uint64_t* host_out, unsigned int* done,
-                    void* stream);
+                    const uint8_t* maps, unsigned long long* stats, void* stream);
 int launch_leap2_compose(const uint8_t* segs, int32_t seg_stride, int32_t num_segs, const uint8_t* maps,
                          unsigned long long* stats, void* stream);
 int launch_leaf_masks(const KParams& p, const KMaskJob* jobs, int32_t num_jobs, uint32_t* out, void* stream);

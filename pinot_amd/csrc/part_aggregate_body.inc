@@ -4,7 +4,7 @@
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   const KParams& p = pp.base;
   const int tid = threadIdx.x;
-  if (p.deadline && p.stats[5]) return;
+  if (p.deadline && p.stats[STAT_TIMED_OUT]) return;
   const int PR = 1 << pp.pshift;
   const int ns = p.num_slots;
   // cs_pack: one word per key (LDS of PR words, part_aggregate_lds), COUNT + SUM from 0; else every slot's row

@@ -4,7 +4,7 @@
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   const KParams& p = pp.base;
   const int tid = threadIdx.x, lane = tid & 63;
-  if (p.deadline && p.stats[5]) return;
+  if (p.deadline && p.stats[STAT_TIMED_OUT]) return;
   const int S = 1 << pp.sbits;
   const int ns = p.num_slots, nst = pp.num_streams;
   uint32_t* keys = reinterpret_cast<uint32_t*>(lds + (size_t)ns * S);

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(kBlock, PGPU_PART_PASS_MIN_WAVES) void part_pass_ke
   // Deadline: the flag expand_tiles_kernel set when the query's end time had passed before this launch.  Every
   // pass reads it at its start and it cannot change while they run, so K8c scatters exactly the docs K8a counted
   // (its cursors run inside K8a's reservations) or nothing, like K8e / K8d.
-  if (p.deadline && p.stats[5]) return;
+  if (p.deadline && p.stats[STAT_TIMED_OUT]) return;
   if (SCATTER) {
     for (int c = tid; c < pp.num_coarse; c += kBlock)
       hist[c] = pp.part_start[c << pp.cshift] + pp.block_off[(int64_t)blockIdx.x * pp.num_coarse + c];
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(kBlock, PGPU_PART_PASS_MIN_WAVES) void part_pass_ke
   }
   if (!SCATTER) {
     {
-      const int idx[1] = {0};
+      const int idx[1] = {STAT_MATCHED};
       unsigned long long v[1] = {matched};
       block_stats_add<1>(p.stats, idx, v);
     }
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(kBlock, PGPU_PART_PASS_MIN_WAVES) void part_pass_ke
 __global__ __launch_bounds__(kBlock) void part_split_kernel(const KPartParams pp) {
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   const int tid = threadIdx.x;
-  if (pp.base.deadline && pp.base.stats[5]) return;  // K8a timed out: its counts cover only part of the docs
+  if (pp.base.deadline && pp.base.stats[STAT_TIMED_OUT]) return;  // K8a timed out: its counts cover only part of the docs
   const int c = blockIdx.x / pp.chunks_per_coarse, j = blockIdx.x % pp.chunks_per_coarse;
   const int p0 = c << pp.cshift, p1 = min(pp.num_parts, (c + 1) << pp.cshift), np = p1 - p0;
   const int NP = 1 << pp.cshift;
@@ -543,7 +543,7 @@ template <bool HASHED>
 __global__ __launch_bounds__(kBlock) void part_split_words_kernel(const KPartParams pp) {
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   const int tid = threadIdx.x;
-  if (pp.base.deadline && pp.base.stats[5]) return;
+  if (pp.base.deadline && pp.base.stats[STAT_TIMED_OUT]) return;
   const int c = blockIdx.x / pp.chunks_per_coarse, j = blockIdx.x % pp.chunks_per_coarse;
   const int p0 = c << pp.cshift, p1 = min(pp.num_parts, (c + 1) << pp.cshift);
   const int NP = 1 << pp.cshift;

@@ -1,8 +1,8 @@
 // rt.h -- the host runtime's model (tables, pinned segments, dictionaries, plans, scratch) and the functions
 // its sources share: rt_core.cpp (errors, diagnostics), rt_dict.cpp (dictionaries), rt_plan.cpp (predicates,
-// planning helpers), rt_plan_create.cpp (plan_create_impl's phases), rt_exec.cpp (execution, finalize),
-// rt_groups.cpp (numGroupsLimit split, plan cache) and the C ABI in abi_table.cpp / abi_plan.cpp / abi_combine.cpp /
-// abi_result.cpp.  Not part of the ABI.
+// planning helpers), rt_plan_create.cpp (plan_create_impl's phases), rt_exec.cpp (execution), rt_finalize.cpp
+// (finalize), rt_groups.cpp (numGroupsLimit split, plan cache) and the C ABI in abi_table.cpp / abi_plan.cpp /
+// abi_combine.cpp / abi_result.cpp.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -255,7 +255,6 @@ constexpr int64_t kHostCompactBytes = 512 * 1024;  // dense tables up to this si
 // finalize of a query without a deadline waits at most this long for them (then aborts the communicator), instead of
 // the communicator's whole timeout.
 constexpr int64_t kDenseCombineWaitMs = 30 * 1000;
-constexpr int64_t kExportBytes = 64 * 1024;  // LDS-table plans up to this size: the epilogue writes them to host memory
 constexpr int64_t kPartMinBytes = 32ll << 20;        // dense tables this large use the partitioned group-by
 #ifndef PGPU_PART_LDS_KB
 #define PGPU_PART_LDS_KB 64
@@ -483,9 +482,6 @@ struct Scratch {
   // receives finalize's copies.  Separate buffers, because a finalize that had to grow the upload buffer would
   // free it while its uploads may still be queued behind other queries' work on a shared stream.
   HostPinned stage, readback, starstage, bitstage, maskstage;
-  // small LDS-table plans: the epilogue's copy of table + statistics (pinned host) and its block counter
-  HostPinned exported;
-  DevBuf export_done;
   std::vector<uint8_t> starrec_sent;  // the star-tree records last uploaded to `starrec` (a repeat skips the copy)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<hipEvent_t> cev;  // per scan launch: (start, end)
@@ -500,8 +496,7 @@ struct Scratch {
     for (const DevBuf* b : {&docbits, &bittasks, &bitblocks, &rawtasks, &segrec, &sets, &slab, &table, &hash_keys,
                             &stats, &ckeys, &cslots, &counter, &bitmap, &tile_seg, &starrec, &starwork, &part_start,
                             &block_off, &rec_key, &rec_val, &rec_key32, &stage_keys, &coarse_fill, &fine_fill,
-                            &mid_key, &mid_val, &leap_maps, &mask_jobs, &leaf_masks, &hsort, &part_mm,
-                            &export_done})
+                            &mid_key, &mid_val, &leap_maps, &mask_jobs, &leaf_masks, &hsort, &part_mm})
       n += b->cap;
     return n;
   }
@@ -522,7 +517,6 @@ struct Scratch {
     coarse_fill.release(); fine_fill.release(); mid_key.release(); mid_val.release();
     leap_maps.release(); mask_jobs.release(); leaf_masks.release(); maskstage.release();
     xcursor.release(); xstage.release(); xsend.release(); xrecv.release(); xshard.release(); hsort.release(); part_mm.release();
-    exported.release(); export_done.release();
     for (auto& e : ev) if (e) { hipEventDestroy(e); e = nullptr; }
   }
 };
@@ -759,7 +753,6 @@ struct pgpu_plan_s {
   bool timed = false;  // PGPU_OPT_TIMING: the executions record their timing events
   bool inflight_counted = false;  // counted in table->scans_inflight (inflight_begin / inflight_end)
   bool alone = false;             // no other execution of the table was in flight when this one launched
-  bool exported = false;          // the last execution's epilogue copied table + statistics to scratch->exported
   bool comm_dense = false;        // combined element-wise (ALL_REDUCE / REDUCE_SCATTER): no host exchange of status
   bool k8d_counts = false;        // K8d wrote the compaction's chunk counts / ranges (KPartParams.chunk_cnt)
   const void* d_table_used = nullptr;
@@ -936,6 +929,26 @@ struct ExecCtx {
   double t_start = 0;
   int64_t slabs_used = 0;  // MODE_LDS: slabs written by the scan launches so far (launches pack them back to back)
 };
+
+// An execution's statistics block as finalize reads it back (StatsWord, internal.h).
+struct ExecStats {
+  uint64_t matched = 0;
+  uint64_t entries = 0;            // STAT_STAR_ENTRIES + STAT_SCAN_ENTRIES
+  int64_t star_docs_read = 0;
+  int64_t star_metric_bytes = -1;  // -1: STAT_STAR_SECTORS was not copied back
+  bool hash_full = false, timed_out = false;
+};
+// w: word 0 of the block's host copy; n: the words copied (kStatsReadWords or kStatsWords).
+inline ExecStats decode_stats(const uint64_t* w, int n) {
+  ExecStats s;
+  s.matched = w[STAT_MATCHED];
+  s.entries = w[STAT_STAR_ENTRIES] + w[STAT_SCAN_ENTRIES];
+  s.star_docs_read = (int64_t)w[STAT_STAR_DOCS_READ];
+  s.hash_full = w[STAT_HASH_FULL] != 0;
+  s.timed_out = w[STAT_TIMED_OUT] != 0;
+  if (n > STAT_STAR_SECTORS) s.star_metric_bytes = (int64_t)w[STAT_STAR_SECTORS] * 64;
+  return s;
+}
 
 // numEntriesScannedInFilter method of a segment whose leaves have the Pinot operator kinds `sig` (base-5 digits,
 // predicate 0 first; filter_stats.h): the folded tree, and the scan-kernel record bits of CHAIN / LEAP2.

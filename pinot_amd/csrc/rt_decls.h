@@ -82,31 +82,22 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
                      const StreamExec* se = nullptr);
 
 // rt_exec.cpp
-double epoch_us();
-int deadline_ticks(pgpu_table_s* t, int64_t end_ms, uint64_t* out);
 int timeout_fail(const pgpu_plan_s* P);
 int abandon_scratch(Scratch* sc, hipStream_t stream);
-int cancel_fail();
 bool cancelled(const pgpu_plan_s* P);
 int wait_plan(pgpu_plan_s* P, hipStream_t stream);
 int launch_raw_leaves(const pgpu_plan_s* P, Scratch* sc, hipStream_t stream);
-void dense_lds_forms(const pgpu_plan_s* P, int32_t* pack_slot, uint32_t* narrow);
 int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chunks, ExecCtx& X);
 int exec_upload_chunk(pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, const LaunchChunk& C);
 bool check_launch_on();
-int check_launch_inputs(const pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, const LaunchChunk& C);
 int scan_variant(const pgpu_plan_s* P);
-extern unsigned long long* g_diag_times;
-int diag_wg_times_begin(KParams& kp, int grid, hipStream_t stream);
-int diag_wg_times_report(pgpu_table_s* t, const KParams& kp, int grid, hipStream_t stream);
-void set_tile_claims(KParams& kp, unsigned long long* d_stats, int grid, int launch);
 bool set_slot_weights(KParams& kp, int grid, int num_cus, double step, int64_t max_run);
-void inflight_begin(pgpu_plan_s* P);
 void inflight_end(pgpu_plan_s* P);
 int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const LaunchChunk& C, int c);
 int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X);
 int plan_execute_impl(pgpu_plan_s* P, hipStream_t stream, void* d_table);
-void decode_keys(const pgpu_plan_s* P, pgpu_result_s* R, int64_t row, uint64_t key);
+
+// rt_finalize.cpp (result_expand and result_resolve_fx: host_result.h)
 int plan_finalize_impl(pgpu_plan_s* P, hipStream_t stream, const void* d_table, int64_t key_begin, int64_t key_count,
                        pgpu_result_s* R);
 

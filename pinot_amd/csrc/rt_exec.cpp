@@ -1,18 +1,18 @@
-// rt_exec.cpp -- query execution (launches) and finalize (rt.h).
+// rt_exec.cpp -- query execution: the wait, and the launches in phases (rt.h).  Finalize is rt_finalize.cpp.
 #include "rt_decls.h"
 
 namespace pgpu {
 // ---- query deadlines (BaseCombineOperator.java:79-132: the combine waits until QueryContext.getEndTimeMs and then
 // returns a timeout block; GroupByCombineOperator.java:193-203 for group-by).  The persistent scans compare the
 // device wall clock against the deadline converted to clock ticks and stop taking tiles past it.
-double epoch_us() {
+static double epoch_us() {
   return (double)std::chrono::duration_cast<std::chrono::microseconds>(
              std::chrono::system_clock::now().time_since_epoch()).count();
 }
 
 // Device clock ticks at host epoch time end_ms, never earlier than the true reading (the calibration pairs a clock
 // value with a host time taken before the kernel that read it, so queueing delay only makes deadlines later).
-int deadline_ticks(pgpu_table_s* t, int64_t end_ms, uint64_t* out) {
+static int deadline_ticks(pgpu_table_s* t, int64_t end_ms, uint64_t* out) {
   std::lock_guard<std::mutex> g(t->clock_mu);
   if (!t->clock_stream) {
     int khz = 0;
@@ -67,14 +67,14 @@ int abandon_scratch(Scratch* sc, hipStream_t stream) {
 // _blockingQueue.poll(endTimeMs - now) / _operatorLatch.await(timeoutMs) do (BaseCombineOperator.java:193-203,
 // GroupByCombineOperator.java:193-203): the query returns PGPU_ERR_TIMEOUT at its deadline and the device work
 // left running keeps its scratch out of the pool until it completes.
-int cancel_fail() {
+static int cancel_fail() {
   return fail(PGPU_ERR_CANCELLED, "QueryException 503 (QUERY_CANCELLATION_ERROR): Query was cancelled");
 }
 
 bool cancelled(const pgpu_plan_s* P) { return __atomic_load_n(&P->cancel, __ATOMIC_ACQUIRE) != 0; }
 
 // table->scans_inflight: counted from the execution's launch until its completion is seen or the plan is destroyed
-void inflight_begin(pgpu_plan_s* P) {
+static void inflight_begin(pgpu_plan_s* P) {
   if (P->inflight_counted) {
     P->alone = P->table->scans_inflight.load(std::memory_order_relaxed) == 1;
     return;
@@ -168,7 +168,7 @@ int launch_raw_leaves(const pgpu_plan_s* P, Scratch* sc, hipStream_t stream) {
 // KParams.pack_slot (planned with the LDS table's rows, lds_pack_slot) and narrow of a dense LDS plan, from the value
 // ranges of its integer columns in every segment (sorted dictionaries: first and last entries; raw columns: their
 // decoded range).  PGPU_NO_DENSE_NARROW=1: no 32-bit min / max (A/B).
-void dense_lds_forms(const pgpu_plan_s* P, int32_t* pack_slot, uint32_t* narrow) {
+static void dense_lds_forms(const pgpu_plan_s* P, int32_t* pack_slot, uint32_t* narrow) {
   *pack_slot = P->mode == MODE_LDS || P->mode == MODE_HASH ? P->pack_slot : -1;  // planned with the table layout
   *narrow = 0;
   if (!P->dense || P->mode != MODE_LDS || P->num_keys <= 1 || !P->star.empty() || P->grid <= 0) return;
@@ -189,15 +189,18 @@ void dense_lds_forms(const pgpu_plan_s* P, int32_t* pack_slot, uint32_t* narrow)
   }
 }
 
-int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chunks, ExecCtx& X) {
+// ---- the prologue's phases, in stream order
+// The checks that launch nothing (cancelled, past the end time), the deadline in device ticks (0: none), and the
+// plan's per-execution state.
+static int exec_begin(pgpu_plan_s* P, ExecCtx& X, uint64_t* deadline) {
   inflight_begin(P);
   X.t_start = trace_on() ? now_us() : 0;
   if (cancelled(P)) return cancel_fail();  // nothing is launched for a cancelled query
-  uint64_t deadline = 0;
+  *deadline = 0;
   if (P->end_time_ms > 0) {  // past the end time already: nothing is launched
     P->exec_start_ms = (int64_t)(epoch_us() / 1000.0);
     if (P->exec_start_ms >= P->end_time_ms) return timeout_fail(P);
-    TRY(deadline_ticks(P->table, P->end_time_ms, &deadline));
+    TRY(deadline_ticks(P->table, P->end_time_ms, deadline));
   }
   // the state a previous execution's combine left (pgpu_plan_combine): planned slot kinds, no shard, no merged table
   if (!P->slot_kind_planned.empty()) {
@@ -210,10 +213,13 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
   P->comm_dense = false;
   P->k8d_counts = false;
   P->merged_records = -1;
-  Scratch* sc = P->scratch;
   X.nslots = (int)P->slot_kind.size();
-  const int nslots = X.nslots;
-  X.words = P->part_hash ? 0 : (int64_t)nslots * P->num_keys;  // hashed partitions: records, no table
+  X.words = P->part_hash ? 0 : (int64_t)X.nslots * P->num_keys;  // hashed partitions: records, no table
+  return 0;
+}
+
+// The scratch's timing events: the four of an execution and a (start, end) pair per scan launch.
+static int exec_events(Scratch* sc, int max_chunks) {
   for (auto& e : sc->ev)
     if (!e) HIP_TRY(hipEventCreate(&e));
   if ((int)sc->cev.size() < 2 * max_chunks) {
@@ -221,19 +227,21 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
     sc->cev.resize(2 * max_chunks, nullptr);
     for (size_t i = old; i < sc->cev.size(); ++i) HIP_TRY(hipEventCreate(&sc->cev[i]));
   }
-  X.mark("events");
-  PGPU_TIMING_RECORD(P, sc->ev[0], stream);
-  X.mark("event 0 recorded");
+  return 0;
+}
+
+// The upload buffers and the statistics block (zeroed on the stream; P->d_stats).
+static int exec_buffers(pgpu_plan_s* P, hipStream_t stream, void* d_table, ExecCtx& X) {
+  Scratch* sc = P->scratch;
   TRY(sc->sets.ensure(std::max<size_t>(std::max<size_t>(P->set_words.size(), (size_t)P->set_words_bound) * 4, 16)));
   const size_t rec_cap = std::max<size_t>((size_t)P->segs.size() * P->seg_stride, P->segrec.size());
   TRY(sc->segrec.ensure(std::max<size_t>(rec_cap, 16)));
   TRY(sc->stage.ensure(std::max<size_t>(rec_cap + (size_t)std::max<int64_t>(P->set_words_bound,
                                                                              (int64_t)P->set_words.size()) * 4, 16)));
-  // Statistics words (docs matched, entries scanned, star-tree docs, timeout flag, star metric sectors): right after
-  // the group table when the table is internal, so finalize reads both with one copy.  (A ring of entries zeroed 256
-  // executions at a time, instead of this fill per query, was measured in r06 sessions i, j, m: no gain on C1 / C3,
-  // and C4's pipelined star-tree step lost 0.17 -> 0.21 ms with the second copy it needs; not kept.)
-  constexpr size_t kStatsBytes = 64;
+  // The statistics block (StatsWord, internal.h): right after the group table when the table is internal, so
+  // finalize reads both with one copy.  (A ring of entries zeroed 256 executions at a time, instead of this fill per
+  // query, was measured in r06 sessions i, j, m: no gain on C1 / C3, and C4's pipelined star-tree step lost
+  // 0.17 -> 0.21 ms with the second copy it needs; not kept.)
   unsigned long long* stats;
   if (!d_table) {
     TRY(sc->table.ensure((size_t)X.words * 8 + kStatsBytes));
@@ -244,9 +252,14 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
   }
   HIP_TRY(hipMemsetAsync(stats, 0, kStatsBytes, stream));
   P->d_stats = stats;
-  P->exported = false;
   X.external = d_table != nullptr;
-  X.mark("buffers");
+  return 0;
+}
+
+// Where the execution's records, bitsets and tile map live: the scratch, or the cached plan's device image (built
+// here once; later executions wait for it).
+static int exec_image(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
+  Scratch* sc = P->scratch;
   X.segrec = sc->segrec.as<uint8_t>();
   X.sets = sc->sets.as<uint32_t>();
   TRY(sc->tile_seg.ensure((size_t)std::max<int64_t>(std::max<int64_t>(P->num_tiles, P->tile_bound), 1) * 4));
@@ -275,7 +288,7 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
       const int32_t nrec = P->seg_stride > 0 ? (int32_t)(P->segrec.size() / P->seg_stride) : 0;
       if (nrec > 0 &&
           launch_expand_tiles(im.segrec.as<uint8_t>(), P->seg_stride, nrec, im.tile_seg.as<int32_t>(), 0,
-                              stats, stream))
+                              P->d_stats, stream))
         return fail(PGPU_ERR_DEVICE, "expand launch failed: %s", hipGetErrorString(hipGetLastError()));
       HIP_TRY(hipEventRecord(im.built, stream));
       im.uploaded = true;
@@ -287,7 +300,12 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
     X.sets = im.sets.as<uint32_t>();
     X.tile_seg = im.tile_seg.as<int32_t>();
   }
-  X.mark("image");
+  return 0;
+}
+
+// The filter's per-query docId bitmaps: inverted-index leaves and raw-value leaves.
+static int exec_filter_bitmaps(pgpu_plan_s* P, hipStream_t stream) {
+  Scratch* sc = P->scratch;
   if (P->docbit_words > 0) TRY(sc->docbits.ensure((size_t)P->docbit_words * 4));
   if (!P->bit_blocks.empty()) {  // BitmapBasedFilterOperator leaves: OR the matching dictIds' containers
     TRY(sc->bittasks.ensure(std::max<size_t>(P->bit_tasks.size(), 1) * sizeof(KBitTask)));
@@ -305,10 +323,12 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
       return fail(PGPU_ERR_DEVICE, "inverted-index materialise launch failed: %s",
                   hipGetErrorString(hipGetLastError()));
   }
-  TRY(launch_raw_leaves(P, sc, stream));  // raw-value leaves' docbits regions
-  uint64_t* table = d_table ? reinterpret_cast<uint64_t*>(d_table) : sc->table.as<uint64_t>();
-  X.table = table;
-  P->d_table_used = table;
+  return launch_raw_leaves(P, sc, stream);  // raw-value leaves' docbits regions
+}
+
+// X.kp: what every launch of the execution shares (no buffer but the statistics block; exec_tables adds the rest).
+static void fill_kparams(const pgpu_plan_s* P, uint64_t deadline, ExecCtx& X) {
+  const int nslots = X.nslots;
   KParams& kp = X.kp;
   memset(&kp, 0, sizeof kp);
   kp.pack_slot = -1;
@@ -347,7 +367,16 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
   kp.pair_leaves = 1;
   dense_lds_forms(P, &kp.pack_slot, &kp.narrow);
   kp.pack_shift = P->pack_shift;
-  kp.stats = stats;
+  kp.stats = P->d_stats;
+}
+
+// The accumulators: LEAP2 maps, the slabs of an LDS-table plan, or the global / hash table (initialised here) with
+// its key tables.
+static int exec_tables(pgpu_plan_s* P, hipStream_t stream, int max_chunks, ExecCtx& X) {
+  Scratch* sc = P->scratch;
+  KParams& kp = X.kp;
+  const int nslots = X.nslots;
+  uint64_t* table = X.table;
   if (P->leap_reserved) {  // one byte per (tile, wave) of the plan, written by the scan kernel for LEAP2 segments
     TRY(sc->leap_maps.ensure((size_t)std::max<int64_t>(std::max<int64_t>(P->num_tiles, P->tile_bound), 1) *
                              (kBlock / 64)));
@@ -381,6 +410,26 @@ int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chu
       return fail(PGPU_ERR_DEVICE, "table init launch failed: %s", hipGetErrorString(hipGetLastError()));
     kp.table = table;
   }
+  return 0;
+}
+
+int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chunks, ExecCtx& X) {
+  uint64_t deadline = 0;
+  TRY(exec_begin(P, X, &deadline));
+  Scratch* sc = P->scratch;
+  TRY(exec_events(sc, max_chunks));
+  X.mark("events");
+  PGPU_TIMING_RECORD(P, sc->ev[0], stream);
+  X.mark("event 0 recorded");
+  TRY(exec_buffers(P, stream, d_table, X));
+  X.mark("buffers");
+  TRY(exec_image(P, stream, X));
+  X.mark("image");
+  TRY(exec_filter_bitmaps(P, stream));
+  X.table = d_table ? reinterpret_cast<uint64_t*>(d_table) : sc->table.as<uint64_t>();
+  P->d_table_used = X.table;
+  fill_kparams(P, deadline, X);
+  TRY(exec_tables(P, stream, max_chunks, X));
   P->launches_done = 0;
   return 0;
 }
@@ -414,8 +463,6 @@ int exec_upload_chunk(pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, cons
   return 0;
 }
 
-// Launches the scan of chunk c (records already uploaded): tile map of its records, then the scan kernel (or the
-// partitioned group-by) over its tiles into slab region c.
 // PGPU_TRACE=check (diagnostics): before a scan launch, the records and tile map the kernel will read are copied
 // back and compared with the plan's host records (pointer fields patched at upload skipped); a mismatch fails the
 // query (PGPU_ERR_DEVICE) instead of launching on them.
@@ -423,7 +470,7 @@ bool check_launch_on() {
   static const bool on = diag("check");
   return on;
 }
-int check_launch_inputs(const pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, const LaunchChunk& C) {
+static int check_launch_inputs(const pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, const LaunchChunk& C) {
   HIP_TRY(hipStreamSynchronize(stream));
   const size_t r0 = (size_t)C.rec_begin * P->seg_stride, rn = (size_t)C.num_recs * P->seg_stride;
   std::vector<uint8_t> dev(rn);
@@ -476,8 +523,8 @@ int scan_variant(const pgpu_plan_s* P) {
 // PGPU_TRACE=wgtimes with a PGPU_DIAG_WG_TIMES build: every scan launch is synchronised and its workgroups' start /
 // tile-loop end / end times (wall clock, relative to the earliest start) summarised on stderr -- how much of a launch
 // is its ramp, its tail and the imbalance of the static tile split.
-unsigned long long* g_diag_times = nullptr;
-int diag_wg_times_begin(KParams& kp, int grid, hipStream_t stream) {
+static unsigned long long* g_diag_times = nullptr;
+static int diag_wg_times_begin(KParams& kp, int grid, hipStream_t stream) {
   constexpr int kMaxWgs = 1 << 16;
   if (grid > kMaxWgs) return 0;
   if (!g_diag_times) HIP_TRY(hipMalloc(&g_diag_times, (size_t)kMaxWgs * 64));
@@ -486,7 +533,7 @@ int diag_wg_times_begin(KParams& kp, int grid, hipStream_t stream) {
   return 0;
 }
 
-int diag_wg_times_report(pgpu_table_s* t, const KParams& kp, int grid, hipStream_t stream) {
+static int diag_wg_times_report(pgpu_table_s* t, const KParams& kp, int grid, hipStream_t stream) {
   if (!kp.diag_times) return 0;
   std::vector<unsigned long long> h((size_t)grid * 8);
   HIP_TRY(hipMemcpyAsync(h.data(), kp.diag_times, h.size() * 8, hipMemcpyDeviceToHost, stream));
@@ -529,7 +576,8 @@ int diag_wg_times_report(pgpu_table_s* t, const KParams& kp, int grid, hipStream
 
 // Run-time claims of a chunked scan launch (KParams.claim; library builds with -DPGPU_TILE_CLAIMS only): the static
 // runs cover the first PGPU_CLAIM_STATIC_PM / 1000 of the tiles and the rest is claimed in runs of 1/PGPU_CLAIM_DIV
-// of a workgroup's share.  The counters are u32 words 12..15 of the statistics block (zeroed per execution): launches
+// of a workgroup's share.  The counters are the four u32 at STAT_TILE_CLAIMS of the statistics block (zeroed per
+// execution; they alias STAT_STAR_SECTORS, see internal.h): launches
 // 0-3 of a plan.  Measured on MI355X and not the default (r06 session b, profiles/r06_ab_summary.txt): C3's scan
 // 729 -> 711 us at 1000 segments but its pipelined step 0.687 -> 0.719 ms, and at 125 segments 119 -> 145 us (every
 // claimed tile reloads its segment's records behind a workgroup barrier).
@@ -556,17 +604,203 @@ bool set_slot_weights(KParams& kp, int grid, int num_cus, double step, int64_t m
   return !declined;
 }
 
-void set_tile_claims(KParams& kp, unsigned long long* d_stats, int grid, int launch) {
+static void set_tile_claims(KParams& kp, unsigned long long* d_stats, int grid, int launch) {
   kp.claim = nullptr;
 #ifdef PGPU_TILE_CLAIMS
   const int64_t share = (int64_t)kp.num_tiles / std::max(grid, 1);
   if (!kp.tile_chunks || grid < 64 || (grid & 7) || launch >= 4 || share < 8) return;
-  kp.claim = reinterpret_cast<unsigned int*>(d_stats + 6) + launch;
+  kp.claim = reinterpret_cast<unsigned int*>(d_stats + STAT_TILE_CLAIMS) + launch;
   kp.claim_base = (int32_t)((int64_t)kp.num_tiles * PGPU_CLAIM_STATIC_PM / 1000);
   kp.claim_tiles = (int32_t)std::max<int64_t>(1, share / PGPU_CLAIM_DIV);
 #endif
 }
 
+// ---- KPartParams of the partitioned pipeline (K8a count, scan, K8c scatter, K8d / K8h aggregate), filled in the
+// order its buffers are taken
+// The streams, the partition shape and the fill counters; cap: the records the chunk can produce.
+static int part_shape_buffers(const pgpu_plan_s* P, int nslots, int64_t cap, KPartParams& pp) {
+  Scratch* sc = P->scratch;
+  pp.pshift = P->part_shift;
+  pp.num_parts = P->num_parts;
+  pp.num_streams = (int)P->stream_col.size();
+  for (size_t j = 0; j < P->stream_col.size(); ++j) { pp.stream_col[j] = P->stream_col[j]; pp.stream_f64[j] = P->stream_f64[j]; }
+  for (int sl = 0; sl < nslots; ++sl) pp.slot_stream[sl] = P->slot_stream[sl];
+  TRY(sc->part_start.ensure((size_t)(P->num_parts + 1) * 4));
+  const int cshift = part_coarse_shift(P->num_parts);
+  pp.cshift = cshift;
+  pp.num_coarse = part_coarse_runs(P->num_parts);
+  pp.chunks_per_coarse = std::max(1, 1024 / pp.num_coarse);
+  {  // K8e batch: as many records as fit 96 KB of LDS beside the per-partition counters, a multiple of kBlock
+    const int kb = P->part_hash ? 4 : 2;  // staged key bytes
+    const int64_t fixed = (int64_t)part_split_lds(cshift, pp.num_streams, 0, kb);
+    const int64_t b = (96 * 1024 - fixed) / (8 * pp.num_streams + 4 + kb) / kBlock * kBlock;
+    pp.split_batch = (int)std::max<int64_t>(kBlock, std::min<int64_t>(kSplitBatch, b));
+  }
+  TRY(sc->coarse_fill.ensure((size_t)pp.num_coarse * 4));
+  TRY(sc->fine_fill.ensure((size_t)P->num_parts * 4));
+  if (cshift > 0) {
+    TRY(sc->mid_key.ensure((size_t)cap * 4));
+    TRY(sc->mid_val.ensure(std::max<size_t>((size_t)cap * 8 * pp.num_streams, 8)));
+    pp.mid_key = sc->mid_key.as<uint32_t>();
+    pp.mid_val = sc->mid_val.as<uint64_t>();
+  }
+  pp.coarse_fill = sc->coarse_fill.as<uint32_t>();
+  pp.fine_fill = sc->fine_fill.as<uint32_t>();
+  return 0;
+}
+
+// The record buffers; for hashed partitions also K8h's outputs: the groups' compacted records, where finalize's
+// compaction of a hash table would put them, their count and each partition's slot ranges.
+static int part_record_buffers(pgpu_plan_s* P, hipStream_t stream, int nslots, int64_t cap, KPartParams& pp) {
+  Scratch* sc = P->scratch;
+  if (P->part_hash) {
+    pp.hashed = 1;
+    pp.mid_pair = pp.cshift > 0 && pp.num_streams == 1 && P->part_val32 && !P->stream_f64[0] ? 1 : 0;
+    pp.pbits = P->part_pbits;
+    pp.sbits = P->part_sbits;
+    TRY(sc->rec_key32.ensure((size_t)cap * 4));
+    pp.rec_key32 = sc->rec_key32.as<uint32_t>();
+    const int64_t ocap = part_hash_out_cap(P);
+    TRY(sc->ckeys.ensure((size_t)ocap * 8 * (1 + nslots)));
+    TRY(sc->counter.ensure(64));
+    HIP_TRY(hipMemsetAsync(sc->counter.p, 0, 8, stream));
+    pp.out_rec = sc->ckeys.as<uint64_t>();
+    pp.out_count = sc->counter.as<unsigned long long>();
+    pp.out_cap = ocap;
+    TRY(sc->part_mm.ensure((size_t)P->num_parts * 2 * nslots * 8));
+    pp.out_mm = sc->part_mm.as<unsigned long long>();
+    P->part_hash_live = true;
+  } else {
+    TRY(sc->rec_key.ensure((size_t)cap * 2));
+  }
+  TRY(sc->rec_val.ensure(std::max<size_t>((size_t)cap * 8 * pp.num_streams, 8)));
+  pp.part_start = sc->part_start.as<uint32_t>();
+  pp.rec_key = sc->rec_key.as<uint16_t>();
+  pp.rec_val = sc->rec_val.as<uint64_t>();
+  pp.rec_cap = cap;
+  pp.val32 = P->part_val32 ? 1 : 0;
+  return 0;
+}
+
+// One-word records, where the operand's range leaves room for it beside the key bits: (value - pack_min) packed above
+// the partition bits of a hashed record's hk, or into the free bits of a dense record's key.  cs_pack: the
+// aggregating kernel's COUNT + SUM_I64 form of such records.
+static void part_record_packing(const pgpu_plan_s* P, int nslots, KPartParams& pp) {
+  if (P->part_pack_range < 0) return;
+  const bool count_sum = nslots == 2 && P->slot_kind[0] == SLOT_COUNT && P->slot_kind[1] == SLOT_SUM_I64 &&
+                         P->slot_stream[1] == 0;
+  if (P->part_hash && pp.num_streams == 1 && pp.val32 && P->part_pbits >= 1) {
+    int vb = 0;
+    while (vb < 32 && (P->part_pack_range >> vb) != 0) ++vb;
+    if (vb <= P->part_pbits) {
+      pp.fine_pack = 1;
+      pp.pack_min = P->part_pack_min;
+      pp.pack_range = P->part_pack_range;
+      pp.cs_pack = count_sum ? 1 : 0;
+    }
+  } else if (!P->part_hash && pp.cshift > 0) {
+    const int free_bits = 32 - (pp.pshift + pp.cshift);
+    int vb = 0;
+    while (vb < free_bits && (P->part_pack_range >> vb) != 0) ++vb;
+    if ((P->part_pack_range >> vb) == 0) {
+      pp.pack_bits = std::max(vb, 1);
+      pp.pack_min = P->part_pack_min;
+      pp.fine_pack = pp.pshift + pp.pack_bits <= 32 && pp.num_streams == 1 ? 1 : 0;
+      pp.cs_pack = pp.fine_pack && count_sum ? 1 : 0;
+      pp.pack_range = P->part_pack_range;
+    }
+  }
+}
+
+// pp.staged and the grid of the record passes.
+static int part_staged_grid(pgpu_plan_s* P, KPartParams& pp) {
+  int grid = P->part_grid;
+#ifndef PGPU_PART_NO_STAGE  // (defined only by an A/B build of the library: every record stored from its lane)
+  // one-word records with <= 64 coarse runs: K8c stages each wave's records by run in LDS and stores them in runs;
+  // the grid (K8a's too) follows that instance's occupancy
+  pp.staged = pp.cshift > 0 && pp.num_coarse <= 64 ? (pp.pack_bits > 0 ? 1 : pp.mid_pair ? 2 : 0) : 0;
+  if (pp.staged) {
+    if (P->part_grid_staged[pp.staged - 1] <= 0) {
+      const int per_cu =
+          std::max(1, std::min(occupancy_part_pass(P->part_lds, P->num_parts, pp.num_coarse, pp.staged), 4));
+      P->part_grid_staged[pp.staged - 1] =
+          (int)std::max<int64_t>(1, std::min<int64_t>(P->num_tiles, (int64_t)P->table->num_cus * per_cu));
+    }
+    grid = P->part_grid_staged[pp.staged - 1];
+  }
+#endif
+  return grid;
+}
+
+// K8d's partitions are the ordered compaction's chunks (C5): K8d writes their counts and ranges, and finalize skips
+// compact_count_kernel's pass over the table (P->k8d_counts).
+static int part_k8d_counts(pgpu_plan_s* P, int nslots, KPartParams& pp) {
+  Scratch* sc = P->scratch;
+  const int64_t G = P->num_keys, nch = compact_ordered_chunks(G);
+  if (pp.cs_pack && !P->hash && ((int64_t)1 << pp.pshift) == kCompactChunkKeys && nch == P->num_parts &&
+      (int64_t)nslots * G * 8 > kHostCompactBytes) {
+    TRY(sc->cslots.ensure(compact_scratch_bytes(G, nslots)));
+    pp.chunk_cnt = sc->cslots.as<uint32_t>();
+    pp.chunk_mm = reinterpret_cast<long long*>(sc->cslots.as<uint8_t>() + ((nch * 4 + 7) & ~int64_t(7)));
+    P->k8d_counts = true;
+  }
+  return 0;
+}
+
+static int launch_partitioned_chunk(pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, const KParams& kp) {
+  Scratch* sc = P->scratch;
+  const int nslots = X.nslots;
+  const int64_t cap = std::max<int64_t>(P->total_docs, 1);
+  KPartParams pp;
+  memset(&pp, 0, sizeof pp);
+  pp.base = kp;
+  TRY(part_shape_buffers(P, nslots, cap, pp));
+  TRY(part_record_buffers(P, stream, nslots, cap, pp));
+  part_record_packing(P, nslots, pp);
+  const int grid = part_staged_grid(P, pp);
+  TRY(sc->block_off.ensure((size_t)grid * pp.num_coarse * 4));
+  pp.block_off = sc->block_off.as<uint32_t>();
+  TRY(part_k8d_counts(P, nslots, pp));
+  const KFxSplit fxs = fx_split(P);  // (plans with SLOT_SUM_FX slots: K8d / K8h split the records' doubles)
+  if (launch_partitioned(pp, grid, P->part_lds, stream, P->fx ? &fxs : nullptr))
+    return fail(PGPU_ERR_DEVICE, "partitioned group-by launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+// The direct scan of a chunk's tiles: claims and slot weights, what the launch looked like (P->last_scan), the
+// plan's scan instance.
+static int launch_scan_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, KParams& kp, int grid, int c) {
+  static const bool wg_times = diag("wgtimes");
+  if (wg_times) TRY(diag_wg_times_begin(kp, grid, stream));
+  set_tile_claims(kp, P->d_stats, grid, c);
+  bool fits = true;
+  if (P->alone)
+    fits = set_slot_weights(kp, grid, P->table->num_cus, P->cfg.slot_weight_step,
+                            P->leap_reserved ? P->leap_tiles : kLeapLdsTiles);
+  P->last_scan.tiles = kp.num_tiles;
+  P->last_scan.grid = grid;
+  P->last_scan.tile_chunks = kp.tile_chunks;
+  P->last_scan.slot_n = kp.slot_n;
+  for (int s = 0; s < kMaxCuSlots; ++s) P->last_scan.slot_w[s] = kp.slot_n ? kp.slot_w[s] : 0;
+  P->last_scan.alone = P->alone;
+  P->last_scan.declined = !fits;
+  int rc;
+  if (P->fx) {  // the FX instances: the launch's parameters and the split of the fixed-point slots
+    KParamsFx kf;
+    static_cast<KParams&>(kf) = kp;
+    kf.fx = fx_split(P);
+    rc = launch_filter_groupby_fx(kf, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
+  } else {
+    rc = launch_filter_groupby(kp, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
+  }
+  if (rc) return fail(PGPU_ERR_DEVICE, "scan launch failed: %s", hipGetErrorString(hipGetLastError()));
+  X.mark("scan launched");
+  if (wg_times) TRY(diag_wg_times_report(P->table, kp, grid, stream));
+  return 0;
+}
+
+// Launches the scan of chunk c (records already uploaded): tile map of its records, then the scan kernel (or the
+// partitioned group-by) over its tiles into slab region c.
 int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const LaunchChunk& C, int c) {
   Scratch* sc = P->scratch;
   KParams kp = X.kp;
@@ -588,151 +822,8 @@ int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const Laun
   X.mark("chunk set up");
   if (c == 0) PGPU_TIMING_RECORD(P, sc->ev[1], stream);
   PGPU_TIMING_RECORD(P, sc->cev[2 * c], stream);
-  if (C.num_tiles > 0 && P->partitioned) {
-    const int nslots = X.nslots;
-    KPartParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.base = kp;
-    pp.pshift = P->part_shift;
-    pp.num_parts = P->num_parts;
-    pp.num_streams = (int)P->stream_col.size();
-    for (size_t j = 0; j < P->stream_col.size(); ++j) { pp.stream_col[j] = P->stream_col[j]; pp.stream_f64[j] = P->stream_f64[j]; }
-    for (int sl = 0; sl < nslots; ++sl) pp.slot_stream[sl] = P->slot_stream[sl];
-    const int64_t cap = std::max<int64_t>(P->total_docs, 1);
-    TRY(sc->part_start.ensure((size_t)(P->num_parts + 1) * 4));
-    const int cshift = part_coarse_shift(P->num_parts);
-    pp.cshift = cshift;
-    pp.num_coarse = part_coarse_runs(P->num_parts);
-    pp.chunks_per_coarse = std::max(1, 1024 / pp.num_coarse);
-    {  // K8e batch: as many records as fit 96 KB of LDS beside the per-partition counters, a multiple of kBlock
-      const int kb = P->part_hash ? 4 : 2;  // staged key bytes
-      const int64_t fixed = (int64_t)part_split_lds(cshift, pp.num_streams, 0, kb);
-      const int64_t b = (96 * 1024 - fixed) / (8 * pp.num_streams + 4 + kb) / kBlock * kBlock;
-      pp.split_batch = (int)std::max<int64_t>(kBlock, std::min<int64_t>(kSplitBatch, b));
-    }
-    TRY(sc->coarse_fill.ensure((size_t)pp.num_coarse * 4));
-    TRY(sc->fine_fill.ensure((size_t)P->num_parts * 4));
-    if (cshift > 0) {
-      TRY(sc->mid_key.ensure((size_t)cap * 4));
-      TRY(sc->mid_val.ensure(std::max<size_t>((size_t)cap * 8 * pp.num_streams, 8)));
-      pp.mid_key = sc->mid_key.as<uint32_t>();
-      pp.mid_val = sc->mid_val.as<uint64_t>();
-    }
-    pp.coarse_fill = sc->coarse_fill.as<uint32_t>();
-    pp.fine_fill = sc->fine_fill.as<uint32_t>();
-    if (P->part_hash) {
-      pp.hashed = 1;
-      pp.mid_pair = cshift > 0 && pp.num_streams == 1 && P->part_val32 && !P->stream_f64[0] ? 1 : 0;
-      pp.pbits = P->part_pbits;
-      pp.sbits = P->part_sbits;
-      TRY(sc->rec_key32.ensure((size_t)cap * 4));
-      pp.rec_key32 = sc->rec_key32.as<uint32_t>();
-      // the groups' compacted records, where finalize's compaction of a hash table would put them
-      const int64_t ocap = part_hash_out_cap(P);
-      TRY(sc->ckeys.ensure((size_t)ocap * 8 * (1 + nslots)));
-      TRY(sc->counter.ensure(64));
-      HIP_TRY(hipMemsetAsync(sc->counter.p, 0, 8, stream));
-      pp.out_rec = sc->ckeys.as<uint64_t>();
-      pp.out_count = sc->counter.as<unsigned long long>();
-      pp.out_cap = ocap;
-      TRY(sc->part_mm.ensure((size_t)P->num_parts * 2 * nslots * 8));
-      pp.out_mm = sc->part_mm.as<unsigned long long>();
-      P->part_hash_live = true;
-    } else {
-      TRY(sc->rec_key.ensure((size_t)cap * 2));
-    }
-    TRY(sc->rec_val.ensure(std::max<size_t>((size_t)cap * 8 * pp.num_streams, 8)));
-    pp.part_start = sc->part_start.as<uint32_t>();
-    pp.rec_key = sc->rec_key.as<uint16_t>();
-    pp.rec_val = sc->rec_val.as<uint64_t>();
-    pp.rec_cap = cap;
-    pp.val32 = P->part_val32 ? 1 : 0;
-    if (P->part_hash && P->part_pack_range >= 0 && pp.num_streams == 1 && pp.val32 && P->part_pbits >= 1) {
-      // hashed partitions: K8e's records packed as hk below the partition bits | (value - pack_min) above them
-      int vb = 0;
-      while (vb < 32 && (P->part_pack_range >> vb) != 0) ++vb;
-      if (vb <= P->part_pbits) {
-        pp.fine_pack = 1;
-        pp.pack_min = P->part_pack_min;
-        pp.pack_range = P->part_pack_range;
-        pp.cs_pack = nslots == 2 && P->slot_kind[0] == SLOT_COUNT && P->slot_kind[1] == SLOT_SUM_I64 &&
-                     P->slot_stream[1] == 0 ? 1 : 0;
-      }
-    } else if (!P->part_hash && cshift > 0 && P->part_pack_range >= 0) {
-      const int free_bits = 32 - (pp.pshift + cshift);
-      int vb = 0;
-      while (vb < free_bits && (P->part_pack_range >> vb) != 0) ++vb;
-      if ((P->part_pack_range >> vb) == 0) {
-        pp.pack_bits = std::max(vb, 1);
-        pp.pack_min = P->part_pack_min;
-        pp.fine_pack = pp.pshift + pp.pack_bits <= 32 && pp.num_streams == 1 ? 1 : 0;
-        pp.cs_pack = pp.fine_pack && nslots == 2 && P->slot_kind[0] == SLOT_COUNT &&
-                     P->slot_kind[1] == SLOT_SUM_I64 && P->slot_stream[1] == 0 ? 1 : 0;
-        pp.pack_range = P->part_pack_range;
-      }
-    }
-    int grid = P->part_grid;
-#ifndef PGPU_PART_NO_STAGE  // (defined only by an A/B build of the library: every record stored from its lane)
-    // one-word records with <= 64 coarse runs: K8c stages each wave's records by run in LDS and stores them in runs;
-    // the grid (K8a's too) follows that instance's occupancy
-    pp.staged = pp.cshift > 0 && pp.num_coarse <= 64 ? (pp.pack_bits > 0 ? 1 : pp.mid_pair ? 2 : 0) : 0;
-    if (pp.staged) {
-      if (P->part_grid_staged[pp.staged - 1] <= 0) {
-        const int per_cu =
-            std::max(1, std::min(occupancy_part_pass(P->part_lds, P->num_parts, pp.num_coarse, pp.staged), 4));
-        P->part_grid_staged[pp.staged - 1] =
-            (int)std::max<int64_t>(1, std::min<int64_t>(P->num_tiles, (int64_t)P->table->num_cus * per_cu));
-      }
-      grid = P->part_grid_staged[pp.staged - 1];
-    }
-#endif
-    TRY(sc->block_off.ensure((size_t)grid * pp.num_coarse * 4));
-    pp.block_off = sc->block_off.as<uint32_t>();
-    // K8d's partitions are the ordered compaction's chunks (C5): K8d writes their counts and ranges, and finalize
-    // skips compact_count_kernel's pass over the table (P->k8d_counts)
-    {
-      const int64_t G = P->num_keys, nch = compact_ordered_chunks(G);
-      if (pp.cs_pack && !P->hash && ((int64_t)1 << pp.pshift) == kCompactChunkKeys && nch == P->num_parts &&
-          (int64_t)nslots * G * 8 > kHostCompactBytes) {
-        TRY(sc->cslots.ensure(compact_scratch_bytes(G, nslots)));
-        pp.chunk_cnt = sc->cslots.as<uint32_t>();
-        pp.chunk_mm = reinterpret_cast<long long*>(sc->cslots.as<uint8_t>() + ((nch * 4 + 7) & ~int64_t(7)));
-        P->k8d_counts = true;
-      }
-    }
-    const KFxSplit fxs = fx_split(P);  // (plans with SLOT_SUM_FX slots: K8d / K8h split the records' doubles)
-    if (launch_partitioned(pp, grid, P->part_lds, stream, P->fx ? &fxs : nullptr))
-      return fail(PGPU_ERR_DEVICE, "partitioned group-by launch failed: %s", hipGetErrorString(hipGetLastError()));
-  } else if (C.num_tiles > 0) {
-    static const bool wg_times = diag("wgtimes");
-    if (wg_times) TRY(diag_wg_times_begin(kp, grid, stream));
-    set_tile_claims(kp, P->d_stats, grid, c);
-    bool fits = true;
-    if (P->alone)
-      fits = set_slot_weights(kp, grid, P->table->num_cus, P->cfg.slot_weight_step,
-                              P->leap_reserved ? P->leap_tiles : kLeapLdsTiles);
-    P->last_scan.tiles = kp.num_tiles;
-    P->last_scan.grid = grid;
-    P->last_scan.tile_chunks = kp.tile_chunks;
-    P->last_scan.slot_n = kp.slot_n;
-    for (int s = 0; s < kMaxCuSlots; ++s) P->last_scan.slot_w[s] = kp.slot_n ? kp.slot_w[s] : 0;
-    P->last_scan.alone = P->alone;
-    P->last_scan.declined = !fits;
-    int rc;
-    if (P->fx) {  // the FX instances: the launch's parameters and the split of the fixed-point slots
-      KParamsFx kf;
-      static_cast<KParams&>(kf) = kp;
-      kf.fx = fx_split(P);
-      rc = launch_filter_groupby_fx(kf, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
-    } else {
-      rc = launch_filter_groupby(kp, P->mode,
-                                 scan_variant(P),
-                                 grid, P->lds_bytes, stream);
-    }
-    if (rc) return fail(PGPU_ERR_DEVICE, "scan launch failed: %s", hipGetErrorString(hipGetLastError()));
-    X.mark("scan launched");
-    if (wg_times) TRY(diag_wg_times_report(P->table, kp, grid, stream));
-  }
+  if (C.num_tiles > 0 && P->partitioned) TRY(launch_partitioned_chunk(P, stream, X, kp));
+  else if (C.num_tiles > 0) TRY(launch_scan_chunk(P, stream, X, kp, grid, c));
   PGPU_TIMING_RECORD(P, sc->cev[2 * c + 1], stream);
   if (C.num_tiles > 0 && P->any_leap2 && P->leap_reserved && !P->partitioned) {
     if (P->chunks.size() == 1 && P->mode == MODE_LDS) {  // folded into the epilogue's launch
@@ -747,137 +838,146 @@ int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const Laun
   return 0;
 }
 
-int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
+// Star-tree segments: their records (this scratch's work buffers, the plan's match sets), then the K5 traversal and
+// the K6 residual scan + aggregation into the same group table.
+static int epilogue_star(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
   Scratch* sc = P->scratch;
   const int nslots = X.nslots;
   const int64_t words = X.words;
-  KParams& kp = X.kp;
-  const int nl = P->launches_done;
-  if (nl == 0) PGPU_TIMING_RECORD(P, sc->ev[1], stream);
-  if (!P->star.empty()) {
-    // star-tree segments: K5 traversal then K6 residual scan + aggregation into the same group table
-    X.mark("before star buffers");
-    TRY(sc->starwork.ensure((size_t)P->star_work_bytes + P->star.size() * 8 + 16));
-    int64_t* seg_total = reinterpret_cast<int64_t*>(sc->starwork.as<uint8_t>() + P->star_work_bytes);
-    {
-      const void* before = sc->starrec.p;
-      TRY(sc->starrec.ensure(P->star.size() * sizeof(KStarSeg)));
-      if (sc->starrec.p != before) sc->starrec_sent.clear();  // a new buffer holds nothing yet
-    }
-    std::vector<KStarSeg> recs = P->star;
-    for (size_t i = 0; i < recs.size(); ++i) {
-      uint8_t* base = sc->starwork.as<uint8_t>() + P->star_work_off[i];
-      const int64_t nn = recs[i].num_nodes;
-      recs[i].ranges = reinterpret_cast<int32_t*>(base);
-      recs[i].prefix = reinterpret_cast<int64_t*>(base + ((2 * nn * 4 + 7) & ~int64_t(7)));
-      recs[i].frontier = reinterpret_cast<int32_t*>(base + ((2 * nn * 4 + 7) & ~int64_t(7)) + (nn + 1) * 8);
-      recs[i].out = recs[i].frontier + 6 * nn;
-    }
-    for (auto& f : P->star_match_fix)
-      recs[std::get<0>(f)].match[std::get<1>(f)] = X.sets + std::get<2>(f);
-    // The records (this scratch's work buffers, the plan's match sets) are the same for every execution of a cached
-    // plan on this scratch: uploaded when they differ from the last upload.  A small host-to-device copy could block
-    // the host for milliseconds behind other streams' work (C4 at 3 queries in flight: 5.4 ms in one execution).
-    const size_t rbytes = recs.size() * sizeof(KStarSeg);
-    X.mark("star buffers + records built");
-    if (sc->starrec_sent.size() != rbytes || memcmp(sc->starrec_sent.data(), recs.data(), rbytes) != 0) {
-      TRY(sc->starstage.ensure(rbytes));
-      memcpy(sc->starstage.p, recs.data(), rbytes);
-      HIP_TRY(hipMemcpyAsync(sc->starrec.p, sc->starstage.p, rbytes, hipMemcpyHostToDevice, stream));
-      sc->starrec_sent.assign(reinterpret_cast<const uint8_t*>(recs.data()),
-                              reinterpret_cast<const uint8_t*>(recs.data()) + rbytes);
-    }
-    X.mark("star records copy queued");
-    if (launch_startree_traverse(sc->starrec.as<KStarSeg>(), (int)recs.size(), seg_total, kp.deadline, kp.stats,
-                                 stream))
-      return fail(PGPU_ERR_DEVICE, "star-tree traversal launch failed: %s", hipGetErrorString(hipGetLastError()));
-    X.mark("K5 launched");
-    KStarParams sp;
-    memset(&sp, 0, sizeof sp);
-    sp.num_wgs = P->star_chunks;
-    sp.range_cache = P->star_range_cache;
-    sp.num_keys = (int)P->key_cols.size();
-    for (size_t j = 0; j < P->key_cols.size(); ++j) sp.key_stride[j] = P->key_stride[j];
-    sp.key_bias = P->key_bias;
-    sp.num_keys_total = P->num_keys;
-    sp.num_slots = nslots;
-    for (int sl = 0; sl < nslots; ++sl) {
-      sp.slot_kind[sl] = X.kp.slot_kind[sl];  // (SLOT_SUM_FX where the plan has fixed-point digits)
-      sp.slot_int[sl] = sl > 0 && P->slot_tcol[sl] >= 0 && is_int_type(P->table->types[P->slot_tcol[sl]]) ? 1 : 0;
-    }
-    sp.fx = fx_split(P);
-    sp.table = kp.table;
-    sp.slab = P->mode == MODE_LDS ? kp.slab + X.slabs_used * words : nullptr;
-    sp.hash_keys = kp.hash_keys;
-    sp.stats = kp.stats;
-    sp.deadline = kp.deadline;
-    sp.cache_ints = P->star_cache_ints;
-    for (int b = 0; b < P->star_batches; ++b) {  // kStarMaxSegs segments per launch, slabs back to back
-      const int s0 = b * kStarMaxSegs;
-      sp.segs = sc->starrec.as<KStarSeg>() + s0;
-      sp.num_segs = (int)std::min<int64_t>(kStarMaxSegs, (int64_t)recs.size() - s0);
-      sp.seg_total = seg_total + s0;
-      if (P->mode == MODE_LDS) sp.slab = kp.slab + (X.slabs_used + (int64_t)b * P->star_chunks) * words;
-      if (launch_startree_scan(sp, P->mode, P->fx, P->star_lds_bytes, stream))
-        return fail(PGPU_ERR_DEVICE, "star-tree scan launch failed: %s", hipGetErrorString(hipGetLastError()));
-      X.mark("K6 launched");
-    }
+  const KParams& kp = X.kp;
+  X.mark("before star buffers");
+  TRY(sc->starwork.ensure((size_t)P->star_work_bytes + P->star.size() * 8 + 16));
+  int64_t* seg_total = reinterpret_cast<int64_t*>(sc->starwork.as<uint8_t>() + P->star_work_bytes);
+  {
+    const void* before = sc->starrec.p;
+    TRY(sc->starrec.ensure(P->star.size() * sizeof(KStarSeg)));
+    if (sc->starrec.p != before) sc->starrec_sent.clear();  // a new buffer holds nothing yet
   }
-  if (!P->generic.empty()) {
-    // STATS_GENERIC segments: the leaves' match bitmaps, read back and replayed on the host at finalize
-    std::vector<KMaskJob> jobs;
-    for (const auto& g : P->generic)
-      for (int64_t g0 = 0; g0 < ((int64_t)g.num_docs + 31) / 32; g0 += kBlock)
-        jobs.push_back(KMaskJob{(int32_t)g.rec, (int32_t)g0, g.out_word});
-    TRY(sc->mask_jobs.ensure(std::max<size_t>(jobs.size(), 1) * sizeof(KMaskJob)));
-    TRY(sc->leaf_masks.ensure((size_t)std::max<int64_t>(P->generic_words, 1) * 4));
-    TRY(sc->maskstage.ensure(std::max<size_t>(jobs.size() * sizeof(KMaskJob), (size_t)P->generic_words * 4) + 16));
-    memcpy(sc->maskstage.p, jobs.data(), jobs.size() * sizeof(KMaskJob));
-    HIP_TRY(hipMemcpyAsync(sc->mask_jobs.p, sc->maskstage.p, jobs.size() * sizeof(KMaskJob), hipMemcpyHostToDevice,
-                           stream));
-    KParams mp = kp;
-    mp.segs = X.segrec;
-    if (launch_leaf_masks(mp, sc->mask_jobs.as<KMaskJob>(), (int32_t)jobs.size(), sc->leaf_masks.as<uint32_t>(),
-                          stream))
-      return fail(PGPU_ERR_DEVICE, "leaf mask launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIP_TRY(hipMemcpyAsync(sc->maskstage.p, sc->leaf_masks.p, (size_t)P->generic_words * 4, hipMemcpyDeviceToHost,
-                           stream));
+  std::vector<KStarSeg> recs = P->star;
+  for (size_t i = 0; i < recs.size(); ++i) {
+    uint8_t* base = sc->starwork.as<uint8_t>() + P->star_work_off[i];
+    const int64_t nn = recs[i].num_nodes;
+    recs[i].ranges = reinterpret_cast<int32_t*>(base);
+    recs[i].prefix = reinterpret_cast<int64_t*>(base + ((2 * nn * 4 + 7) & ~int64_t(7)));
+    recs[i].frontier = reinterpret_cast<int32_t*>(base + ((2 * nn * 4 + 7) & ~int64_t(7)) + (nn + 1) * 8);
+    recs[i].out = recs[i].frontier + 6 * nn;
   }
+  for (auto& f : P->star_match_fix)
+    recs[std::get<0>(f)].match[std::get<1>(f)] = X.sets + std::get<2>(f);
+  // The records (this scratch's work buffers, the plan's match sets) are the same for every execution of a cached
+  // plan on this scratch: uploaded when they differ from the last upload.  A small host-to-device copy could block
+  // the host for milliseconds behind other streams' work (C4 at 3 queries in flight: 5.4 ms in one execution).
+  const size_t rbytes = recs.size() * sizeof(KStarSeg);
+  X.mark("star buffers + records built");
+  if (sc->starrec_sent.size() != rbytes || memcmp(sc->starrec_sent.data(), recs.data(), rbytes) != 0) {
+    TRY(sc->starstage.ensure(rbytes));
+    memcpy(sc->starstage.p, recs.data(), rbytes);
+    HIP_TRY(hipMemcpyAsync(sc->starrec.p, sc->starstage.p, rbytes, hipMemcpyHostToDevice, stream));
+    sc->starrec_sent.assign(reinterpret_cast<const uint8_t*>(recs.data()),
+                            reinterpret_cast<const uint8_t*>(recs.data()) + rbytes);
+  }
+  X.mark("star records copy queued");
+  if (launch_startree_traverse(sc->starrec.as<KStarSeg>(), (int)recs.size(), seg_total, kp.deadline, kp.stats,
+                               stream))
+    return fail(PGPU_ERR_DEVICE, "star-tree traversal launch failed: %s", hipGetErrorString(hipGetLastError()));
+  X.mark("K5 launched");
+  KStarParams sp;
+  memset(&sp, 0, sizeof sp);
+  sp.num_wgs = P->star_chunks;
+  sp.range_cache = P->star_range_cache;
+  sp.num_keys = (int)P->key_cols.size();
+  for (size_t j = 0; j < P->key_cols.size(); ++j) sp.key_stride[j] = P->key_stride[j];
+  sp.key_bias = P->key_bias;
+  sp.num_keys_total = P->num_keys;
+  sp.num_slots = nslots;
+  for (int sl = 0; sl < nslots; ++sl) {
+    sp.slot_kind[sl] = X.kp.slot_kind[sl];  // (SLOT_SUM_FX where the plan has fixed-point digits)
+    sp.slot_int[sl] = sl > 0 && P->slot_tcol[sl] >= 0 && is_int_type(P->table->types[P->slot_tcol[sl]]) ? 1 : 0;
+  }
+  sp.fx = fx_split(P);
+  sp.table = kp.table;
+  sp.slab = P->mode == MODE_LDS ? kp.slab + X.slabs_used * words : nullptr;
+  sp.hash_keys = kp.hash_keys;
+  sp.stats = kp.stats;
+  sp.deadline = kp.deadline;
+  sp.cache_ints = P->star_cache_ints;
+  for (int b = 0; b < P->star_batches; ++b) {  // kStarMaxSegs segments per launch, slabs back to back
+    const int s0 = b * kStarMaxSegs;
+    sp.segs = sc->starrec.as<KStarSeg>() + s0;
+    sp.num_segs = (int)std::min<int64_t>(kStarMaxSegs, (int64_t)recs.size() - s0);
+    sp.seg_total = seg_total + s0;
+    if (P->mode == MODE_LDS) sp.slab = kp.slab + (X.slabs_used + (int64_t)b * P->star_chunks) * words;
+    if (launch_startree_scan(sp, P->mode, P->fx, P->star_lds_bytes, stream))
+      return fail(PGPU_ERR_DEVICE, "star-tree scan launch failed: %s", hipGetErrorString(hipGetLastError()));
+    X.mark("K6 launched");
+  }
+  return 0;
+}
+
+// STATS_GENERIC segments: the leaves' match bitmaps, read back and replayed on the host at finalize.
+static int epilogue_generic_masks(pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X) {
+  Scratch* sc = P->scratch;
+  std::vector<KMaskJob> jobs;
+  for (const auto& g : P->generic)
+    for (int64_t g0 = 0; g0 < ((int64_t)g.num_docs + 31) / 32; g0 += kBlock)
+      jobs.push_back(KMaskJob{(int32_t)g.rec, (int32_t)g0, g.out_word});
+  TRY(sc->mask_jobs.ensure(std::max<size_t>(jobs.size(), 1) * sizeof(KMaskJob)));
+  TRY(sc->leaf_masks.ensure((size_t)std::max<int64_t>(P->generic_words, 1) * 4));
+  TRY(sc->maskstage.ensure(std::max<size_t>(jobs.size() * sizeof(KMaskJob), (size_t)P->generic_words * 4) + 16));
+  memcpy(sc->maskstage.p, jobs.data(), jobs.size() * sizeof(KMaskJob));
+  HIP_TRY(hipMemcpyAsync(sc->mask_jobs.p, sc->maskstage.p, jobs.size() * sizeof(KMaskJob), hipMemcpyHostToDevice,
+                         stream));
+  KParams mp = X.kp;
+  mp.segs = X.segrec;
+  if (launch_leaf_masks(mp, sc->mask_jobs.as<KMaskJob>(), (int32_t)jobs.size(), sc->leaf_masks.as<uint32_t>(),
+                        stream))
+    return fail(PGPU_ERR_DEVICE, "leaf mask launch failed: %s", hipGetErrorString(hipGetLastError()));
+  HIP_TRY(hipMemcpyAsync(sc->maskstage.p, sc->leaf_masks.p, (size_t)P->generic_words * 4, hipMemcpyDeviceToHost,
+                         stream));
+  return 0;
+}
+
+// MODE_LDS: folds every slab written -- the scan launches' (back to back) and the star-tree chunks' after them -- into
+// the table, with the deferred leap-frog statistics in the same launch; no slab: the table's initial values.
+static int epilogue_fold(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
+  const KParams& kp = X.kp;
+  const int64_t all = X.slabs_used + (int64_t)P->star_batches * P->star_chunks;
+  if (all == 0) {
+    if (launch_table_init(X.table, P->slot_kind.data(), X.nslots, P->num_keys, nullptr, stream))
+      return fail(PGPU_ERR_DEVICE, "table init launch failed");
+  } else if (launch_epilogue(kp.slab, P->slot_kind.data(), X.nslots, P->num_keys, (int32_t)all, X.table, X.leap_segs,
+                             P->seg_stride, X.leap_nsegs, kp.leap_maps, kp.stats, stream)) {
+    return fail(PGPU_ERR_DEVICE, "reduce launch failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  X.leap_nsegs = 0;
+  X.mark("epilogue launched");
+  return 0;
+}
+
+// PGPU_TRACE: the execution's host time, and its marks when it took over a millisecond.
+static void trace_execution(const ExecCtx& X) {
+  const double end = now_us();
+  fprintf(stderr, "[pgpu] execute: %.1f us host\n", end - X.t_start);
+  static const bool all_marks = diag("marks");  // PGPU_TRACE=1,marks: every execution's marks
+  if (end - X.t_start > 1000.0 || all_marks) {
+    double prev = X.t_start;
+    for (const auto& m : X.marks) {
+      fprintf(stderr, "[pgpu]   %s +%.1f us\n", m.first, m.second - prev);
+      prev = m.second;
+    }
+    fprintf(stderr, "[pgpu]   (end) +%.1f us\n", end - prev);
+  }
+}
+
+int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
+  Scratch* sc = P->scratch;
+  const KParams& kp = X.kp;
+  if (P->launches_done == 0) PGPU_TIMING_RECORD(P, sc->ev[1], stream);
+  if (!P->star.empty()) TRY(epilogue_star(P, stream, X));
+  if (!P->generic.empty()) TRY(epilogue_generic_masks(P, stream, X));
   PGPU_TIMING_RECORD(P, sc->ev[2], stream);
   X.mark("event 2 recorded");
-  if (P->mode == MODE_LDS) {
-    // fold every slab written: the scan launches' (back to back) and the star-tree chunks' after them
-    const int64_t all = X.slabs_used + (int64_t)P->star_batches * P->star_chunks;
-    if (all == 0) {
-      if (launch_table_init(X.table, P->slot_kind.data(), nslots, P->num_keys, nullptr, stream))
-        return fail(PGPU_ERR_DEVICE, "table init launch failed");
-    } else {
-      // PGPU_EPILOGUE_EXPORT (an A/B build of the library only): for small internal tables the epilogue's last block
-      // also writes table + statistics to pinned host memory and finalize launches no copy.  Measured and not the
-      // default (r06 sessions i, j): the copy launch goes, but the host sees the stream complete ~10-15 us later
-      // (C1 latency 0.057 -> 0.071 ms, C3 at 125 segments 0.163 -> 0.169).
-#ifdef PGPU_EPILOGUE_EXPORT
-      const bool exp = !X.external && X.words * 8 <= kExportBytes;
-#else
-      const bool exp = false;
-#endif
-      if (exp) {
-        TRY(sc->exported.ensure((size_t)X.words * 8 + 64));
-        if (!sc->export_done.p) {
-          TRY(sc->export_done.ensure(64));
-          HIP_TRY(hipMemsetAsync(sc->export_done.p, 0, 64, stream));
-        }
-      }
-      if (launch_epilogue(kp.slab, P->slot_kind.data(), nslots, P->num_keys, (int32_t)all, X.table, X.leap_segs,
-                          P->seg_stride, X.leap_nsegs, kp.leap_maps, kp.stats,
-                          exp ? reinterpret_cast<uint64_t*>(sc->exported.p) : nullptr, exp ? sc->export_done.as<unsigned int>() : nullptr,
-                          stream))
-        return fail(PGPU_ERR_DEVICE, "reduce launch failed: %s", hipGetErrorString(hipGetLastError()));
-      P->exported = exp;
-    }
-    X.leap_nsegs = 0;
-    X.mark("epilogue launched");
-  }
+  if (P->mode == MODE_LDS) TRY(epilogue_fold(P, stream, X));
   if (P->mode == MODE_HASH && !P->part_hash && kp.pack_slot >= 0 &&
       launch_hash_unpack(X.table, kp.hash_keys, P->num_keys, kp.pack_slot, kp.pack_shift, stream))
     return fail(PGPU_ERR_DEVICE, "hash unpack launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -887,19 +987,7 @@ int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
   PGPU_TIMING_RECORD(P, sc->ev[3], stream);
   P->last_stream = stream;
   P->executed = true;
-  if (trace_on()) {
-    const double end = now_us();
-    fprintf(stderr, "[pgpu] execute: %.1f us host\n", end - X.t_start);
-    static const bool all_marks = diag("marks");  // PGPU_TRACE=1,marks: every execution's marks
-    if (end - X.t_start > 1000.0 || all_marks) {
-      double prev = X.t_start;
-      for (const auto& m : X.marks) {
-        fprintf(stderr, "[pgpu]   %s +%.1f us\n", m.first, m.second - prev);
-        prev = m.second;
-      }
-      fprintf(stderr, "[pgpu]   (end) +%.1f us\n", end - prev);
-    }
-  }
+  if (trace_on()) trace_execution(X);
   return 0;
 }
 
@@ -914,480 +1002,4 @@ int plan_execute_impl(pgpu_plan_s* P, hipStream_t stream, void* d_table) {
   return exec_epilogue(P, stream, X);
 }
 
-// Group-by dictIds of composite key k: (k / stride[j]) % card[j] (DictionaryBasedGroupKeyGenerator.java:276-323).
-void decode_keys(const pgpu_plan_s* P, pgpu_result_s* R, int64_t row, uint64_t key) {
-  for (int j = 0; j < R->num_keys; ++j)
-    R->gid(j)[row] = (int32_t)((key / (uint64_t)P->key_stride[j]) % (uint64_t)P->key_card[j] + P->key_off[j]);
-}
-
-// key_begin / key_count: a shard [slots][key_count] of the dense table holding keys [key_begin, key_begin +
-// key_count) (after a reduce-scatter across GPUs); the whole table is (0, num_keys).
-int plan_finalize_impl(pgpu_plan_s* P, hipStream_t stream, const void* d_table, int64_t key_begin, int64_t key_count,
-                       pgpu_result_s* R) {
-  Scratch* sc = P->scratch;
-  const double t_start = trace_on() ? now_us() : 0;
-  if (!P->executed) return fail(PGPU_ERR_INVALID_ARGUMENT, "plan not executed");
-  const uint64_t* table = reinterpret_cast<const uint64_t*>(d_table ? d_table : P->d_table_used);
-  const int nslots = (int)P->slot_kind.size();
-  const int nk = (int)P->key_cols.size();
-  const int64_t G = key_count;
-  int64_t n = 0;
-  uint64_t matched = 0, star_scanned = 0;
-  const int64_t words = (int64_t)nslots * G;
-  // the epilogue wrote this execution's whole table + statistics to host memory, and nothing has changed the table
-  // since (a combine clears P->exported)
-  const bool from_export = P->exported && table == P->d_table_used && key_begin == 0 && G == P->num_keys;
-  P->star_metric_bytes = -1;  // read back by the small-table path only
-  double t_sync1 = 0;
-  R->pool = P->table->result_pool;
-  {
-    // The buffers filled before the wait below: growing one frees the old one, and hipFree waits for the whole
-    // device -- it would hold the wait (and a pgpu_plan_cancel or the query's deadline) until the scan is done.  When
-    // one must grow, the plan's work is waited for first (cancel- and deadline-aware), then the buffers grow.
-    bool grow = sc->counter.cap < 64 + (size_t)kMaxSlots * 16 || sc->readback.cap < 64 + (size_t)nslots * 16;
-    if (!P->hash && words * 8 <= kHostCompactBytes && !from_export) grow |= sc->readback.cap < (size_t)words * 8 + 64;
-    else if (!P->hash) grow |= sc->cslots.cap < compact_scratch_bytes(G, nslots);
-    else if (!P->part_hash_live)
-      grow |= sc->ckeys.cap < (size_t)std::max<int64_t>(1, std::min<int64_t>(G, P->merged_records >= 0
-                                                                                 ? P->merged_records
-                                                                                 : std::max<int64_t>(P->total_docs, 1))) *
-                                 8 * (1 + nslots);
-    if (grow) {
-      TRY(wait_plan(P, stream));
-      TRY(sc->counter.ensure(64 + (size_t)kMaxSlots * 16));
-    }
-  }
-  if (!P->hash && words * 8 <= kHostCompactBytes) {
-    // small dense table: the epilogue's copy in pinned host memory (from_export), else one or two copies (table +
-    // stats) and one sync; compacted on the host in key order
-    uint64_t* st;
-    if (from_export) {
-      st = reinterpret_cast<uint64_t*>(sc->exported.p);
-    } else {
-      TRY(sc->readback.ensure((size_t)words * 8 + 64));
-      st = reinterpret_cast<uint64_t*>(sc->readback.p);
-      if (reinterpret_cast<const uint8_t*>(P->d_stats) == reinterpret_cast<const uint8_t*>(table) + words * 8) {
-        HIP_TRY(hipMemcpyAsync(st, table, (size_t)words * 8 + 64, hipMemcpyDeviceToHost, stream));  // table + stats
-      } else {
-        HIP_TRY(hipMemcpyAsync(st, table, (size_t)words * 8, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(st + words, P->d_stats, 64, hipMemcpyDeviceToHost, stream));
-      }
-    }
-    TRY(wait_plan(P, stream));
-    t_sync1 = trace_on() ? now_us() : 0;
-    if (st[words + 5]) return timeout_fail(P);
-    matched = st[words];
-    star_scanned = st[words + 1] + st[words + 2];
-    P->star_docs_read = (int64_t)st[words + 3];
-    P->star_metric_bytes = (int64_t)st[words + 7] * 64;
-    for (int64_t k = 0; k < G; ++k) n += st[k] != 0;
-    TRY(R->alloc(nk, nslots, n));
-    int64_t j = 0;
-    for (int64_t k = 0; k < G; ++k) {
-      if (!st[k]) continue;
-      decode_keys(P, R, j, (uint64_t)(key_begin + k));
-      for (int s = 0; s < nslots; ++s) R->slot(s)[j] = st[(int64_t)s * G + k];
-      ++j;
-    }
-  } else if (!P->hash) {
-    // large dense table: ordered compaction on the device (count / scan, then a scatter in key order), copied back
-    // into the pinned result buffer.  Two forms: the columnar dictIds + 8-byte words, or -- when it moves fewer
-    // bytes, as for C5's 10M groups of 10M keys -- a presence bitmap over the keys plus each slot's words at the
-    // narrowest width their range allows (decoded on the host on first access).
-    const int64_t nch = compact_ordered_chunks(G);
-    TRY(sc->counter.ensure(64 + (size_t)nslots * 16));
-    TRY(sc->cslots.ensure(compact_scratch_bytes(G, nslots)));
-    long long* d_minmax = reinterpret_cast<long long*>(sc->counter.as<uint8_t>() + 64);
-    // K8d already counted this execution's table by chunk (unchanged since: no combine, the whole key range)
-    const bool counted = P->k8d_counts && table == P->d_table_used && key_begin == 0 && G == P->num_keys;
-    if (launch_compact_dense_count(table, nslots, G, sc->cslots.as<uint32_t>(), sc->counter.as<unsigned long long>(),
-                                   d_minmax, stream, counted))
-      return fail(PGPU_ERR_DEVICE, "compact count launch failed: %s", hipGetErrorString(hipGetLastError()));
-    TRY(sc->readback.ensure(64 + (size_t)nslots * 16));
-    uint64_t* st = reinterpret_cast<uint64_t*>(sc->readback.p);
-    HIP_TRY(hipMemcpyAsync(st, sc->counter.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(st + 1, P->d_stats, 48, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(st + 8, d_minmax, (size_t)nslots * 16, hipMemcpyDeviceToHost, stream));
-    TRY(wait_plan(P, stream));
-    t_sync1 = trace_on() ? now_us() : 0;
-    if (st[6]) return timeout_fail(P);
-    n = (int64_t)std::min<uint64_t>(st[0], (uint64_t)G);
-    matched = st[1];
-    star_scanned = st[2] + st[3];
-    P->star_docs_read = (int64_t)st[4];
-    std::vector<int32_t> width(nslots, 8);
-    int64_t narrow_bytes = 0;
-    for (int s = 0; s < nslots; ++s) {
-      const long long lo = (long long)st[8 + s], hi = (long long)st[8 + nslots + s];
-      width[s] = n > 0 ? compact_slot_width(lo, hi, P->slot_kind[s]) : 8;
-      narrow_bytes += n * width[s];
-    }
-    const int64_t bitmap_words = (G + 63) / 64;
-    const bool compact = P->cfg.compact_results && n > 0 && bitmap_words * 8 + narrow_bytes < n * (4 * nk + 8 * nslots);
-    if (compact) {
-      const int64_t cap = n;
-      TRY(sc->ckeys.ensure((size_t)bitmap_words * 8 + (size_t)nslots * cap * 8));
-      uint8_t* dev = sc->ckeys.as<uint8_t>();
-      if (launch_compact_dense_scatter(table, nslots, G, P->slot_kind.data(), sc->cslots.as<uint32_t>(), d_minmax,
-                                       reinterpret_cast<uint64_t*>(dev), dev + bitmap_words * 8, cap, stream))
-        return fail(PGPU_ERR_DEVICE, "compact scatter launch failed: %s", hipGetErrorString(hipGetLastError()));
-      R->num_keys = nk;
-      R->num_slots = nslots;
-      R->n = n;
-      R->ckey_base = key_begin;
-      R->cbits = G;
-      R->cstride = P->key_stride;
-      R->ccard = P->key_card;
-      R->coff = P->key_off;
-      R->cwidth = width;
-      R->cslot_off.assign(nslots, 0);
-      size_t off = (size_t)bitmap_words * 8;
-      for (int s = 0; s < nslots; ++s) {
-        R->cslot_off[s] = off;
-        off += ((size_t)n * width[s] + 7) & ~size_t(7);
-      }
-      if (R->pool) R->cbuf = R->pool->take();
-      TRY(R->cbuf.ensure(off));
-      uint8_t* h = reinterpret_cast<uint8_t*>(R->cbuf.p);
-      HIP_TRY(hipMemcpyAsync(h, dev, (size_t)bitmap_words * 8, hipMemcpyDeviceToHost, stream));
-      for (int s = 0; s < nslots; ++s)
-        HIP_TRY(hipMemcpyAsync(h + R->cslot_off[s], dev + bitmap_words * 8 + (size_t)s * cap * 8, (size_t)n * width[s],
-                               hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      R->compact.store(true, std::memory_order_release);
-    } else {
-      const int64_t cap = std::max<int64_t>(2, (n + 1) & ~int64_t(1));
-      TRY(sc->ckeys.ensure((size_t)cap * (4 * nk + 8 * nslots) + 8));
-      if (launch_compact_ordered_scatter(table, nslots, G, key_begin, P->key_stride.data(), P->key_card.data(),
-                                         P->key_off.data(), nk, sc->cslots.as<uint32_t>(), sc->ckeys.p, cap, stream))
-        return fail(PGPU_ERR_DEVICE, "compact launch failed: %s", hipGetErrorString(hipGetLastError()));
-      TRY(R->alloc(nk, nslots, n));
-      if (n > 0) {
-        const uint8_t* dev = sc->ckeys.as<uint8_t>();
-        for (int j = 0; j < nk; ++j)
-          HIP_TRY(hipMemcpyAsync(R->gid_raw(j), dev + (size_t)j * cap * 4, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-        for (int s = 0; s < nslots; ++s)
-          HIP_TRY(hipMemcpyAsync(R->slot_raw(s), dev + (size_t)nk * cap * 4 + (size_t)s * cap * 8, (size_t)n * 8,
-                                 hipMemcpyDeviceToHost, stream));
-      }
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
-  } else {
-    // hash table: unordered compaction, then key order on the host
-    const int64_t rec = 1 + nslots;  // entry-major compact record: key, then the slot words
-    int64_t cap;
-    const bool k8h = P->part_hash_live;
-    if (k8h) {  // K8h wrote the compacted records and their count at execute
-      cap = part_hash_out_cap(P);
-    } else {
-      cap = std::max<int64_t>(1, std::min<int64_t>(G, P->merged_records >= 0 ? P->merged_records
-                                                                            : std::max<int64_t>(P->total_docs, 1)));
-      TRY(sc->counter.ensure(64));
-      TRY(sc->ckeys.ensure((size_t)cap * 8 * rec));
-      HIP_TRY(hipMemsetAsync(sc->counter.p, 0, 8, stream));
-      if (launch_compact(table, sc->hash_keys.as<unsigned long long>(), nslots, G, sc->counter.as<unsigned long long>(),
-                         sc->ckeys.as<uint64_t>(), cap, stream))
-        return fail(PGPU_ERR_DEVICE, "compact launch failed");
-    }
-    // each slot's range over the records, read back with their count (the compact form's widths, below)
-    const bool want_compact = P->stage_end.empty() && P->cfg.compact_results;
-    TRY(sc->counter.ensure(64 + (size_t)kMaxSlots * 16));  // (no regrowth: the first allocation is 4 KB)
-    unsigned long long* d_mm = reinterpret_cast<unsigned long long*>(sc->counter.as<uint8_t>() + 64);
-    if (want_compact &&
-        (k8h ? launch_hash_minmax_parts(sc->part_mm.as<unsigned long long>(), P->num_parts, nslots, d_mm, stream)
-             : launch_hash_minmax(sc->ckeys.as<uint64_t>(), sc->counter.as<unsigned long long>(), cap, nslots, d_mm,
-                                  stream)))
-      return fail(PGPU_ERR_DEVICE, "slot range launch failed: %s", hipGetErrorString(hipGetLastError()));
-    TRY(sc->readback.ensure(64 + (size_t)nslots * 16));
-    uint64_t* st = reinterpret_cast<uint64_t*>(sc->readback.p);
-    HIP_TRY(hipMemcpyAsync(st, sc->counter.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(st + 1, P->d_stats, 48, hipMemcpyDeviceToHost, stream));
-    if (want_compact) HIP_TRY(hipMemcpyAsync(st + 8, d_mm, (size_t)nslots * 16, hipMemcpyDeviceToHost, stream));
-    TRY(wait_plan(P, stream));
-    t_sync1 = trace_on() ? now_us() : 0;
-    if (st[6]) return timeout_fail(P);
-    if (st[5])  // stats[4]: a probe found no free slot (hash_slot) -- the table was sized below the plan's groups
-      return fail(PGPU_ERR_DEVICE, "group hash table of %lld slots overflowed (plan bound %lld groups)",
-                  (long long)G, (long long)P->group_bound);
-    if (k8h && st[0] > (uint64_t)cap) return part_hash_overflow(P, st[0]);
-    n = (int64_t)std::min<uint64_t>(st[0], (uint64_t)cap);
-    matched = st[1];
-    star_scanned = st[2] + st[3];
-    P->star_docs_read = (int64_t)st[4];
-    if (P->groups_seen && P->merged_records < 0) P->groups_seen->store(n, std::memory_order_relaxed);
-    if (n >= 4096 && P->stage_end.empty()) {
-      // Decoded on the device in one streaming pass over the records, in their (hash / partition) order -- the
-      // LONG_MAP holder's iteration order is fastutil's hash order (DictionaryBasedGroupKeyGenerator.java:693, :719)
-      // and no consumer depends on group order -- held in compact form when that moves fewer bytes (C5-sized
-      // results: 10M groups): composite keys at 4 or 8 bytes instead of the decoded dictIds, and each slot at the
-      // narrowest width of its range (as the dense compact form); the host decodes it on first access
-      // (result_expand).
-      int key_bits = 1;
-      {
-        const long double space = (long double)P->key_stride[nk - 1] * (long double)P->key_card[nk - 1];
-        while (key_bits < 64 && (long double)(INT64_C(1) << key_bits) < space) ++key_bits;
-      }
-      const int32_t key_width = key_bits <= 32 ? 4 : 8;
-      std::vector<int32_t> width(nslots, 8);
-      std::vector<int64_t> woff(nslots, 0);
-      size_t cbytes = ((size_t)n * key_width + 7) & ~size_t(7);
-      for (int s2 = 0; s2 < nslots; ++s2) {
-        const long long lo = (long long)(st[8 + s2] ^ (1ull << 63)), hi = (long long)(st[8 + nslots + s2] ^ (1ull << 63));
-        width[s2] = compact_slot_width(lo, hi, P->slot_kind[s2]);
-        woff[s2] = (int64_t)cbytes;
-        cbytes += ((size_t)n * width[s2] + 7) & ~size_t(7);
-      }
-      if (want_compact && cbytes < (size_t)n * (4 * nk + 8 * nslots)) {
-        TRY(sc->hsort.ensure(cbytes + 256));
-        uint8_t* out = sc->hsort.as<uint8_t>();
-        if (launch_hash_compact(sc->ckeys.as<uint64_t>(), n, nslots, key_width, width.data(), woff.data(), out, stream))
-          return fail(PGPU_ERR_DEVICE, "hash compact launch failed: %s", hipGetErrorString(hipGetLastError()));
-        R->num_keys = nk;
-        R->num_slots = nslots;
-        R->n = n;
-        R->ckey_width = key_width;
-        R->cstride = P->key_stride;
-        R->ccard = P->key_card;
-        R->coff = P->key_off;
-        R->cwidth = width;
-        R->cslot_off.assign(woff.begin(), woff.end());
-        if (R->pool) R->cbuf = R->pool->take();
-        TRY(R->cbuf.ensure(cbytes));
-        HIP_TRY(hipMemcpyAsync(R->cbuf.p, out, cbytes, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        R->compact.store(true, std::memory_order_release);
-        n = -1;  // held compact
-      }
-    }
-    if (n >= 4096 && P->stage_end.empty()) {
-      // decoded into the columnar result on the device: one copy back
-      const size_t slot_off = pgpu_result_s::slot_offset(nk, n);
-      const size_t out_bytes = slot_off + (size_t)nslots * n * 8;
-      TRY(sc->hsort.ensure(out_bytes + 256));
-      uint8_t* out = sc->hsort.as<uint8_t>();
-      if (launch_hash_decode(sc->ckeys.as<uint64_t>(), n, nslots, nk, P->key_stride.data(), P->key_card.data(),
-                             P->key_off.data(), out, slot_off, stream))
-        return fail(PGPU_ERR_DEVICE, "hash decode launch failed: %s", hipGetErrorString(hipGetLastError()));
-      TRY(R->alloc(nk, nslots, n));
-      HIP_TRY(hipMemcpyAsync(R->buf.p, out, out_bytes, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      n = -1;  // decoded
-    } else if (n > 0) {
-      TRY(sc->readback.ensure((size_t)n * rec * 8));
-      st = reinterpret_cast<uint64_t*>(sc->readback.p);
-      HIP_TRY(hipMemcpyAsync(st, sc->ckeys.p, (size_t)n * rec * 8, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if (n < 0) {
-      n = R->n;
-    } else {
-    std::vector<uint64_t> stages;  // ARRAY_MAP: the stage tables (slot -> that group's key), back to back
-    std::vector<int64_t> stage_off;
-    if (!P->stage_end.empty() && n > 0) {
-      int64_t total = 0;
-      for (int64_t c : P->stage_cap) { stage_off.push_back(total); total += c; }
-      stages.resize((size_t)total);
-      HIP_TRY(hipMemcpyAsync(stages.data(), sc->stage_keys.p, (size_t)total * 8, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
-    std::vector<int64_t> order(n);
-    for (int64_t i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return st[a * rec] < st[b * rec]; });
-    TRY(R->alloc(nk, nslots, n));
-    for (int64_t r = 0; r < n; ++r) {
-      const uint64_t* e = st + order[r] * rec;
-      if (!P->stage_end.empty()) {  // last group first: its key's slot part names the previous group's key
-        uint64_t cur = e[0];
-        for (int g = (int)P->stage_space.size() - 1; g >= 0; --g) {
-          const uint64_t local = cur % (uint64_t)P->stage_space[g], slot = cur / (uint64_t)P->stage_space[g];
-          const int j0 = g == 0 ? 0 : P->stage_end[g - 1], j1 = g < (int)P->stage_end.size() ? P->stage_end[g] : nk;
-          for (int j = j0; j < j1; ++j)
-            R->gid(j)[r] = (int32_t)((local / (uint64_t)P->key_stride[j]) % (uint64_t)P->key_card[j]);
-          if (g > 0) {
-            if (slot >= (uint64_t)P->stage_cap[g - 1]) return fail(PGPU_ERR_DEVICE, "ARRAY_MAP stage slot out of range");
-            cur = stages[(size_t)(stage_off[g - 1] + (int64_t)slot)];
-          }
-        }
-      } else {
-        decode_keys(P, R, r, e[0]);
-      }
-      for (int s = 0; s < nslots; ++s) R->slot(s)[r] = e[1 + s];
-    }
-    }
-  }
-  const double t_sync2 = trace_on() ? now_us() : 0;
-  const int na = (int)P->agg_fn.size();
-  R->num_aggs = na;
-  R->agg_slot = P->agg_slot;
-  R->slot_kind = P->slot_kind;
-  R->key_cols = P->key_cols;
-  R->key_dicts.assign(P->key_dicts.begin(), P->key_dicts.end());
-  R->key_types.clear();
-  for (int c : P->key_cols) R->key_types.push_back(P->table->types[c]);
-  R->agg_fn = P->agg_fn;
-  R->agg_col = P->agg_col;
-  R->agg_conv.assign(na, RCONV_I64);
-  for (int a = 0; a < na; ++a) {
-    const int fn = P->agg_fn[a];
-    if (fn == PGPU_AGG_COUNT) continue;  // CountAggregationFunction: exact count (held as double by Pinot)
-    if (fn == PGPU_AGG_SUM || fn == PGPU_AGG_AVG)
-      R->agg_conv[a] = P->slot_kind[P->agg_slot[a]] == SLOT_SUM_I64 ? RCONV_I64 : RCONV_F64;
-    else
-      R->agg_conv[a] = is_int_type(P->table->types[P->agg_col[a]]) ? RCONV_I64 : RCONV_KEY_F64;
-  }
-  // fixed-point FLOAT / DOUBLE sums (PGPU_OPT_EXACT_FP_SUM): W digit sums from the aggregation's slot on, converted to
-  // the one double on the result's first read -- after the merge for the parts of a composite plan
-  R->agg_fx.clear();
-  if (P->fx) {
-    R->agg_fx.assign(na, FxFormat{});
-    bool any = false;
-    for (int a = 0; a < na; ++a) {
-      const int sl = P->agg_slot[a];
-      if (P->agg_fn[a] == PGPU_AGG_COUNT || sl < 0 || P->slot_fx[sl] < 0) continue;
-      R->agg_fx[a] = P->slot_fmt[sl];
-      R->agg_conv[a] = RCONV_FX;
-      any = true;
-    }
-    R->fx_pending.store(any && !P->fx_part, std::memory_order_release);
-    R->fx_agreed = P->fx_agreed;
-  }
-  int64_t generic_entries = 0;
-  if (!P->generic.empty()) {  // the leaves' bitmaps were copied into maskstage by the (synchronised) stream
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(P->scratch->maskstage.p);
-    std::vector<int64_t> part(P->generic.size(), 0);
-    auto replay = [&](int i) {
-      const auto& g = P->generic[i];
-      const int64_t ngroups = ((int64_t)g.num_docs + 31) / 32;
-      std::vector<const uint32_t*> masks(P->num_leaves);
-      for (int k = 0; k < P->num_leaves; ++k) masks[P->leaf_perm[k]] = words + g.out_word + (int64_t)k * ngroups;
-      part[i] = simulate_entries_scanned(g.tree, masks, g.num_docs);
-    };
-    if (P->generic.size() > 4) host_pool().run((int)P->generic.size(), replay);
-    else for (size_t i = 0; i < P->generic.size(); ++i) replay((int)i);
-    for (int64_t v : part) generic_entries += v;
-  }
-  // GroupByCombineOperator.mergeResults (:215-219): the merged map holds >= numGroupsLimit groups (PQL mode only)
-  R->groups_limit_reached = P->pql_cap && nk > 0 && P->num_groups_limit > 0 && n >= P->num_groups_limit;
-  R->stats[0] = (int64_t)matched;
-  R->stats[1] = P->scanned_entries_model + (int64_t)star_scanned + generic_entries;
-  R->stats[2] = ((int64_t)matched - P->post_exempt_docs) * P->num_projected;
-  R->stats[3] = P->total_docs;
-  R->stats[4] = (int64_t)P->segs.size();
-  R->stats[5] = P->segments_matched_filter;
-  if (trace_on())
-    fprintf(stderr, "[pgpu] finalize: launch+sync1 %.1f us, copy+sync2 %.1f us, decode %.1f us (n=%lld)\n",
-            t_sync1 - t_start, t_sync2 - t_sync1, now_us() - t_sync2, (long long)n);
-  return 0;
-}
-
 }  // namespace pgpu
-
-void pgpu::result_resolve_fx(pgpu_result_s* R) {
-  if (R->compact.load(std::memory_order_acquire) && result_expand(R)) return;
-  std::lock_guard<std::mutex> g(R->expand_mu);
-  if (!R->fx_pending.load(std::memory_order_acquire)) return;
-  for (int a = 0; a < R->num_aggs && a < (int)R->agg_fx.size(); ++a) {
-    if (R->agg_conv[a] != RCONV_FX) continue;
-    const FxFormat f = R->agg_fx[a];
-    const int s0 = R->agg_slot[a];
-    bool done = false;  // SUM and AVG of a column share their digit slots: converted once
-    for (int b = 0; b < a; ++b) done |= R->agg_slot[b] == s0 && b < (int)R->agg_fx.size() && R->agg_fx[b].mode != FX_NONE;
-    if (done) {
-      R->agg_conv[a] = RCONV_F64;
-      continue;
-    }
-    uint64_t* out = R->slot_raw(s0);
-    const uint64_t* d1 = R->slot_raw(s0 + 1);
-    const uint64_t* d2 = f.W > 2 ? R->slot_raw(s0 + 2) : nullptr;
-    for (int64_t i = 0; i < R->n; ++i) {
-      const int64_t digits[kFxMaxDigits] = {(int64_t)out[i], (int64_t)d1[i], d2 ? (int64_t)d2[i] : 0};
-      const double v = fx_result(digits, f);
-      memcpy(&out[i], &v, 8);
-    }
-    R->agg_conv[a] = RCONV_F64;
-    if (s0 < (int)R->slot_kind.size()) R->slot_kind[s0] = SLOT_SUM_F64;
-  }
-  R->fx_pending.store(false, std::memory_order_release);
-}
-
-// Columnar form of a compact result: rows are the bitmap's set bits in key order; each block of 4096 bitmap words is
-// decoded by one task of the host pool (a prefix of its popcounts gives its first row).
-int pgpu::result_expand(pgpu_result_s* R) {
-  std::lock_guard<std::mutex> g(R->expand_mu);
-  if (!R->compact.load(std::memory_order_acquire)) return 0;
-  const int nk = R->num_keys, ns = R->num_slots;
-  const int64_t n = R->n;
-  TRY(R->alloc(nk, ns, n));
-  if (R->ckey_width) {  // composite keys (hash-mode results): decode each row's key
-    const uint8_t* kb = reinterpret_cast<const uint8_t*>(R->cbuf.p);
-    constexpr int64_t kRowsPerTask = 1 << 20;
-    const int64_t ktasks = (n + kRowsPerTask - 1) / kRowsPerTask;
-    auto keys = [&](int t) {
-      const int64_t r0 = t * kRowsPerTask, r1 = std::min(n, r0 + kRowsPerTask);
-      for (int64_t r = r0; r < r1; ++r) {
-        const uint64_t key = R->ckey_width == 4 ? (uint64_t)reinterpret_cast<const uint32_t*>(kb)[r]
-                                                : reinterpret_cast<const uint64_t*>(kb)[r];
-        for (int j = 0; j < nk; ++j)
-          R->gid_raw(j)[r] = (int32_t)((key / (uint64_t)R->cstride[j]) % (uint64_t)R->ccard[j] + R->coff[j]);
-      }
-    };
-    if (ktasks > 1) host_pool().run((int)ktasks, keys);
-    else if (ktasks == 1) keys(0);
-  }
-  const uint64_t* bm = reinterpret_cast<const uint64_t*>(R->cbuf.p);
-  const int64_t words = R->ckey_width ? 0 : (R->cbits + 63) / 64;
-  constexpr int64_t kBlockWords = 4096;
-  const int64_t nb = (words + kBlockWords - 1) / kBlockWords;
-  std::vector<int64_t> first(nb + 1, 0);
-  auto count = [&](int b) {
-    int64_t c = 0;
-    for (int64_t w = b * kBlockWords; w < std::min(words, (b + 1) * kBlockWords); ++w) c += __builtin_popcountll(bm[w]);
-    first[b + 1] = c;
-  };
-  auto decode = [&](int b) {
-    int64_t row = first[b];
-    std::vector<int32_t*> gid(nk);
-    for (int j = 0; j < nk; ++j) gid[j] = R->gid_raw(j);
-    for (int64_t w = b * kBlockWords; w < std::min(words, (b + 1) * kBlockWords); ++w) {
-      for (uint64_t bits = bm[w]; bits; bits &= bits - 1, ++row) {
-        if (row >= n) return;
-        const uint64_t key = (uint64_t)(R->ckey_base + w * 64 + __builtin_ctzll(bits));
-        for (int j = 0; j < nk; ++j)
-          gid[j][row] = (int32_t)((key / (uint64_t)R->cstride[j]) % (uint64_t)R->ccard[j] + R->coff[j]);
-      }
-    }
-  };
-  if (nb > 1) host_pool().run((int)nb, count);
-  else if (nb == 1) count(0);
-  for (int64_t b = 0; b < nb; ++b) first[b + 1] += first[b];
-  if (nb > 1) host_pool().run((int)nb, decode);
-  else if (nb == 1) decode(0);
-  // the words, sign-extended from their compact widths
-  const uint8_t* base = reinterpret_cast<const uint8_t*>(R->cbuf.p);
-  constexpr int64_t kRows = 1 << 20;
-  const int64_t tasks = (n + kRows - 1) / kRows;
-  auto widen = [&](int t) {
-    const int64_t r0 = t * kRows, r1 = std::min(n, r0 + kRows);
-    for (int s = 0; s < ns; ++s) {
-      const uint8_t* src = base + R->cslot_off[s];
-      uint64_t* dst = R->slot_raw(s);
-      switch (R->cwidth[s]) {
-        case 1: for (int64_t r = r0; r < r1; ++r) dst[r] = (uint64_t)(int64_t)reinterpret_cast<const int8_t*>(src)[r]; break;
-        case 2: for (int64_t r = r0; r < r1; ++r) dst[r] = (uint64_t)(int64_t)reinterpret_cast<const int16_t*>(src)[r]; break;
-        case 3:  // 24-bit little-endian, sign-extended
-          for (int64_t r = r0; r < r1; ++r) {
-            const uint32_t u = (uint32_t)src[3 * r] | (uint32_t)src[3 * r + 1] << 8 | (uint32_t)src[3 * r + 2] << 16;
-            dst[r] = (uint64_t)(int64_t)((int32_t)(u << 8) >> 8);
-          }
-          break;
-        case 4: for (int64_t r = r0; r < r1; ++r) dst[r] = (uint64_t)(int64_t)reinterpret_cast<const int32_t*>(src)[r]; break;
-        default: memcpy(dst + r0, reinterpret_cast<const uint64_t*>(src) + r0, (size_t)(r1 - r0) * 8); break;
-      }
-    }
-  };
-  if (tasks > 1) host_pool().run((int)tasks, widen);
-  else if (tasks == 1) widen(0);
-  R->compact.store(false, std::memory_order_release);
-  return 0;
-}
-

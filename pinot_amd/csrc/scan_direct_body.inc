@@ -19,10 +19,10 @@
   uint8_t* lmaps = lds8 + L.maps;
   int kk = 0;  // tiles of this workgroup so far
   // The query's end time had passed when the launch came up (expand_tiles_kernel, run just before on the stream,
-  // read the device clock and set stats[5]): take no tile.  No clock read in this kernel -- even one outside the
+  // read the device clock and set stats[STAT_TIMED_OUT]): take no tile.  No clock read in this kernel -- even one outside the
   // tile loop changes the sparse instance's register allocation (108 -> 134 VGPRs, one wave less per SIMD; an
   // in-loop check cost 18% on C3, measured).  A scan already running is abandoned by the host (wait_plan).
-  if (p.deadline && p.stats[5]) return;
+  if (p.deadline && p.stats[STAT_TIMED_OUT]) return;
 #ifdef PGPU_SLOT_PRIO
   // (A/B build) the later-dispatched workgroups' waves get the higher issue priority: the SIMDs otherwise issue the
   // oldest wave first and equal shares end in dispatch-slot order
@@ -243,12 +243,12 @@
   for (int off = 32; off > 0; off >>= 1) matched += __shfl_xor(matched, off);
   unsigned long long entries = in_filter;
   for (int off = 32; off > 0; off >>= 1) entries += __shfl_xor(entries, off);
-  if ((tid & 63) == 0 && matched) atomicAdd(p.stats, matched);
-  if ((tid & 63) == 0 && entries) atomicAdd(p.stats + 2, entries);
+  if ((tid & 63) == 0 && matched) atomicAdd(p.stats + STAT_MATCHED, matched);
+  if ((tid & 63) == 0 && entries) atomicAdd(p.stats + STAT_SCAN_ENTRIES, entries);
   if (MODE == MODE_LDS) __syncthreads();
 #else
   {
-    const int idx[2] = {0, 2};
+    const int idx[2] = {STAT_MATCHED, STAT_SCAN_ENTRIES};
     unsigned long long v[2] = {matched, (unsigned long long)in_filter};
     block_stats_add<2>(p.stats, idx, v);
   }

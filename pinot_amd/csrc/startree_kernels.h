@@ -207,7 +207,7 @@ __device__ __forceinline__ void star_aggregate_half(const KStarParams& p, const 
 #pragma unroll
     for (int i = 0; i < 16; ++i)
       if ((m >> i) & 1u) {
-        const int64_t slot = hash_slot(p.hash_keys, G, (uint64_t)key[i], p.stats + 4);
+        const int64_t slot = hash_slot(p.hash_keys, G, (uint64_t)key[i], p.stats + STAT_HASH_FULL);
         if (slot < 0) m &= ~(1u << i);
         key[i] = (KeyT)(slot < 0 ? 0 : slot);
       }
@@ -301,7 +301,7 @@ __device__ __forceinline__ void startree_scan_body(const KStarParams& p) {
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   __shared__ int64_t wsum[BLOCK / 64];
   const int tid = threadIdx.x;
-  if (p.deadline && p.stats[5]) return;  // end time passed before the traversal ran (K5 set the flag)
+  if (p.deadline && p.stats[STAT_TIMED_OUT]) return;  // end time passed before the traversal ran (K5 set the flag)
   const int64_t G = p.num_keys_total;
   const int64_t words = MODE == MODE_LDS ? (int64_t)p.num_slots * G : 0;
   if (MODE == MODE_LDS)
@@ -440,7 +440,7 @@ __device__ __forceinline__ void startree_scan_body(const KStarParams& p) {
     }
   }
   {
-    const int idx[4] = {0, 1, 3, 7};
+    const int idx[4] = {STAT_MATCHED, STAT_STAR_ENTRIES, STAT_STAR_DOCS_READ, STAT_STAR_SECTORS};  // 0, 1, 3, 7
     unsigned long long v[4] = {(unsigned long long)matched, (unsigned long long)scanned, (unsigned long long)read,
                                sectors};
     block_stats_add<4, BLOCK>(p.stats, idx, v);
