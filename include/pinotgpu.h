@@ -203,8 +203,28 @@ typedef struct {
   int32_t arg;
 } pgpu_filter_op;
 
-/* AggregationFunctionType subset (core/query/aggregation/function/{Count,Sum,Min,Max,Avg}AggregationFunction). */
-enum pgpu_agg_fn { PGPU_AGG_COUNT = 0, PGPU_AGG_SUM = 1, PGPU_AGG_MIN = 2, PGPU_AGG_MAX = 3, PGPU_AGG_AVG = 4 };
+/* AggregationFunctionType subset (core/query/aggregation/function/{Count,Sum,Min,Max,Avg,DistinctCount}
+ * AggregationFunction).
+ * PGPU_AGG_DISTINCTCOUNT(col): per group, the number of distinct values of a dictionary-encoded single-value column of
+ * any type (INT / LONG / FLOAT / DOUBLE / STRING) among the matched docs -- DistinctCountAggregationFunction.java:
+ * 131-143 collects the docs' dictIds in a RoaringBitmap per group and counts the values they stand for.  Here the
+ * per-group set is a bitmap over the column's table-global dictIds (the same ids on every segment, so segments merge
+ * by OR in any order); the result is an exact integer: pgpu_result_values_i64 and pgpu_result_words_view (form 0)
+ * return it, pgpu_result_values as a double; ORDER BY and the trims compare it like a COUNT; no match gives 0.
+ * The column counts as projected (numEntriesScannedPostFilter); a segment carrying a star-tree is scanned
+ * (StarTreeUtils finds no function-column pair for it); an aggregation-only query whose functions are all MIN / MAX /
+ * DISTINCTCOUNT over match-all segments reports numEntriesScannedPostFilter 0 (AggregationPlanNode.java:233-246).
+ * Supported: dense key spaces (the LDS and global group tables, aggregation-only queries included); planned as with
+ * pgpu_config.partitioned_group_by = 0, hash_partitions = 0 and stream_chunks = 1.
+ * Declined with PGPU_ERR_UNSUPPORTED (the message names DISTINCTCOUNT): side bitmaps (keys x ceil(cardinality / 64)
+ * x 8 bytes per distinct column) above 1 GiB in one plan; key spaces that take the hash table (past 2^26 keys, or
+ * ARRAY_MAP stages); numGroupsLimit plans that split per segment; a raw (no-dictionary) column; more than 8 distinct
+ * columns; the combination with PGPU_OPT_EXACT_FP_SUM; every cross-GPU or external-merge entry point
+ * (pgpu_plan_combine*, pgpu_plan_exchange_*, pgpu_plan_finalize_range, an external d_table,
+ * pgpu_result_exchange_rows / merge_rows / combine_rows: per-rank counts do not add) and pgpu_result_datatable (Pinot
+ * ships the value set as an OBJECT). */
+enum pgpu_agg_fn { PGPU_AGG_COUNT = 0, PGPU_AGG_SUM = 1, PGPU_AGG_MIN = 2, PGPU_AGG_MAX = 3, PGPU_AGG_AVG = 4,
+                   PGPU_AGG_DISTINCTCOUNT = 5 };
 typedef struct {
   int32_t fn;
   int32_t column;   /* -1 for COUNT(*) */
@@ -475,7 +495,7 @@ int pgpu_plan_star_work(pgpu_plan plan, int64_t* out3);
  * was in flight (weights are for such launches only), [14] 1 = weights were declined because the longest weighted
  * run could pass [2]; [15] the scan kernel's instance: 0 sparse, 1 dense, 2 dense without gathers, 3 - 5 the sparse
  * specialisations (index + scan pair, pure AND, pure AND with 4-doc batches), 6 / 7 the sparse / dense instance of
- * plans with fixed-point sums (PGPU_OPT_EXACT_FP_SUM). */
+ * plans with fixed-point sums (PGPU_OPT_EXACT_FP_SUM), 8 / 9: sparse / dense of plans with PGPU_AGG_DISTINCTCOUNT. */
 int pgpu_plan_scan_geometry(pgpu_plan plan, int64_t* out16);
 /* Bytes of the star-tree metric arrays the last execution's document scan read (after finalize): the 64-byte
  * sectors holding at least one matched document, summed over the arrays read; -1 where finalize did not read the

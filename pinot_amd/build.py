@@ -22,7 +22,8 @@ SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTI
     [("k_direct.hip", ["-DPGPU_MODE=%d" % m], "k_direct_%d" % m) for m in range(3)] + \
     [("k_startree.hip", ["-DPGPU_MODE=%d" % m], "k_startree_%d" % m) for m in range(3)] + \
     [("k_direct_fx.hip", ["-DPGPU_MODE=%d" % m], "k_direct_fx_%d" % m) for m in range(3)] + \
-    [("k_startree_fx.hip", ["-DPGPU_MODE=%d" % m], "k_startree_fx_%d" % m) for m in range(3)]
+    [("k_startree_fx.hip", ["-DPGPU_MODE=%d" % m], "k_startree_fx_%d" % m) for m in range(3)] + \
+    [("k_direct_dc.hip", ["-DPGPU_MODE=%d" % m], "k_direct_dc_%d" % m) for m in range(2)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
            "rt_decls.h", "tile_split.h", "fx_sum.h", "scan_direct_body.inc", "part_aggregate_body.inc",

@@ -6,6 +6,7 @@ extern "C" {
 namespace {
 int exchangeable(pgpu_plan P) {
   if (!P) return fail(PGPU_ERR_INVALID_ARGUMENT, "null plan");
+  if (plan_has_distinct(P)) return distinct_decline("a cross-GPU exchange");
   if (P->composite) return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit plan: exchange its finalized result rows");
   if (!P->hash) return fail(PGPU_ERR_UNSUPPORTED, "dense group tables merge element-wise (all-reduce / reduce-scatter)");
   if (!P->stage_end.empty())
@@ -191,6 +192,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
   PGPU_ABI_GUARD;
   if (!r || nparts < 1 || nparts > (1 << 20) || !counts || (r->n > 0 && !rows))
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_has_distinct(r)) return distinct_decline("a cross-GPU exchange of rows");
   TRY(fx_rows_ready(r, "a cross-GPU exchange of rows"));
   if ((int)r->slot_kind.size() != r->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
   uint32_t conv = 0;
@@ -225,6 +227,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
 int pgpu_result_merge_rows(pgpu_result tmpl, const int64_t* rows, int64_t n, const int32_t* kinds, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!tmpl || !out || n < 0 || (n > 0 && !rows)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_has_distinct(tmpl)) return distinct_decline("a cross-GPU merge of rows");
   TRY(fx_rows_ready(tmpl, "a cross-GPU merge of rows"));
   if ((int)tmpl->slot_kind.size() != tmpl->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
   uint32_t conv = 0;
@@ -535,6 +538,7 @@ int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_
   PGPU_ABI_GUARD;
   if (!P || !c || !mode) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
+  if (plan_has_distinct(P)) return distinct_decline("a cross-GPU combine");  // (every rank's query carries the function)
   pgpu::CommWaitScope wait_limits(P->end_time_ms, &P->cancel);
   const int N = c->impl->nranks;
   int local;
@@ -601,6 +605,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   PGPU_ABI_GUARD;
   if (!P || !c) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
+  if (plan_has_distinct(P)) return distinct_decline("a cross-GPU combine");  // (every rank's query carries the function)
   P->k8d_counts = false;
   if (mode == PGPU_COMBINE_LOCAL) {
     if (key_begin) *key_begin = 0;
@@ -732,6 +737,7 @@ int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!r || !c || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (result_fx_local(r)) return fx_decline("a cross-GPU combine of rows");  // every rank's query carries the option
+  if (result_has_distinct(r)) return distinct_decline("a cross-GPU combine of rows");
   pgpu::Comm* C = c->impl.get();
   const int N = C->nranks, me = C->rank;
   TRY(C->usable());

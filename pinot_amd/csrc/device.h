@@ -472,6 +472,18 @@ __device__ __forceinline__ int64_t hash_slot(unsigned long long* __restrict__ ke
 // The split of the SLOT_SUM_FX slots: p is the KParamsFx of an FX instance (the only callers).
 __device__ __forceinline__ const KFxSplit& fx_split(const KParams& p) { return static_cast<const KParamsFx&>(p).fx; }
 
+// The side bitmaps of the SLOT_DISTINCT slots: p is the KParamsDc of a DC instance (the only callers).
+__device__ __forceinline__ const KDistinct& dc_bitmaps(const KParams& p) { return static_cast<const KParamsDc&>(p).dc; }
+
+// Sets bit `gid` of a group's bitmap row (`row`: the group's first word).  Tested before it is set: almost every doc
+// of a large scan meets a bit already set, and a plain load that sees a stale 0 only costs a redundant atomic, never
+// a bit (the words are written with atomicOr alone).
+__device__ __forceinline__ void distinct_mark(unsigned long long* __restrict__ row, uint32_t gid) {
+  unsigned long long* w = row + (gid >> 6);
+  const unsigned long long m = 1ull << (gid & 63u);
+  if (!(*gp(w) & m)) atomicOr(w, m);
+}
+
 template <int MODE>
 __device__ __forceinline__ void accumulate(uint64_t* __restrict__ base, int64_t idx, int kind, int64_t ikey,
                                            double dval) {
@@ -578,7 +590,9 @@ __device__ __forceinline__ int64_t slot_fold(int kind, int64_t a, int64_t v) {
 // dictionary lookup) and no slot sums doubles -- the gathers compile away, and with them their registers.
 // FX (instances of plans with PGPU_OPT_EXACT_FP_SUM): SLOT_SUM_FX slots -- the operand's double is split into its
 // fixed-point digit (fx_sum.h, KParams.fx_*) and added as an integer SUM.
-template <int MODE, int NB, bool SIMPLE = false, bool FX = false>
+// DC (instances of plans with DISTINCTCOUNT): SLOT_DISTINCT slots are skipped by the slot loop; each aggregation's
+// column is mapped to its global dictId, whose bit is set in the group's row of the side bitmap (distinct_mark).
+template <int MODE, int NB, bool SIMPLE = false, bool FX = false, bool DC = false>
 __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView (&S)[NB], const int64_t (&doc)[NB],
                                                 const bool (&ok)[NB], uint64_t* __restrict__ tbl, int64_t G) {
   int64_t key[NB];
@@ -630,6 +644,9 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
   int prev_col = -1;
   for (int s = 0; s < p.num_slots; ++s) {
     const int kind = p.slot_kind[s];
+    if constexpr (DC) {
+      if (kind == SLOT_DISTINCT) continue;  // the row is distinct_popcount_kernel's
+    }
     int64_t ikey[NB];
     double dval[NB];
 #pragma unroll
@@ -689,6 +706,29 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
 #pragma unroll
     for (int b = 0; b < NB; ++b)
       if (live[b]) accumulate<MODE>(tbl, (int64_t)s * G + idx[b], akind, ikey[b], dval[b]);
+  }
+  if constexpr (DC) {
+    // dense key spaces only: idx is the composite key in [0, G) (0 in a single-row table)
+    const KDistinct& D = dc_bitmaps(p);
+    for (int d = 0; d < D.n; ++d) {
+      const int col = D.col[d];
+      const int64_t W = D.words[d];
+      uint32_t did[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        KColC& c = S[b].cols[col];
+        did[b] = gather_id(c.fwd, c.bits, ok[b] ? doc[b] : 0);
+      }
+      uint32_t g[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {  // local -> global dictId, as a group-by key's
+        KColC& c = S[b].cols[col];
+        g[b] = c.lut ? (uint32_t)gp(c.lut)[did[b]] : did[b] + (uint32_t)c.lut_off;
+      }
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+        if (live[b]) distinct_mark(D.bits[d] + idx[b] * W, g[b]);
+    }
   }
 }
 
@@ -826,7 +866,7 @@ __device__ __forceinline__ void accumulate16_f(uint64_t* __restrict__ row, const
 }
 
 // One half (docs H..H+15 of the lane's group) of aggregate_group.
-template <int MODE, int H, bool SIMPLE = false, bool FX = false>
+template <int MODE, int H, bool SIMPLE = false, bool FX = false, bool DC = false>
 __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
                                                uint64_t* __restrict__ tbl, int64_t G) {
   const uint32_t m = (mask >> H) & 0xFFFFu;
@@ -866,12 +906,19 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
       ++s;
       continue;
     }
+    if constexpr (DC) {
+      if (kind == SLOT_DISTINCT) {  // the row is distinct_popcount_kernel's (the bitmaps: below)
+        ++s;
+        continue;
+      }
+    }
     const int col = p.slot_col[s];
     int e = s + 1;
     // (FX: a SLOT_SUM_FX slot reads the doubles as a float64 SUM does)
     auto is_f = [](int k) { return k == SLOT_SUM_F64 || (FX && k == SLOT_SUM_FX); };
     bool need_i = !is_f(kind), need_f = is_f(kind);
-    while (e < p.num_slots && p.slot_kind[e] != SLOT_COUNT && p.slot_col[e] == col) {
+    while (e < p.num_slots && p.slot_kind[e] != SLOT_COUNT && !(DC && p.slot_kind[e] == SLOT_DISTINCT) &&
+           p.slot_col[e] == col) {
       need_i |= !is_f(p.slot_kind[e]);
       need_f |= is_f(p.slot_kind[e]);
       ++e;
@@ -967,21 +1014,40 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
     }
     s = e;
   }
+  if constexpr (DC) {
+    const KDistinct& D = dc_bitmaps(p);
+    for (int d = 0; d < D.n; ++d) {
+      KColC& c = S.cols[D.col[d]];
+      const int64_t W = D.words[d];
+      decode_group<H>(c.fwd, c.bits, group, ids);
+      if (c.lut) {  // segment-uniform: local -> global dictId, as a group-by key's
+        gmem<int32_t>* __restrict__ lut = gp(c.lut);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ids[i] = (uint32_t)lut[ids[i]];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ids[i] += (uint32_t)c.lut_off;
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if ((m >> i) & 1u) distinct_mark(D.bits[d] + (int64_t)key[i] * W, ids[i]);
+    }
+  }
 }
 
 // Aggregates the matched docs (bits of `mask`) of this lane's 32-doc group `group` of segment S, 16 docs at a
 // time.  Dense key spaces only (MODE_LDS / MODE_GLOBAL: composite keys < 2^31).  Docs beyond numDocs decode from
 // the zero padding to dictId 0 (in bounds) and are never in `mask`.
-template <int MODE, bool SIMPLE = false, bool FX = false>
+template <int MODE, bool SIMPLE = false, bool FX = false, bool DC = false>
 __device__ __forceinline__ void aggregate_group(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
                                                 uint64_t* __restrict__ tbl, int64_t G) {
   // wave-uniform conditions: the single-row (G == 1) fold inside uses cross-lane shuffles
-  if (__any((mask & 0xFFFFu) != 0u)) aggregate_half<MODE, 0, SIMPLE, FX>(p, S, group, mask, tbl, G);
-  if (__any((mask >> 16) != 0u)) aggregate_half<MODE, 16, SIMPLE, FX>(p, S, group, mask, tbl, G);
+  if (__any((mask & 0xFFFFu) != 0u)) aggregate_half<MODE, 0, SIMPLE, FX, DC>(p, S, group, mask, tbl, G);
+  if (__any((mask >> 16) != 0u)) aggregate_half<MODE, 16, SIMPLE, FX, DC>(p, S, group, mask, tbl, G);
 }
 
 // Drains a wave's queue of matched (segment, doc) entries: 2 per lane per batch.
-template <int MODE, bool SIMPLE = false, bool FX = false>
+template <int MODE, bool SIMPLE = false, bool FX = false, bool DC = false>
 __device__ __forceinline__ void flush_wave_queue(const KParams& p, const uint32_t* qd, const uint32_t* qs, uint32_t qn,
                                                  int lane, uint64_t* __restrict__ tbl, int64_t G) {
   for (uint32_t base = 0; base < qn; base += 128) {
@@ -993,7 +1059,7 @@ __device__ __forceinline__ void flush_wave_queue(const KParams& p, const uint32_
     doc[0] = ok[0] ? qd[i0] : 0;
     doc[1] = ok[1] ? qd[i1] : 0;
     const SegView S[2] = {seg_view(p, ok[0] ? (int)qs[i0] : (int)qs[0]), seg_view(p, ok[1] ? (int)qs[i1] : (int)qs[0])};
-    aggregate_batch<MODE, 2, SIMPLE, FX>(p, S, doc, ok, tbl, G);
+    aggregate_batch<MODE, 2, SIMPLE, FX, DC>(p, S, doc, ok, tbl, G);
   }
 }
 

@@ -52,8 +52,12 @@ enum OpCode : int32_t { OP_LEAF = 0, OP_AND = 1, OP_OR = 2, OP_NOT = 3 };
 // the partitioned pipelines for agreed plans): they split the operand and add the digit
 // as an integer.  To everything after the accumulate -- table init, slab fold, compactions, widths, merges -- the
 // word is an int64 SUM, and the plan's own slot_kind says SLOT_SUM_I64 (pgpu_plan_s::slot_fx tells the digits apart).
+// SLOT_DISTINCT (plans with DISTINCTCOUNT aggregations): the row of the group table that holds the aggregation's count.
+// Only the DC instances of the scan see the kind (KParamsDc.slot_kind): they leave the row alone (it starts at 0) and
+// set the docs' global dictIds in the aggregation's side bitmap (KDistinct); distinct_popcount_kernel then stores the
+// per-key popcounts into the row.  To everything else the word is an int64 SUM (pgpu_plan_s::slot_dc tells them apart).
 enum SlotKind : int32_t { SLOT_COUNT = 0, SLOT_SUM_I64 = 1, SLOT_SUM_F64 = 2, SLOT_MIN_KEY = 3, SLOT_MAX_KEY = 4,
-                          SLOT_SUM_FX = 5 };
+                          SLOT_SUM_FX = 5, SLOT_DISTINCT = 6 };
 enum Mode : int32_t { MODE_LDS = 0, MODE_GLOBAL = 1, MODE_HASH = 2 };
 
 // The statistics block of one execution (KParams.stats / KStarParams.stats): kStatsWords u64, zeroed by the prologue,
@@ -206,6 +210,27 @@ struct KFxSplit {
 // that the kernel arguments of every other instance stay what they were.
 struct KParamsFx : KParams {
   KFxSplit fx;
+};
+
+// DISTINCTCOUNT aggregations of a plan (at most kMaxDistinct distinct columns): aggregation d's side bitmap holds
+// num_keys_total x words[d] 64-bit words at bits[d], words[d] = ceil(card / 64) over the plan's snapshot of the column's
+// global dictionary; bit (gid & 63) of word key * words[d] + (gid >> 6) = group `key` saw global dictId gid.  col[d]:
+// the column's record index (its KCol carries the local -> global mapping: lut, or id + lut_off); slot[d]: its row.
+// Zeroed on the stream before every execution, written with atomicOr only, read by distinct_popcount_kernel.
+constexpr int kMaxDistinct = 8;
+constexpr int64_t kDistinctMaxBytes = int64_t(1) << 30;  // side bitmaps of one plan, at most
+struct KDistinct {
+  unsigned long long* bits[kMaxDistinct];
+  int32_t words[kMaxDistinct];
+  int32_t col[kMaxDistinct];
+  int32_t slot[kMaxDistinct];
+  int32_t n;
+  int32_t pad;
+};
+// The parameters of the scan's DC instances (filter_groupby_dc_kernel): KParams and the side bitmaps.  A type of its
+// own, as KParamsFx is: the kernel arguments of every other instance stay what they were.
+struct KParamsDc : KParams {
+  KDistinct dc;
 };
 
 // leaf_masks_kernel work item: groups [group0, group0 + 256) of plan record `rec`; its leaves' masks go to
@@ -414,11 +439,16 @@ int launch_expand_tiles(const uint8_t* segs, int32_t seg_stride, int32_t num_seg
                         uint64_t deadline, unsigned long long* stats, void* stream);
 // variant: 0 sparse instance, 1 dense, 2 dense "simple" (no LUT / dictionary gathers, no double sums), 3 - 5 the
 // sparse specialisations (k_direct.hip); 6 / 7: the sparse / dense instance of plans with SLOT_SUM_FX slots
-// (k_direct_fx.hip)
-constexpr int kVariantFxSparse = 6, kVariantFxDense = 7;
+// (k_direct_fx.hip); 8 / 9: the sparse / dense instance of plans with SLOT_DISTINCT slots (k_direct_dc.hip)
+constexpr int kVariantFxSparse = 6, kVariantFxDense = 7, kVariantDcSparse = 8, kVariantDcDense = 9;
 int launch_filter_groupby(const KParams& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
 // The FX instances (variant kVariantFxSparse / kVariantFxDense).
 int launch_filter_groupby_fx(const KParamsFx& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
+// The DC instances (variant kVariantDcSparse / kVariantDcDense; MODE_LDS and MODE_GLOBAL only).
+int launch_filter_groupby_dc(const KParamsDc& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
+// Row dc.slot[d] of table [num_slots][num_keys] <- per key the popcount of its words[d] bitmap words (0 where the
+// key's COUNT, row 0, is 0), for every d.
+int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_keys, void* stream);
 // Resident workgroups per CU of the direct kernel instance (< 0: query failed).
 int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes);
 int launch_reduce_slabs(const uint64_t* slab, const int32_t* slot_kind_dev, int32_t num_slots, int64_t num_keys,

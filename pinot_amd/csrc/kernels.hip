@@ -831,6 +831,11 @@ PGPU_MODE_DECLS(0)
 PGPU_MODE_DECLS(1)
 PGPU_MODE_DECLS(2)
 #undef PGPU_MODE_DECLS
+// The instances for plans with SLOT_DISTINCT slots (k_direct_dc.hip: dense key spaces, -DPGPU_MODE=0,1).
+int launch_direct_dc_mode0(const KParamsDc& p, int variant, int grid, size_t lds_bytes, void* stream);
+int launch_direct_dc_mode1(const KParamsDc& p, int variant, int grid, size_t lds_bytes, void* stream);
+int occupancy_direct_dc_mode0(int variant, size_t lds_bytes);
+int occupancy_direct_dc_mode1(int variant, size_t lds_bytes);
 
 int launch_startree_scan(const KStarParams& p, int mode, bool fx, size_t lds_bytes, void* stream) {
   switch (mode) {
@@ -857,7 +862,53 @@ int launch_filter_groupby_fx(const KParamsFx& p, int mode, int variant, int grid
   }
 }
 
+int launch_filter_groupby_dc(const KParamsDc& p, int mode, int variant, int grid, size_t lds_bytes, void* stream) {
+  if (variant != kVariantDcSparse && variant != kVariantDcDense) return -1;
+  if (p.dc.n < 0 || p.dc.n > kMaxDistinct) return -1;
+  switch (mode) {
+    case MODE_LDS: return launch_direct_dc_mode0(p, variant, grid, lds_bytes, stream);
+    case MODE_GLOBAL: return launch_direct_dc_mode1(p, variant, grid, lds_bytes, stream);
+    default: return -1;  // hash-mode plans with DISTINCTCOUNT are declined at plan time
+  }
+}
+
+// DISTINCTCOUNT's final step: one wave per key, its lanes striding the key's words[d] bitmap words -- per lane popcounts,
+// a wave reduction, one store of the count into the aggregation's row.  A key without docs (COUNT 0) stores 0 without
+// reading its words.  Bytes: G x W x 8 read (present keys), G x 8 written, per aggregation.
+__global__ __launch_bounds__(256) void distinct_popcount_kernel(const KDistinct dc, uint64_t* __restrict__ table,
+                                                                int64_t num_keys) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t key = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); key < num_keys; key += nwaves) {
+    const bool present = table[key] != 0;  // the COUNT row: wave-uniform
+    for (int d = 0; d < dc.n; ++d) {
+      const int64_t W = dc.words[d];
+      int64_t c = 0;
+      if (present) {
+        const unsigned long long* __restrict__ row = dc.bits[d] + key * W;
+        for (int64_t w = lane; w < W; w += 64) c += __popcll(row[w]);
+      }
+      c = wave_sum_i64(c);
+      if (lane == 0) table[(int64_t)dc.slot[d] * num_keys + key] = (uint64_t)c;
+    }
+  }
+}
+
+int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_keys, void* stream) {
+  if (dc.n <= 0 || num_keys <= 0) return 0;
+  if (dc.n > kMaxDistinct) return -1;
+  for (int d = 0; d < dc.n; ++d)
+    if (dc.slot[d] <= 0 || dc.slot[d] >= kMaxSlots || dc.words[d] <= 0 || !dc.bits[d]) return -1;
+  int64_t grid = (num_keys + 3) / 4;
+  if (grid > 16384) grid = 16384;
+  hipLaunchKernelGGL(distinct_popcount_kernel, dim3((unsigned)grid), dim3(256), 0, S(stream), dc, table, num_keys);
+  return PGPU_HIP_OK(hipGetLastError());
+}
+
 int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes) {
+  if (variant >= kVariantDcSparse)
+    return mode == MODE_LDS ? occupancy_direct_dc_mode0(variant, lds_bytes)
+           : mode == MODE_GLOBAL ? occupancy_direct_dc_mode1(variant, lds_bytes) : -1;
   const bool fx = variant >= kVariantFxSparse;
   switch (mode) {
     case MODE_LDS: return fx ? occupancy_direct_fx_mode0(variant, lds_bytes) : occupancy_direct_mode0(variant, lds_bytes);

@@ -477,6 +477,7 @@ struct Scratch {
   DevBuf xsend, xrecv, xshard;          // pgpu_plan_combine: exported / received records, the reduce-scattered shard
   DevBuf hsort;                         // hash-mode finalize: the decoded columns / compact form
   DevBuf part_mm;                       // hashed partitions: each partition's slot ranges (KPartParams.out_mm)
+  DevBuf dc_bits;                       // DISTINCTCOUNT: the side bitmaps of the plan's aggregations, back to back
   HostPinned xstage;                    // their initial values (pinned: the upload is asynchronous)
   // Pinned staging: `stage` is the source of the execution's asynchronous uploads (records, bitsets); `readback`
   // receives finalize's copies.  Separate buffers, because a finalize that had to grow the upload buffer would
@@ -496,7 +497,7 @@ struct Scratch {
     for (const DevBuf* b : {&docbits, &bittasks, &bitblocks, &rawtasks, &segrec, &sets, &slab, &table, &hash_keys,
                             &stats, &ckeys, &cslots, &counter, &bitmap, &tile_seg, &starrec, &starwork, &part_start,
                             &block_off, &rec_key, &rec_val, &rec_key32, &stage_keys, &coarse_fill, &fine_fill,
-                            &mid_key, &mid_val, &leap_maps, &mask_jobs, &leaf_masks, &hsort, &part_mm})
+                            &mid_key, &mid_val, &leap_maps, &mask_jobs, &leaf_masks, &hsort, &part_mm, &dc_bits})
       n += b->cap;
     return n;
   }
@@ -517,6 +518,7 @@ struct Scratch {
     coarse_fill.release(); fine_fill.release(); mid_key.release(); mid_val.release();
     leap_maps.release(); mask_jobs.release(); leaf_masks.release(); maskstage.release();
     xcursor.release(); xstage.release(); xsend.release(); xrecv.release(); xshard.release(); hsort.release(); part_mm.release();
+    dc_bits.release();
     for (auto& e : ev) if (e) { hipEventDestroy(e); e = nullptr; }
   }
 };
@@ -679,6 +681,16 @@ struct pgpu_plan_s {
   std::vector<pgpu::FxFormat> slot_fmt;
   std::vector<Segment*> fx_scope;
   std::vector<pgpu::FxAgree> fx_ranges;
+  // DISTINCTCOUNT aggregations, one entry per distinct column (the aggregations of a column share it): its row of the
+  // group table (slot_kind says SLOT_SUM_I64: after distinct_popcount_kernel the row holds the int64 counts; the DC
+  // scan instances alone see SLOT_DISTINCT), its table and query column, the size of the plan's snapshot of the
+  // column's global dictionary and the bitmap words per key, ceil(card / 64).  slot_dc: per slot its entry, -1 for
+  // every other slot.  dc_lut: [segment][entry] the local -> global dictId mapping as planned (under the table mutex,
+  // with card), as key_lut is for the group-by columns.
+  struct Distinct { int32_t slot = 0, tcol = 0, qcol = 0; int64_t card = 0, words = 0; };
+  std::vector<Distinct> dc;
+  std::vector<int32_t> slot_dc;
+  std::vector<KeyLut> dc_lut;
   std::vector<int32_t> agg_fn, agg_slot, agg_col;   // per aggregation: fn, value slot (or -1), table column
   int num_projected = 0;
   // per-segment compiled data
@@ -837,6 +849,26 @@ inline bool result_has_fx(const pgpu_result_s* r) {
   return false;
 }
 inline bool result_fx_local(const pgpu_result_s* r) { return !r->fx_agreed && result_has_fx(r); }
+// Plans / results with DISTINCTCOUNT aggregations.  Every cross-GPU or external-merge entry point declines them
+// (distinct_decline): a rank's counts do not add, and merging the side bitmaps by OR across ranks is not built.
+inline bool query_has_distinct(const pgpu_query* q) {
+  for (int i = 0; q && q->aggs && i < q->num_aggs; ++i)
+    if (q->aggs[i].fn == PGPU_AGG_DISTINCTCOUNT) return true;
+  return false;
+}
+inline bool plan_has_distinct(const pgpu_plan_s* P) {
+  if (!P->dc.empty()) return true;
+  for (const auto& part : P->parts)
+    if (part.plan && !part.plan->dc.empty()) return true;
+  return false;
+}
+inline bool result_has_distinct(const pgpu_result_s* r) {
+  return std::find(r->agg_fn.begin(), r->agg_fn.end(), (int32_t)PGPU_AGG_DISTINCTCOUNT) != r->agg_fn.end();
+}
+inline int distinct_decline(const char* what) {
+  return fail(PGPU_ERR_UNSUPPORTED, "%s with DISTINCTCOUNT: per-rank distinct counts do not add (the value sets would "
+                         "have to be merged)", what);
+}
 inline int fx_decline(const char* what) {
   return fail(PGPU_ERR_UNSUPPORTED, "%s with PGPU_OPT_EXACT_FP_SUM: the ranks would have to agree on the "
                          "fixed-point format (E, K, W) first", what);
@@ -911,6 +943,7 @@ int sorted_search(const std::vector<T>& a, T v) {
 
 struct ExecCtx {
   KParams kp;
+  KDistinct dc{};  // the side bitmaps of the plan's DISTINCTCOUNT aggregations (n = 0: none)
   // PGPU_TRACE=1: host time marks of the execution, printed when it took over a millisecond
   std::vector<std::pair<const char*, double>> marks;
   void mark(const char* what) { if (trace_on()) marks.emplace_back(what, now_us()); }

@@ -364,10 +364,37 @@ static void fill_kparams(const pgpu_plan_s* P, uint64_t deadline, ExecCtx& X) {
   for (int sl = 0; sl < nslots; ++sl) { kp.slot_kind[sl] = P->slot_kind[sl]; kp.slot_col[sl] = P->slot_col[sl]; }
   for (int sl = 0; sl < nslots && P->fx; ++sl)  // the scan's view of the fixed-point digits (fx_split has the rest)
     if (P->slot_fx[sl] >= 0) kp.slot_kind[sl] = SLOT_SUM_FX;
+  for (const pgpu_plan_s::Distinct& d : P->dc) kp.slot_kind[d.slot] = SLOT_DISTINCT;  // (X.dc has the bitmaps)
   kp.pair_leaves = 1;
   dense_lds_forms(P, &kp.pack_slot, &kp.narrow);
   kp.pack_shift = P->pack_shift;
   kp.stats = P->d_stats;
+}
+
+// DISTINCTCOUNT: the aggregations' side bitmaps (X.dc), back to back in the arena's buffer and zeroed on the stream
+// for this execution.
+static int exec_distinct_bitmaps(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
+  memset(&X.dc, 0, sizeof X.dc);
+  if (P->dc.empty()) return 0;
+  if (P->mode == MODE_HASH || (int)P->dc.size() > kMaxDistinct)
+    return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT outside the dense group tables");
+  Scratch* sc = P->scratch;
+  int64_t words = 0;
+  for (const pgpu_plan_s::Distinct& d : P->dc) words += P->num_keys * d.words;
+  if (words * 8 > kDistinctMaxBytes) return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT bitmaps above the cap");
+  TRY(sc->dc_bits.ensure((size_t)words * 8));
+  HIP_TRY(hipMemsetAsync(sc->dc_bits.p, 0, (size_t)words * 8, stream));
+  int64_t off = 0;
+  X.dc.n = (int32_t)P->dc.size();
+  for (size_t i = 0; i < P->dc.size(); ++i) {
+    const pgpu_plan_s::Distinct& d = P->dc[i];
+    X.dc.bits[i] = sc->dc_bits.as<unsigned long long>() + off;
+    X.dc.words[i] = (int32_t)d.words;
+    X.dc.col[i] = d.qcol;
+    X.dc.slot[i] = d.slot;
+    off += P->num_keys * d.words;
+  }
+  return 0;
 }
 
 // The accumulators: LEAP2 maps, the slabs of an LDS-table plan, or the global / hash table (initialised here) with
@@ -410,7 +437,7 @@ static int exec_tables(pgpu_plan_s* P, hipStream_t stream, int max_chunks, ExecC
       return fail(PGPU_ERR_DEVICE, "table init launch failed: %s", hipGetErrorString(hipGetLastError()));
     kp.table = table;
   }
-  return 0;
+  return exec_distinct_bitmaps(P, stream, X);
 }
 
 int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chunks, ExecCtx& X) {
@@ -516,6 +543,7 @@ KFxSplit fx_split(const pgpu_plan_s* P) {
 }
 
 int scan_variant(const pgpu_plan_s* P) {
+  if (!P->dc.empty()) return P->dense ? kVariantDcDense : kVariantDcSparse;  // plans with DISTINCTCOUNT: theirs
   if (P->fx) return P->dense ? kVariantFxDense : kVariantFxSparse;  // plans with SLOT_SUM_FX slots: their own instances
   return P->dense_simple ? 2 : P->dense ? 1 : P->pair_variant ? 3 : P->fast_wide ? 5 : P->fast_variant ? 4 : 0;
 }
@@ -785,7 +813,12 @@ static int launch_scan_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, KPa
   P->last_scan.alone = P->alone;
   P->last_scan.declined = !fits;
   int rc;
-  if (P->fx) {  // the FX instances: the launch's parameters and the split of the fixed-point slots
+  if (!P->dc.empty()) {  // the DC instances: the launch's parameters and the side bitmaps
+    KParamsDc kd;
+    static_cast<KParams&>(kd) = kp;
+    kd.dc = X.dc;
+    rc = launch_filter_groupby_dc(kd, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
+  } else if (P->fx) {  // the FX instances: the launch's parameters and the split of the fixed-point slots
     KParamsFx kf;
     static_cast<KParams&>(kf) = kp;
     kf.fx = fx_split(P);
@@ -981,6 +1014,9 @@ int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
   if (P->mode == MODE_HASH && !P->part_hash && kp.pack_slot >= 0 &&
       launch_hash_unpack(X.table, kp.hash_keys, P->num_keys, kp.pack_slot, kp.pack_shift, stream))
     return fail(PGPU_ERR_DEVICE, "hash unpack launch failed: %s", hipGetErrorString(hipGetLastError()));
+  // DISTINCTCOUNT: the table is whole (slabs folded) -- its rows take the per-key popcounts of the side bitmaps
+  if (X.dc.n > 0 && launch_distinct_popcount(X.dc, X.table, P->num_keys, stream))
+    return fail(PGPU_ERR_DEVICE, "distinct popcount launch failed: %s", hipGetErrorString(hipGetLastError()));
   if (X.leap_nsegs > 0 &&  // deferred but no fold ran (cannot happen for a plan with scan tiles; kept exact)
       launch_leap2_compose(X.leap_segs, P->seg_stride, X.leap_nsegs, kp.leap_maps, kp.stats, stream))
     return fail(PGPU_ERR_DEVICE, "filter statistics launch failed: %s", hipGetErrorString(hipGetLastError()));

@@ -421,6 +421,7 @@ void describe_result(const pgpu_plan_s* P, pgpu_result_s* R) {
   for (int a = 0; a < na; ++a) {
     const int fn = P->agg_fn[a];
     if (fn == PGPU_AGG_COUNT) continue;  // CountAggregationFunction: exact count (held as double by Pinot)
+    if (fn == PGPU_AGG_DISTINCTCOUNT) continue;  // the set's size (DistinctCountAggregationFunction.extractFinalResult)
     if (fn == PGPU_AGG_SUM || fn == PGPU_AGG_AVG)
       R->agg_conv[a] = P->slot_kind[P->agg_slot[a]] == SLOT_SUM_I64 ? RCONV_I64 : RCONV_F64;
     else

@@ -630,6 +630,7 @@ int32_t pack_slot_for(const pgpu_table_s* t, const pgpu_plan_s* P, const pgpu_qu
     const int c = P->slot_tcol[sl];
     if (P->slot_kind[sl] != SLOT_SUM_I64 || c < 0 || c == kDocIdColumn || !is_int_type(t->types[c])) continue;
     if (P->slot_fx[sl] >= 0) continue;  // a fixed-point digit (of an integer column past int_sum_fits): signed
+    if (P->slot_dc[sl] >= 0) continue;  // a DISTINCTCOUNT row: written after the scan, never added to
     const IntRange r = int_column_range(P->segs, c);
     if (r.known && r.lo <= r.hi && r.lo >= 0 && (long double)max_count * (long double)r.hi < ldexpl(1.0L, shift))
       return (int32_t)sl;

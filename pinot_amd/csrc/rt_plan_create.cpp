@@ -20,6 +20,7 @@ struct PlanCtx {
   bool star_allowed = false, exempt_kind = false, minmax_kind = false, any_star = false, any_inv = false;
   std::vector<int> qcol_key;   // per query column: its group-by key index (-1: none)
   std::vector<char> qcol_val;  // ... and whether an accumulator reads its values
+  std::vector<int> qcol_dc;    // ... and its DISTINCTCOUNT entry (pgpu_plan_s::dc; -1: none)
   std::vector<int> perm;       // order_leaves: evaluation position -> predicate
   double t_start = 0, tr[8] = {0};  // trace marks
   int ntr = 0;
@@ -154,14 +155,30 @@ void push_slot(pgpu_plan_s* P, int kind, int tcol, int fx_digit, const FxFormat&
   P->slot_col.push_back(tcol == -1 ? 0 : query_col(P, tcol));
   P->slot_fx.push_back(fx_digit);
   P->slot_fmt.push_back(fmt);
+  P->slot_dc.push_back(-1);
 }
 
 // The slot of (kind, tcol), shared by the aggregations that need the same one.
 int add_slot(pgpu_plan_s* P, int kind, int tcol) {
   for (size_t s = 1; s < P->slot_kind.size(); ++s)
-    if (P->slot_kind[s] == kind && P->slot_tcol[s] == tcol && P->slot_fx[s] < 0) return (int)s;
+    if (P->slot_kind[s] == kind && P->slot_tcol[s] == tcol && P->slot_fx[s] < 0 && P->slot_dc[s] < 0) return (int)s;
   push_slot(P, kind, tcol, -1, FxFormat{});
   return (int)P->slot_kind.size() - 1;
+}
+
+// The row of DISTINCTCOUNT(tcol), shared by the aggregations of the column: an ordinary row of the group table that
+// starts at 0 and that the scan never touches -- SLOT_SUM_I64 to everything but the DC scan instances (rt.h dc).
+int add_distinct_slot(pgpu_plan_s* P, int tcol) {
+  for (const pgpu_plan_s::Distinct& d : P->dc)
+    if (d.tcol == tcol) return d.slot;
+  push_slot(P, SLOT_SUM_I64, tcol, -1, FxFormat{});
+  pgpu_plan_s::Distinct d;
+  d.slot = (int32_t)P->slot_kind.size() - 1;
+  d.tcol = tcol;
+  d.qcol = P->slot_col[d.slot];
+  P->slot_dc[d.slot] = (int32_t)P->dc.size();
+  P->dc.push_back(d);
+  return d.slot;
 }
 
 // The W digit slots of a fixed-point sum: adjacent, of the one column, shared by SUM and AVG of the column.
@@ -253,6 +270,15 @@ int assign_slots(PlanCtx& cx) {
     P->agg_col.push_back(a.column);
     if (a.fn == PGPU_AGG_COUNT) { P->agg_slot.push_back(0); continue; }
     if (a.column < 0 || a.column >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: bad column", i);
+    if (a.fn == PGPU_AGG_DISTINCTCOUNT) {  // any column type: the set is over dictIds
+      if (q->options & PGPU_OPT_EXACT_FP_SUM)
+        return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT with PGPU_OPT_EXACT_FP_SUM");
+      for (const Segment* s : P->segs)
+        if (s->cols[a.column].raw)
+          return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT over raw (no-dictionary) column %d", a.column);
+      P->agg_slot.push_back(add_distinct_slot(P, a.column));
+      continue;
+    }
     if (cx.t->types[a.column] == PGPU_STRING) return fail(PGPU_ERR_UNSUPPORTED, "numeric aggregation over a STRING column");
     int slot = 0;
     TRY(agg_slot_for(cx, i, &slot));
@@ -269,6 +295,15 @@ int assign_slots(PlanCtx& cx) {
       P->cfg.partitioned_group_by = 0;
       P->cfg.hash_partitions = 0;
     }
+    P->cfg.stream_chunks = 1;
+  }
+  if (!P->dc.empty()) {
+    // as a plain plan with fixed-point sums: the scan kernel's LDS / global tables, one launch
+    if ((int)P->dc.size() > kMaxDistinct)
+      return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT over more than %d columns in one query", kMaxDistinct);
+    if (P->first_doc_slot) return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT in a numGroupsLimit (composite) plan");
+    P->cfg.partitioned_group_by = 0;
+    P->cfg.hash_partitions = 0;
     P->cfg.stream_chunks = 1;
   }
   if ((int)P->slot_kind.size() > kMaxSlots) return fail(PGPU_ERR_UNSUPPORTED, "too many accumulators");
@@ -309,8 +344,10 @@ int plan_segment_arrays(PlanCtx& cx) {
   pgpu_plan_s* P = cx.P;
   const hipStream_t stream = t->stream;
   const size_t nk = P->key_cols.size();
+  const size_t nd = P->dc.size();
   P->key_lut.resize(P->segs.size() * nk);
-  P->refs->luts.reserve(P->segs.size() * nk);
+  P->dc_lut.resize(P->segs.size() * nd);
+  P->refs->luts.reserve(P->segs.size() * (nk + nd));
   for (size_t i = 0; i < P->segs.size(); ++i) {
     Segment* s = P->segs[i];
     for (size_t j = 0; j < nk; ++j) {
@@ -323,9 +360,21 @@ int plan_segment_arrays(PlanCtx& cx) {
       kl.off = col.lut_off;
     }
     for (size_t k = 1; k < P->slot_kind.size(); ++k)
-      if (P->slot_tcol[k] != kDocIdColumn) TRY(ensure_values(t, *s, P->slot_tcol[k], stream));
+      if (P->slot_tcol[k] != kDocIdColumn && P->slot_dc[k] < 0) TRY(ensure_values(t, *s, P->slot_tcol[k], stream));
     if (P->first_doc_slot) TRY(ensure_docid(t, s->num_docs, stream));
   }
+  // the distinct columns' local -> global mapping, as a key column's (after the key LUTs: plan_star_segment indexes
+  // refs->luts by segment and key)
+  for (size_t i = 0; i < P->segs.size(); ++i)
+    for (size_t d = 0; d < nd; ++d) {
+      const int c = P->dc[d].tcol;
+      TRY(ensure_lut(t, *P->segs[i], c, stream));
+      const Column& col = P->segs[i]->cols[c];
+      P->refs->luts.push_back(col.lut);
+      KeyLut& kl = P->dc_lut[i * nd + d];
+      kl.lut = col.lut_off >= 0 ? nullptr : reinterpret_cast<const int32_t*>(col.lut->p);
+      kl.off = col.lut_off;
+    }
   return 0;
 }
 
@@ -337,6 +386,7 @@ int plan_global_values(PlanCtx& cx) {
   P->val_cols.clear();
   for (size_t k = 1; k < P->slot_kind.size(); ++k) {
     const int c = P->slot_tcol[k];
+    if (P->slot_dc[k] >= 0) continue;  // a DISTINCTCOUNT row reads no values
     if (c == kDocIdColumn || std::find(P->val_cols.begin(), P->val_cols.end(), c) != P->val_cols.end()) continue;
     bool any = false;
     for (Segment* s : P->segs) {
@@ -382,6 +432,10 @@ int build_device_arrays(PlanCtx& cx) {
   for (size_t j = 0; j < nk; ++j) {
     P->key_dicts[j] = t->global[P->key_cols[j]];
     cx.gcard[j] = (int64_t)P->key_dicts[j]->size();
+  }
+  for (pgpu_plan_s::Distinct& d : P->dc) {  // the bitmap's width: the snapshot the LUTs taken below map into
+    d.card = std::max<int64_t>((int64_t)t->global[d.tcol]->size(), 1);
+    d.words = (d.card + 63) / 64;
   }
   TRY(plan_segment_arrays(cx));
   TRY(plan_global_values(cx));
@@ -566,6 +620,22 @@ void choose_table_mode(PlanCtx& cx) {
   }
 }
 
+// DISTINCTCOUNT plans: dense key spaces only (the bitmap rows are indexed by the composite key), and side bitmaps of at
+// most kDistinctMaxBytes in all.
+int check_distinct_shape(const PlanCtx& cx) {
+  const pgpu_plan_s* P = cx.P;
+  if (P->dc.empty()) return 0;
+  if (P->mode == MODE_HASH)
+    return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT over a key space that takes the hash table (%s)",
+                P->stage_end.empty() ? "past 2^26 keys" : "ARRAY_MAP stages");
+  long double bytes = 0;
+  for (const pgpu_plan_s::Distinct& d : P->dc) bytes += (long double)P->num_keys * (long double)d.words * 8.0L;
+  if (bytes > (long double)kDistinctMaxBytes)
+    return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT bitmaps of %.0Lf bytes (%lld keys), above the cap of %lld", bytes,
+                (long long)P->num_keys, (long long)kDistinctMaxBytes);
+  return 0;
+}
+
 // What the per-segment translation reads besides the plan: the record stride, the parsed literals, the star-tree
 // composites, which aggregation-only answers skip the post-filter scan, and the roles of the query columns.
 int prepare_translation(PlanCtx& cx) {
@@ -580,16 +650,19 @@ int prepare_translation(PlanCtx& cx) {
   cx.parsed.resize(P->num_leaves);
   for (int l = 0; l < P->num_leaves; ++l)
     TRY(parse_predicate(t->types[q->predicates[l].column], q->predicates[l], &cx.parsed[l]));
+  // (DISTINCTCOUNT: StarTreeUtils finds no function-column pair for it -- such a plan scans)
   cx.star_allowed = q->num_group_by > 0 && !(q->options & PGPU_OPT_NO_STAR_TREE) && P->stage_end.empty() &&
-                    star_composites(P->ops, q, &cx.star_comps);
-  // Aggregation-only over a match-all segment: COUNT-only is answered from metadata, MIN/MAX-only from the
-  // dictionaries (AggregationPlanNode.java:165-183) -- same values, numEntriesScannedPostFilter 0
+                    P->dc.empty() && star_composites(P->ops, q, &cx.star_comps);
+  // Aggregation-only over a match-all segment: COUNT-only is answered from metadata, MIN / MAX / DISTINCTCOUNT-only
+  // from the dictionaries (AggregationPlanNode.java:165-183, isFitForDictionaryBasedPlan :233-246; every dictionary
+  // value occurs in its segment, so the scan gives the same set) -- same values, numEntriesScannedPostFilter 0
   // (MetadataBasedAggregationOperator.java:89-92, DictionaryBasedAggregationOperator.java:171-173).
   if (q->num_group_by == 0 && q->num_aggs > 0) {
     bool all_count = true, all_minmax = true;
     for (int i = 0; i < q->num_aggs; ++i) {
       all_count &= q->aggs[i].fn == PGPU_AGG_COUNT;
-      all_minmax &= q->aggs[i].fn == PGPU_AGG_MIN || q->aggs[i].fn == PGPU_AGG_MAX;
+      all_minmax &= q->aggs[i].fn == PGPU_AGG_MIN || q->aggs[i].fn == PGPU_AGG_MAX ||
+                    q->aggs[i].fn == PGPU_AGG_DISTINCTCOUNT;
     }
     cx.exempt_kind = all_count || all_minmax;
     cx.minmax_kind = all_minmax && !all_count;
@@ -605,7 +678,10 @@ int prepare_translation(PlanCtx& cx) {
   for (size_t j = 0; j < P->key_cols.size(); ++j)
     for (size_t i = 0; i < P->query_cols.size(); ++i)
       if (P->query_cols[i] == P->key_cols[j]) cx.qcol_key[i] = (int)j;
-  for (size_t k = 1; k < P->slot_col.size(); ++k) cx.qcol_val[P->slot_col[k]] = 1;
+  for (size_t k = 1; k < P->slot_col.size(); ++k)
+    if (P->slot_dc[k] < 0) cx.qcol_val[P->slot_col[k]] = 1;
+  cx.qcol_dc.assign(P->query_cols.size(), -1);
+  for (size_t d = 0; d < P->dc.size(); ++d) cx.qcol_dc[P->dc[d].qcol] = (int)d;
   return 0;
 }
 
@@ -751,6 +827,10 @@ bool fill_kcols(const PlanCtx& cx, size_t i, KCol* kc) {
         const KeyLut& kl = P->key_lut[i * P->key_cols.size() + cx.qcol_key[j]];
         kc[j].lut = kl.lut;
         kc[j].lut_off = kl.off;
+      } else if (cx.qcol_dc[j] >= 0) {  // DISTINCTCOUNT column: the same mapping (of the same dictionary snapshot)
+        const KeyLut& kl = P->dc_lut[i * P->dc.size() + cx.qcol_dc[j]];
+        kc[j].lut = kl.lut;
+        kc[j].lut_off = kl.off;
       }
       if (cx.qcol_val[j]) {  // accumulator operand: value arrays, built once (ensure_values) and never replaced
         kc[j].dkey = c->key_affine ? nullptr : c->d_key;
@@ -769,7 +849,8 @@ bool fill_kcols(const PlanCtx& cx, size_t i, KCol* kc) {
         }
       }
     }
-    gathers |= (cx.qcol_key[j] >= 0 && kc[j].lut != nullptr) || (cx.qcol_val[j] && kc[j].dkey != nullptr);
+    gathers |= ((cx.qcol_key[j] >= 0 || cx.qcol_dc[j] >= 0) && kc[j].lut != nullptr) ||
+               (cx.qcol_val[j] && kc[j].dkey != nullptr);
   }
   return gathers;
 }
@@ -974,7 +1055,7 @@ void configure_scan_grid(PlanCtx& cx, int64_t tile_base) {
   bool f64 = false;
   for (int k : P->slot_kind) f64 |= k == SLOT_SUM_F64;
   // (a streamed plan configures before its later chunks are planned: never simple)
-  P->dense_simple = P->dense && !P->gathers && !f64 && !P->fx && P->tile_bound == 0;
+  P->dense_simple = P->dense && !P->gathers && !f64 && !P->fx && P->dc.empty() && P->tile_bound == 0;
   // the sparse instance with the index + scan pair: two-leaf AND plans with an in-place index leaf
   P->pair_variant = !P->dense && P->pure_and && P->num_leaves == 2 && P->leaf_kinds[LEAF_BITDIR] > 0;
   P->fast_variant = !P->dense && !P->pair_variant && P->pure_and && P->num_leaves <= kFastLeaves;
@@ -1279,6 +1360,7 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
   TRY(restrict_key_space(cx, &kspan));
   TRY(layout_keys(cx, kspan));
   choose_table_mode(cx);
+  TRY(check_distinct_shape(cx));
   TRY(prepare_translation(cx));
   order_leaves(cx);
   const bool partitions = part_eligible(P, cx.nslots, cx.G);

@@ -52,7 +52,9 @@ __device__ __forceinline__ uint32_t leap2_entries(uint8_t* __restrict__ maps, in
 // C3, where that path is rare, 1.5 % -- 710 -> 722 us -- and the dense instance's C2 2 %).
 // FX: the instances of plans with fixed-point FLOAT / DOUBLE sums (SLOT_SUM_FX slots, fx_sum.h) -- kernels of their
 // own (filter_groupby_fx_kernel, k_direct_fx.hip, with KParamsFx), so the others keep their registers and arguments.
-// The two kernels share their body as text (scan_direct_body.inc): a body function inlined into both changed the
+// DC: the instances of plans with DISTINCTCOUNT aggregations (SLOT_DISTINCT slots and their side bitmaps) -- kernels of
+// their own again (filter_groupby_dc_kernel, k_direct_dc.hip, with KParamsDc).
+// The kernels share their body as text (scan_direct_body.inc): a body function inlined into them changed the
 // scalar register allocation of the existing instances.
 #ifndef PGPU_MIN_WAVES
 #define PGPU_MIN_WAVES 1
@@ -65,14 +67,22 @@ __device__ __forceinline__ uint32_t leap2_entries(uint8_t* __restrict__ maps, in
 #endif
 template <int MODE, bool DENSE, bool SIMPLE = false, bool PAIR = false, bool FAST = false, int LANE_BATCH = 2>
 __global__ __launch_bounds__(kBlock, DENSE ? (SIMPLE ? PGPU_SIMPLE_MIN_WAVES : PGPU_DENSE_MIN_WAVES) : PGPU_MIN_WAVES) void filter_groupby_kernel(const KParams p) {
-  constexpr bool FX = false;
+  constexpr bool FX = false, DC = false;
 #include "scan_direct_body.inc"
 }
 
 // The sparse (general filter programs and pure-AND ones alike) and the dense instance for plans with SLOT_SUM_FX slots.
 template <int MODE, bool DENSE>
 __global__ __launch_bounds__(kBlock, DENSE ? PGPU_DENSE_MIN_WAVES : PGPU_MIN_WAVES) void filter_groupby_fx_kernel(const KParamsFx p) {
-  constexpr bool FX = true, SIMPLE = false, PAIR = false, FAST = false;
+  constexpr bool FX = true, DC = false, SIMPLE = false, PAIR = false, FAST = false;
+  constexpr int LANE_BATCH = 2;
+#include "scan_direct_body.inc"
+}
+
+// The sparse and the dense instance for plans with SLOT_DISTINCT slots (DISTINCTCOUNT): MODE_LDS and MODE_GLOBAL.
+template <int MODE, bool DENSE>
+__global__ __launch_bounds__(kBlock, DENSE ? PGPU_DENSE_MIN_WAVES : PGPU_MIN_WAVES) void filter_groupby_dc_kernel(const KParamsDc p) {
+  constexpr bool FX = false, DC = true, SIMPLE = false, PAIR = false, FAST = false;
   constexpr int LANE_BATCH = 2;
 #include "scan_direct_body.inc"
 }

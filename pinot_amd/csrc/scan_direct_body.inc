@@ -1,5 +1,6 @@
 // scan_direct_body.inc -- the body of the fused scan kernels (scan_direct.h), included into filter_groupby_kernel and
-// filter_groupby_fx_kernel: `p` is the kernel's parameter block; MODE, DENSE, SIMPLE, PAIR, FAST, LANE_BATCH and FX are
+// filter_groupby_fx_kernel and filter_groupby_dc_kernel: `p` is the kernel's parameter block; MODE, DENSE, SIMPLE, PAIR,
+// FAST, LANE_BATCH, FX and DC are
 // the including kernel's template parameters or constants.
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -175,7 +176,7 @@
       }
       if (DENSE && MODE != MODE_HASH && wave_cnt >= (uint32_t)kDenseGroupMin) {
         // dense tile: whole-group decode of the group-by / aggregated columns
-        aggregate_group<MODE, SIMPLE, FX>(p, S, gclamp, mask, tbl, G);
+        aggregate_group<MODE, SIMPLE, FX, DC>(p, S, gclamp, mask, tbl, G);
       } else if (__any(cnt > 2u)) {
         // dense: the lane's own 32-doc group, LANE_BATCH matched docs per batch (the lines are already cached)
         constexpr int LB = LANE_BATCH;
@@ -191,7 +192,7 @@
           SegView SS[LB];
 #pragma unroll
           for (int b = 0; b < LB; ++b) SS[b] = S;
-          aggregate_batch<MODE, LB, SIMPLE, FX>(p, SS, doc, ok, tbl, G);
+          aggregate_batch<MODE, LB, SIMPLE, FX, DC>(p, SS, doc, ok, tbl, G);
         }
       } else if (__any(mask != 0u)) {
         // sparse: append to the wave's queue (<= 2 per lane, so <= 128 per tile), aggregate in batches
@@ -208,7 +209,7 @@
           qn += (uint32_t)__popcll(bal);
         }
         if (qn >= (uint32_t)kFlushAt) {
-          flush_wave_queue<MODE, SIMPLE, FX>(p, wq, wqs, qn, lane, tbl, G);
+          flush_wave_queue<MODE, SIMPLE, FX, DC>(p, wq, wqs, qn, lane, tbl, G);
           qn = 0;
         }
       }
@@ -234,7 +235,7 @@
     t_end = c0 + p.claim_tiles < T ? c0 + p.claim_tiles : T;
     t_step = 1;
   }
-  if (qn) flush_wave_queue<MODE, SIMPLE, FX>(p, wq, wqs, qn, lane, tbl, G);
+  if (qn) flush_wave_queue<MODE, SIMPLE, FX, DC>(p, wq, wqs, qn, lane, tbl, G);
 #ifdef PGPU_DIAG_WG_TIMES
   diag_t1 = wall_clock64();
 #endif

@@ -19,11 +19,18 @@ from . import _lib as L
 EQ, NOT_EQ, IN, NOT_IN, RANGE = "EQ", "NOT_EQ", "IN", "NOT_IN", "RANGE"
 UNBOUNDED = "*"  # RangePredicate.UNBOUNDED
 _PRED_CODE = {EQ: L.PRED_EQ, NOT_EQ: L.PRED_NOT_EQ, IN: L.PRED_IN, NOT_IN: L.PRED_NOT_IN, RANGE: L.PRED_RANGE}
-AGG_FUNCTIONS = {"COUNT": L.AGG_COUNT, "SUM": L.AGG_SUM, "MIN": L.AGG_MIN, "MAX": L.AGG_MAX, "AVG": L.AGG_AVG}
+AGG_FUNCTIONS = {"COUNT": L.AGG_COUNT, "SUM": L.AGG_SUM, "MIN": L.AGG_MIN, "MAX": L.AGG_MAX, "AVG": L.AGG_AVG,
+                 "DISTINCTCOUNT": L.AGG_DISTINCTCOUNT}
 DEFAULT_NUM_GROUPS_LIMIT = 100000  # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT (:70)
 DEFAULT_LIMIT = 10  # QueryContext default LIMIT / TOP
 DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE = 5000  # InstancePlanMakerImplV2.DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE
 DEFAULT_GROUP_TRIM_THRESHOLD = 1000000  # InstancePlanMakerImplV2.DEFAULT_GROUPBY_TRIM_THRESHOLD
+
+
+def function_name(fn):
+    """An aggregation function's canonical name: upper case, underscores dropped (DISTINCT_COUNT = DISTINCTCOUNT), as
+    AggregationFunctionType.getAggregationFunctionType normalises it."""
+    return fn.upper().replace("_", "")
 
 
 class Predicate:
@@ -109,7 +116,7 @@ class QueryContext:
         self.sql_group_by = sql_group_by
         self.use_star_tree = use_star_tree  # debug option useStarTree (StarTreeUtils.java:51-59)
         self.group_by = list(group_by)
-        self.aggregations = [(fn.upper(), col) for fn, col in aggregations]
+        self.aggregations = [(function_name(fn), col) for fn, col in aggregations]
         self.num_groups_limit = num_groups_limit
         # SQL-mode parts (QueryContext.getSelectExpressions / getOrderByExpressions / getLimit): the SELECT list as
         # ('col', name) / ('agg', FN, col), ORDER BY as [(expr, ascending)], LIMIT; the combine's trim options
@@ -136,7 +143,7 @@ class QueryContext:
         (1, aggregation position)."""
         if expr[0] == "col":
             return L.ORDER_GROUP_BY, self.group_by.index(expr[1])
-        return L.ORDER_AGGREGATION, self.aggregations.index((expr[1].upper(), expr[2]))
+        return L.ORDER_AGGREGATION, self.aggregations.index((function_name(expr[1]), expr[2]))
 
     def sql_trim_c(self):
         """The SQL-mode combine / reduce options as pgpu_sql_trim (keepalive, struct)."""
@@ -295,7 +302,7 @@ class _Parser:
     def select_list_item(self):
         tok = self.peek()
         if tok[0] == "id" and self.peek(1) == ("op", "("):
-            fn = self.take("id").upper()
+            fn = function_name(self.take("id"))
             self.take("op", "(")
             col = "*" if self.peek() == ("op", "*") else None
             if col:
