@@ -219,10 +219,15 @@ typedef struct {
  * Declined with PGPU_ERR_UNSUPPORTED (the message names DISTINCTCOUNT): side bitmaps (keys x ceil(cardinality / 64)
  * x 8 bytes per distinct column) above 1 GiB in one plan; key spaces that take the hash table (past 2^26 keys, or
  * ARRAY_MAP stages); numGroupsLimit plans that split per segment; a raw (no-dictionary) column; more than 8 distinct
- * columns; the combination with PGPU_OPT_EXACT_FP_SUM; every cross-GPU or external-merge entry point
- * (pgpu_plan_combine*, pgpu_plan_exchange_*, pgpu_plan_finalize_range, an external d_table,
- * pgpu_result_exchange_rows / merge_rows / combine_rows: per-rank counts do not add) and pgpu_result_datatable (Pinot
- * ships the value set as an OBJECT). */
+ * columns; the combination with PGPU_OPT_EXACT_FP_SUM; pgpu_result_datatable (Pinot ships the value set as an
+ * OBJECT); and, because per-rank counts do not add, every cross-GPU or external-merge entry point but one:
+ * pgpu_plan_exchange_*, pgpu_plan_finalize_range, an external d_table (execute, finalize, pgpu_plan_combine),
+ * pgpu_result_exchange_rows / merge_rows / combine_rows, and a pgpu_plan_combine_mode whose ranks do not agree on a
+ * dense mode (they would meet as rows).
+ * Across GPUs: pgpu_plan_combine_mode / pgpu_plan_combine merge it in PGPU_COMBINE_ALL_REDUCE and
+ * PGPU_COMBINE_REDUCE_SCATTER on the plan's own table (d_table NULL), as DistinctCountAggregationFunction.merge does
+ * (the union of the sets) -- see pgpu_plan_combine.  The ranks union the dictionaries of the distinct columns, like
+ * those of the group-by columns, first (pgpu_table_add_dictionary_values): bit i must mean one value everywhere. */
 enum pgpu_agg_fn { PGPU_AGG_COUNT = 0, PGPU_AGG_SUM = 1, PGPU_AGG_MIN = 2, PGPU_AGG_MAX = 3, PGPU_AGG_AVG = 4,
                    PGPU_AGG_DISTINCTCOUNT = 5 };
 typedef struct {
@@ -417,13 +422,29 @@ int pgpu_comm_recreate(pgpu_comm comm, const void* id);
  * segments), and in kinds[num_slots] the slot kinds the merge runs in (an int64 SUM travels as float64 when another
  * rank's sum of the slot is float64).  Modes that differ between ranks fall back to ROWS, which merges any plan
  * kind.  PGPU_ERR_INVALID_ARGUMENT when the ranks' group-by dictionaries differ (pgpu_table_add_dictionary_values
- * with the union first).  The caller may reuse the answer for every later query of the same shape. */
+ * with the union first), and likewise -- the message names DISTINCTCOUNT and the column -- when their snapshots of a
+ * DISTINCTCOUNT column's global dictionary differ.  A plan with DISTINCTCOUNT whose ranks do not agree on ALL_REDUCE or
+ * REDUCE_SCATTER is declined (PGPU_ERR_UNSUPPORTED: its rows do not merge).  The caller may reuse the answer for every
+ * later query of the same shape. */
 int pgpu_plan_combine_mode(pgpu_plan plan, pgpu_comm comm, int64_t shard_bytes, int32_t* mode, int32_t* kinds);
 /* Collective, ordered on `stream`: merges the executed plan's table (d_table as given to execute, NULL = the plan's
  * own) with the other ranks' in `mode` (ALL_REDUCE, REDUCE_SCATTER or HASH).  For REDUCE_SCATTER, d_shard (NULL = the
  * plan's scratch) receives [num_slots][key_count] words, key_begin / key_count say which keys; they are 0 / num_keys
  * otherwise.  pgpu_plan_finalize(plan, stream, d_table) then returns this rank's share of the merged groups (all of
- * them for ALL_REDUCE; disjoint shares otherwise). */
+ * them for ALL_REDUCE; disjoint shares otherwise).
+ * PGPU_AGG_DISTINCTCOUNT (ALL_REDUCE and REDUCE_SCATTER, d_table NULL; a caller table is declined as at execute): the
+ * sets merge by OR, which no collective offers, so the side bitmaps are reduce-scattered by key range first.  With
+ * chunk = ceil(num_keys / nranks), rank r owns keys [min(num_keys, r*chunk), min(num_keys, (r+1)*chunk)) -- the
+ * REDUCE_SCATTER split.  A bitmap is key-major, so per distinct column one all-to-all sends each peer its range's
+ * rows straight from the bitmap; the owner ORs the nranks blocks into its own rows, stores their popcounts into the
+ * aggregation's row of the table and zeroes that row outside its range.  The int64 SUM of the all-reduce /
+ * reduce-scatter that follows then yields the merged count on every rank (in the owner's shard).  Memory: the
+ * receive area holds nranks x (owned keys) x ceil(cardinality / 64) x 8 bytes per distinct column -- about the side
+ * bitmaps (at most 1 GiB per plan) once more; link bytes: (nranks - 1) / nranks of the rank's bitmaps sent, on top of
+ * the table's collectives.  The receive area is allocated before any collective and the ranks exchange their status
+ * once (a host round trip only plans with DISTINCTCOUNT pay), so a rank that fails there fails with its peers.
+ * Afterwards the rank holds the merged value *sets* of its own key range only (the counts are in the table); nothing
+ * returns the sets yet.  With one rank the same code runs and gives the local answer. */
 int pgpu_plan_combine(pgpu_plan plan, pgpu_comm comm, void* stream, void* d_table, int32_t mode, const int32_t* kinds,
                       void* d_shard, int64_t* key_begin, int64_t* key_count);
 /* Collective, ROWS mode: the finalized result's rows split by owner, exchanged, merged by the owner as the broker

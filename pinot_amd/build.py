@@ -26,7 +26,7 @@ SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTI
     [("k_direct_dc.hip", ["-DPGPU_MODE=%d" % m], "k_direct_dc_%d" % m) for m in range(2)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "scan_direct_body.inc", "part_aggregate_body.inc",
            "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
@@ -200,6 +200,11 @@ def build_fx_sum_check(force=False):
 def build_fx_agree_check(force=False):
     """The cross-rank agreement on the fixed-point format (fx_sum.h)."""
     return _build_header_check("fx_agree_check", "fx_agree_check.cpp", "fx_sum.h", force)
+
+
+def build_key_range_check(force=False):
+    """The key range a rank owns in the dense cross-GPU combine (key_range.h)."""
+    return _build_header_check("key_range_check", "key_range_check.cpp", "key_range.h", force)
 
 
 if __name__ == "__main__":

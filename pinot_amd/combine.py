@@ -373,7 +373,8 @@ class Communicator:
 
 
 def union_dictionaries_comm(table, columns, comm):
-    """union_dictionaries over a pgpu_comm (values travel as JSON: exact for ints, floats via repr, and strings)."""
+    """union_dictionaries over a pgpu_comm (values travel as JSON: exact for ints, floats via repr, and strings).
+    Pass the DISTINCTCOUNT columns of the queries along with the group-by columns: their sets merge by dictId."""
     import json
     for col in columns:
         mine = json.dumps(list(table.dictionary(col))).encode()
@@ -382,7 +383,8 @@ def union_dictionaries_comm(table, columns, comm):
 
 
 def combine_mode(plan, comm, shard_bytes):
-    """(mode, kinds) every rank agrees on for this query (pgpu_plan_combine_mode, a collective)."""
+    """(mode, kinds) every rank agrees on for this query (pgpu_plan_combine_mode, a collective).  Plans with
+    DISTINCTCOUNT pass in the dense modes (combine_plan on the plan's own table then merges the sets)."""
     mode = ctypes.c_int32()
     kinds = (ctypes.c_int32 * 32)()
     L.check(plan.lib.pgpu_plan_combine_mode(plan.handle, comm.handle, int(shard_bytes), ctypes.byref(mode), kinds))

@@ -1,5 +1,6 @@
 // abi_combine.cpp -- C ABI: the cross-GPU exchange, row merges, communicator, combine.
 #include "rt_decls.h"
+#include "key_range.h"
 
 extern "C" {
 
@@ -485,8 +486,28 @@ uint64_t plan_fx_digest(const pgpu_plan_s* K) {
   return fx_digest(K->agg_slot, fx);
 }
 
+// The DISTINCTCOUNT columns of a plan: per column (aggregation order) its row, its snapshot of the column's global
+// dictionary (size and values) and the bitmap words per key.  Ranks whose digests differ would OR bits that mean
+// different values.  0: no such column.
+uint64_t distinct_column_digest(const pgpu_plan_s::Distinct& d) {
+  uint64_t h = 0x9ce484222325cbf2ull;
+  auto mix = [&h](uint64_t v) { h = (h ^ v) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; };
+  mix((uint64_t)d.slot);
+  mix(d.dict ? dict_digest(*d.dict) : 0);
+  mix((uint64_t)d.words);
+  return h ? h : 1;
+}
+uint64_t distinct_digest(const pgpu_plan_s* P) {
+  if (P->dc.empty()) return 0;
+  uint64_t h = 0xf29ce484222325cbull;
+  auto mix = [&h](uint64_t v) { h = (h ^ v) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; };
+  mix(P->dc.size());
+  for (const pgpu_plan_s::Distinct& d : P->dc) mix(distinct_column_digest(d));
+  return h ? h : 1;
+}
+
 // One rank's part of the mode agreement (int64 words).
-enum { CI_MODE = 0, CI_KEYS, CI_SLOTS, CI_DIGEST, CI_FX, CI_KINDS, CI_WORDS = CI_KINDS + kMaxSlots };
+enum { CI_MODE = 0, CI_KEYS, CI_SLOTS, CI_DIGEST, CI_FX, CI_DC, CI_KINDS, CI_WORDS = CI_KINDS + kMaxSlots };
 
 // Agreed kinds of ranks' slots: equal, or int64 / float64 sums of one slot meeting as float64.
 int agree_kinds(const std::vector<int64_t>& all, int nranks, int ns, int32_t* kinds) {
@@ -532,13 +553,93 @@ int agree_status(pgpu::Comm* C, int rc) {
   const int64_t mine = rc;
   return agree_status_with(C, rc, &mine, 8, all.data());
 }
+
+// DISTINCTCOUNT in the mode agreement: `all` holds every rank's CI_* words.  Equal CI_DC words pass.  Otherwise every
+// rank sees the mismatch (the words are the same on all of them) and meets in one more exchange, of the per-column
+// digests, that finds the column to name.
+int agree_distinct_dictionaries(const pgpu_plan_s* P, pgpu::Comm* C, const std::vector<int64_t>& all) {
+  const int N = C->nranks;
+  bool differ = false;
+  for (int r = 0; r < N; ++r) differ |= all[(size_t)r * CI_WORDS + CI_DC] != all[(size_t)C->rank * CI_WORDS + CI_DC];
+  if (!differ) return 0;
+  std::vector<int64_t> mine(1 + kMaxDistinct, 0), cols((size_t)N * (1 + kMaxDistinct), 0);
+  mine[0] = (int64_t)P->dc.size();
+  for (size_t d = 0; d < P->dc.size() && d < (size_t)kMaxDistinct; ++d)
+    mine[1 + d] = (int64_t)distinct_column_digest(P->dc[d]);
+  {
+    DeviceGuard g(C->device);
+    TRY(C->allgather_host(mine.data(), mine.size() * 8, cols.data()));
+  }
+  for (int r = 0; r < N; ++r) {
+    const int64_t* w = cols.data() + (size_t)r * (1 + kMaxDistinct);
+    if (w[0] != mine[0])
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "rank %d's query has %lld DISTINCTCOUNT columns, rank %d's %lld", r,
+                  (long long)w[0], C->rank, (long long)mine[0]);
+    for (size_t d = 0; d < P->dc.size(); ++d)
+      if (w[1 + d] != mine[1 + d]) {
+        const int col = P->dc[d].tcol;
+        return fail(PGPU_ERR_INVALID_ARGUMENT, "DISTINCTCOUNT over column %d (%s): rank %d's global dictionary differs "
+                    "from rank %d's: union the dictionaries of the distinct columns too "
+                    "(pgpu_table_add_dictionary_values) before the query", col,
+                    col >= 0 && col < (int)P->table->names.size() ? P->table->names[col].c_str() : "?", r, C->rank);
+      }
+  }
+  return fail(PGPU_ERR_INVALID_ARGUMENT, "ranks disagree on the DISTINCTCOUNT columns of the query");
+}
+
+// DISTINCTCOUNT in the dense combine modes, before the table's own collectives.  The sets merge by OR, which no
+// collective offers, and an all-gather of whole bitmaps would cost nranks times their memory: the bitmaps are
+// reduce-scattered by key range instead.  A bitmap is key-major, so the rows of rank p's range `owned_key_range(G, N,
+// p)` are one contiguous block and rank order is key order -- one all-to-all per distinct column, sent straight from
+// the bitmap into sc->dc_recv (nranks blocks of own.count x words[d] words; at most about the bitmaps' size again,
+// nranks x ceil(G / nranks) x W x 8 bytes per column).  distinct_merge_popcount_kernel ORs the blocks into this rank's
+// bitmap rows of its range and stores their popcounts into the aggregation's row; the row outside the range is zeroed.
+// Every key's merged count is then non-zero on one rank only, and the int64 SUM the row takes in the all-reduce /
+// reduce-scatter that follows yields it everywhere (its owner's shard).  Afterwards this rank holds the merged sets of
+// its own key range only.
+int combine_distinct_bitmaps(pgpu_plan_s* P, pgpu::Comm* C, Scratch* sc, uint64_t* table, const pgpu::KeyRange& own,
+                             hipStream_t s) {
+  const int N = C->nranks;
+  const int64_t G = P->num_keys;
+  KDistinct kd;
+  KDistinctRecv rv;
+  memset(&kd, 0, sizeof kd);
+  memset(&rv, 0, sizeof rv);
+  std::vector<int64_t> scount(N), rcount(N);
+  unsigned long long* bits = sc->dc_bits.as<unsigned long long>();
+  unsigned long long* recv = sc->dc_recv.as<unsigned long long>();
+  kd.n = (int32_t)P->dc.size();
+  for (size_t i = 0; i < P->dc.size(); ++i) {
+    const pgpu_plan_s::Distinct& d = P->dc[i];
+    for (int p = 0; p < N; ++p) {
+      scount[p] = pgpu::owned_key_range(G, N, p).count * d.words;
+      rcount[p] = own.count * d.words;
+    }
+    TRY(C->alltoallv(bits, scount.data(), recv, rcount.data(), 8, s));
+    kd.bits[i] = bits;
+    kd.words[i] = (int32_t)d.words;
+    kd.col[i] = d.qcol;
+    kd.slot[i] = d.slot;
+    rv.recv[i] = recv;
+    bits += G * d.words;
+    recv += (int64_t)N * own.count * d.words;
+  }
+  if (launch_distinct_merge_popcount(kd, rv, table, G, own.begin, own.count, N, s))
+    return fail(PGPU_ERR_DEVICE, "distinct merge launch failed: %s", hipGetErrorString(hipGetLastError()));
+  const int64_t end = own.begin + own.count;
+  for (const pgpu_plan_s::Distinct& d : P->dc) {  // the counts of the peers' keys: theirs to contribute
+    uint64_t* row = table + (size_t)d.slot * G;
+    if (own.begin > 0) HIP_TRY(hipMemsetAsync(row, 0, (size_t)own.begin * 8, s));
+    if (end < G) HIP_TRY(hipMemsetAsync(row + end, 0, (size_t)(G - end) * 8, s));
+  }
+  return 0;
+}
 }  // namespace
 
 int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_t* mode, int32_t* kinds) try {
   PGPU_ABI_GUARD;
   if (!P || !c || !mode) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
-  if (plan_has_distinct(P)) return distinct_decline("a cross-GPU combine");  // (every rank's query carries the function)
   pgpu::CommWaitScope wait_limits(P->end_time_ms, &P->cancel);
   const int N = c->impl->nranks;
   int local;
@@ -558,6 +659,7 @@ int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_
   mine[CI_SLOTS] = (int64_t)K->slot_kind.size();
   mine[CI_DIGEST] = (int64_t)key_space_digest(K, local != PGPU_COMBINE_ROWS);
   mine[CI_FX] = (int64_t)plan_fx_digest(K);
+  mine[CI_DC] = (int64_t)distinct_digest(P);
   for (size_t s = 0; s < K->slot_kind.size() && s < (size_t)kMaxSlots; ++s) mine[CI_KINDS + s] = K->slot_kind[s];
   {
     DeviceGuard g(c->impl->device);
@@ -595,6 +697,9 @@ int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_
         return fail(PGPU_ERR_INVALID_ARGUMENT, "rank %d's group-by dictionaries differ from rank %d's: union them "
                     "(pgpu_table_add_dictionary_values) before the query", r, c->impl->rank);
   }
+  // DISTINCTCOUNT: bit i of a set must mean one value on every rank; the sets merge in the dense modes only
+  TRY(agree_distinct_dictionaries(P, c->impl.get(), all));
+  if (agreed == PGPU_COMBINE_ROWS && plan_has_distinct(P)) return distinct_decline("a cross-GPU combine of rows");
   if (kinds) TRY(agree_kinds(all, N, (int)mine[CI_SLOTS], kinds));
   *mode = agreed;
   return 0;
@@ -605,7 +710,8 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   PGPU_ABI_GUARD;
   if (!P || !c) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
-  if (plan_has_distinct(P)) return distinct_decline("a cross-GPU combine");  // (every rank's query carries the function)
+  // DISTINCTCOUNT: the side bitmaps belong to the plan's own table (a caller table is declined at execute already)
+  if (d_table && plan_has_distinct(P)) return distinct_decline("external table");  // (every rank passes one or none)
   P->k8d_counts = false;
   if (mode == PGPU_COMBINE_LOCAL) {
     if (key_begin) *key_begin = 0;
@@ -626,7 +732,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   // host exchange (one would cost every query a round trip): a failed rank issues no collective, its peers' ones stay
   // pending on their streams, and their finalize waits end at the query deadline or the communicator's timeout,
   // which aborts the communicator -- for a query without a deadline at most kDenseCombineWaitMs (wait_plan), not the
-  // communicator's whole timeout.
+  // communicator's whole timeout.  (A dense plan with DISTINCTCOUNT does have one, before its bitmap all-to-all.)
   uint32_t conv = 0;
   int pre = 0;
   if (P->composite) pre = fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit plan: combine its finalized rows (ROWS)");
@@ -639,7 +745,9 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   else if (mode != PGPU_COMBINE_HASH && P->hash)
     pre = fail(PGPU_ERR_UNSUPPORTED, "hash-mode tables merge with PGPU_COMBINE_HASH");
   if (!pre) pre = check_kinds(P->slot_kind, kinds, &conv);
-  if (mode != PGPU_COMBINE_HASH && pre) return pre;
+  // (its failed rank meets its peers there)
+  const bool dc = mode != PGPU_COMBINE_HASH && !P->dc.empty();
+  if (mode != PGPU_COMBINE_HASH && pre && !dc) return pre;
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
   Scratch* sc = P->scratch;
@@ -669,8 +777,25 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
     return 0;
   }
   uint64_t* table = reinterpret_cast<uint64_t*>(d_table ? d_table : const_cast<void*>(P->d_table_used));
-  if (!table) return fail(PGPU_ERR_INVALID_ARGUMENT, "no group table");
   const int64_t G = P->num_keys;
+  const pgpu::KeyRange own = pgpu::owned_key_range(G, N, me);
+  if (dc) {
+    // The bitmap all-to-all needs room for the peers' rows of this rank's key range.  Allocated before any collective,
+    // then one host exchange that only plans with DISTINCTCOUNT pay: a rank that cannot allocate (or failed its checks)
+    // fails together with its peers instead of leaving them waiting in the all-to-all.
+    int rc = pre;
+    if (!rc && !table) rc = fail(PGPU_ERR_INVALID_ARGUMENT, "no group table");
+    if (!rc) {
+      int64_t words = 0;
+      for (const pgpu_plan_s::Distinct& d : P->dc) words += (int64_t)N * own.count * d.words;
+      rc = sc->dc_recv.ensure((size_t)std::max<int64_t>(words, 1) * 8);
+    }
+    TRY(agree_status(C, rc));
+    P->comm_used = c->impl;
+    P->comm_dense = true;
+    TRY(combine_distinct_bitmaps(P, C, sc, table, own, s));
+  }
+  if (!table) return fail(PGPU_ERR_INVALID_ARGUMENT, "no group table");
   for (int k = 0; k < ns; ++k)
     if ((conv >> k) & 1u)
       if (launch_i64_to_f64(table + (size_t)k * G, G, s))
@@ -698,9 +823,8 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
     return 0;
   }
   // REDUCE_SCATTER: rank r keeps keys [r*chunk, (r+1)*chunk) -- half an all-reduce's link bytes, 1/N of the finalize
-  const int64_t chunk = (G + N - 1) / N;
-  const int64_t begin = std::min<int64_t>(G, (int64_t)me * chunk);
-  const int64_t count = std::min<int64_t>(G, begin + chunk) - begin;
+  // (owned_key_range: the split the DISTINCTCOUNT bitmaps were merged by above)
+  const int64_t chunk = own.chunk, begin = own.begin, count = own.count;
   uint64_t* shard = reinterpret_cast<uint64_t*>(d_shard);
   if (!shard) {
     TRY(sc->xshard.ensure((size_t)ns * std::max<int64_t>(chunk, 1) * 8 + 64));

@@ -216,7 +216,9 @@ struct KParamsFx : KParams {
 // num_keys_total x words[d] 64-bit words at bits[d], words[d] = ceil(card / 64) over the plan's snapshot of the column's
 // global dictionary; bit (gid & 63) of word key * words[d] + (gid >> 6) = group `key` saw global dictId gid.  col[d]:
 // the column's record index (its KCol carries the local -> global mapping: lut, or id + lut_off); slot[d]: its row.
-// Zeroed on the stream before every execution, written with atomicOr only, read by distinct_popcount_kernel.
+// Zeroed on the stream before every execution, written with atomicOr only, read by distinct_popcount_kernel; a
+// cross-GPU combine then overwrites the rows of this rank's key range with the ranks' merged sets
+// (distinct_merge_popcount_kernel).
 constexpr int kMaxDistinct = 8;
 constexpr int64_t kDistinctMaxBytes = int64_t(1) << 30;  // side bitmaps of one plan, at most
 struct KDistinct {
@@ -226,6 +228,11 @@ struct KDistinct {
   int32_t slot[kMaxDistinct];
   int32_t n;
   int32_t pad;
+};
+// What the bitmap all-to-all of a cross-GPU combine received, per distinct column: nranks blocks of (owned keys x
+// words[d]) words, block p = rank p's rows of this rank's key range (distinct_merge_popcount_kernel).
+struct KDistinctRecv {
+  const unsigned long long* recv[kMaxDistinct];
 };
 // The parameters of the scan's DC instances (filter_groupby_dc_kernel): KParams and the side bitmaps.  A type of its
 // own, as KParamsFx is: the kernel arguments of every other instance stay what they were.
@@ -449,6 +456,10 @@ int launch_filter_groupby_dc(const KParamsDc& p, int mode, int variant, int grid
 // Row dc.slot[d] of table [num_slots][num_keys] <- per key the popcount of its words[d] bitmap words (0 where the
 // key's COUNT, row 0, is 0), for every d.
 int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_keys, void* stream);
+// The cross-rank merge of keys [begin, begin + count): bitmap rows <- the OR of the nranks received blocks (rv), row
+// dc.slot[d] <- the popcount of the merged rows, with no gate on the COUNT row.  count 0 launches nothing.
+int launch_distinct_merge_popcount(const KDistinct& dc, const KDistinctRecv& rv, uint64_t* table, int64_t num_keys,
+                                   int64_t begin, int64_t count, int nranks, void* stream);
 // Resident workgroups per CU of the direct kernel instance (< 0: query failed).
 int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes);
 int launch_reduce_slabs(const uint64_t* slab, const int32_t* slot_kind_dev, int32_t num_slots, int64_t num_keys,

@@ -905,6 +905,50 @@ int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_k
   return PGPU_HIP_OK(hipGetLastError());
 }
 
+// DISTINCTCOUNT across ranks (pgpu_plan_combine): the merge of the sets of this rank's key range [begin, begin +
+// count).  recv[d] holds nranks blocks of count x words[d] words, block p = rank p's bitmap rows of that range (the
+// bitmap all-to-all).  One wave per owned key, its lanes striding the key's words[d]: a lane ORs the nranks received
+// words, stores the merged word into this rank's bitmap at the key's place (the rank then holds the merged sets of
+// its range) and popcounts it; a wave reduction, one store of the count into the aggregation's row.  No gate on the
+// COUNT row: the table is not merged yet, and a key without a local doc can have docs on a peer.  Streaming, no LDS.
+// Bytes per aggregation: nranks x count x W x 8 read, count x W x 8 + count x 8 written.
+__global__ __launch_bounds__(256) void distinct_merge_popcount_kernel(const KDistinct dc, const KDistinctRecv rv,
+                                                                      uint64_t* __restrict__ table, int64_t num_keys,
+                                                                      int64_t begin, int64_t count, int nranks) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t k = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); k < count; k += nwaves) {
+    for (int d = 0; d < dc.n; ++d) {
+      const int64_t W = dc.words[d];
+      const int64_t block = count * W;  // one rank's words of this range
+      const unsigned long long* __restrict__ in = rv.recv[d] + k * W;
+      unsigned long long* __restrict__ row = dc.bits[d] + (begin + k) * W;
+      int64_t c = 0;
+      for (int64_t w = lane; w < W; w += 64) {
+        unsigned long long m = 0;
+        for (int p = 0; p < nranks; ++p) m |= in[(int64_t)p * block + w];
+        row[w] = m;
+        c += __popcll(m);
+      }
+      c = wave_sum_i64(c);
+      if (lane == 0) table[(int64_t)dc.slot[d] * num_keys + begin + k] = (uint64_t)c;
+    }
+  }
+}
+
+int launch_distinct_merge_popcount(const KDistinct& dc, const KDistinctRecv& rv, uint64_t* table, int64_t num_keys,
+                                   int64_t begin, int64_t count, int nranks, void* stream) {
+  if (dc.n <= 0 || count <= 0) return 0;
+  if (dc.n > kMaxDistinct || nranks <= 0 || begin < 0 || begin + count > num_keys || !table) return -1;
+  for (int d = 0; d < dc.n; ++d)
+    if (dc.slot[d] <= 0 || dc.slot[d] >= kMaxSlots || dc.words[d] <= 0 || !dc.bits[d] || !rv.recv[d]) return -1;
+  int64_t grid = (count + 3) / 4;
+  if (grid > 16384) grid = 16384;
+  hipLaunchKernelGGL(distinct_merge_popcount_kernel, dim3((unsigned)grid), dim3(256), 0, S(stream), dc, rv, table,
+                     num_keys, begin, count, nranks);
+  return PGPU_HIP_OK(hipGetLastError());
+}
+
 int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes) {
   if (variant >= kVariantDcSparse)
     return mode == MODE_LDS ? occupancy_direct_dc_mode0(variant, lds_bytes)

@@ -478,6 +478,7 @@ struct Scratch {
   DevBuf hsort;                         // hash-mode finalize: the decoded columns / compact form
   DevBuf part_mm;                       // hashed partitions: each partition's slot ranges (KPartParams.out_mm)
   DevBuf dc_bits;                       // DISTINCTCOUNT: the side bitmaps of the plan's aggregations, back to back
+  DevBuf dc_recv;                       // its cross-GPU combine: the peers' bitmap rows of this rank's key range
   HostPinned xstage;                    // their initial values (pinned: the upload is asynchronous)
   // Pinned staging: `stage` is the source of the execution's asynchronous uploads (records, bitsets); `readback`
   // receives finalize's copies.  Separate buffers, because a finalize that had to grow the upload buffer would
@@ -497,7 +498,7 @@ struct Scratch {
     for (const DevBuf* b : {&docbits, &bittasks, &bitblocks, &rawtasks, &segrec, &sets, &slab, &table, &hash_keys,
                             &stats, &ckeys, &cslots, &counter, &bitmap, &tile_seg, &starrec, &starwork, &part_start,
                             &block_off, &rec_key, &rec_val, &rec_key32, &stage_keys, &coarse_fill, &fine_fill,
-                            &mid_key, &mid_val, &leap_maps, &mask_jobs, &leaf_masks, &hsort, &part_mm, &dc_bits})
+                            &mid_key, &mid_val, &leap_maps, &mask_jobs, &leaf_masks, &hsort, &part_mm, &dc_bits, &dc_recv})
       n += b->cap;
     return n;
   }
@@ -519,6 +520,7 @@ struct Scratch {
     leap_maps.release(); mask_jobs.release(); leaf_masks.release(); maskstage.release();
     xcursor.release(); xstage.release(); xsend.release(); xrecv.release(); xshard.release(); hsort.release(); part_mm.release();
     dc_bits.release();
+    dc_recv.release();
     for (auto& e : ev) if (e) { hipEventDestroy(e); e = nullptr; }
   }
 };
@@ -686,8 +688,13 @@ struct pgpu_plan_s {
   // scan instances alone see SLOT_DISTINCT), its table and query column, the size of the plan's snapshot of the
   // column's global dictionary and the bitmap words per key, ceil(card / 64).  slot_dc: per slot its entry, -1 for
   // every other slot.  dc_lut: [segment][entry] the local -> global dictId mapping as planned (under the table mutex,
-  // with card), as key_lut is for the group-by columns.
-  struct Distinct { int32_t slot = 0, tcol = 0, qcol = 0; int64_t card = 0, words = 0; };
+  // with card), as key_lut is for the group-by columns.  dict: that snapshot -- the ranks of a cross-GPU combine must
+  // hold the same one, or a bit means different values on different ranks (pgpu_plan_combine_mode compares digests).
+  struct Distinct {
+    int32_t slot = 0, tcol = 0, qcol = 0;
+    int64_t card = 0, words = 0;
+    std::shared_ptr<const Dict> dict;
+  };
   std::vector<Distinct> dc;
   std::vector<int32_t> slot_dc;
   std::vector<KeyLut> dc_lut;
@@ -849,8 +856,9 @@ inline bool result_has_fx(const pgpu_result_s* r) {
   return false;
 }
 inline bool result_fx_local(const pgpu_result_s* r) { return !r->fx_agreed && result_has_fx(r); }
-// Plans / results with DISTINCTCOUNT aggregations.  Every cross-GPU or external-merge entry point declines them
-// (distinct_decline): a rank's counts do not add, and merging the side bitmaps by OR across ranks is not built.
+// Plans / results with DISTINCTCOUNT aggregations.  A rank's counts do not add: the dense modes of pgpu_plan_combine
+// on the plan's own table merge the side bitmaps by OR (a bitmap all-to-all by key range, abi_combine.cpp); every
+// other cross-GPU or external-merge entry point declines them (distinct_decline).
 inline bool query_has_distinct(const pgpu_query* q) {
   for (int i = 0; q && q->aggs && i < q->num_aggs; ++i)
     if (q->aggs[i].fn == PGPU_AGG_DISTINCTCOUNT) return true;

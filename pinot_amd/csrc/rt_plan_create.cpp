@@ -434,7 +434,8 @@ int build_device_arrays(PlanCtx& cx) {
     cx.gcard[j] = (int64_t)P->key_dicts[j]->size();
   }
   for (pgpu_plan_s::Distinct& d : P->dc) {  // the bitmap's width: the snapshot the LUTs taken below map into
-    d.card = std::max<int64_t>((int64_t)t->global[d.tcol]->size(), 1);
+    d.dict = t->global[d.tcol];
+    d.card = std::max<int64_t>((int64_t)d.dict->size(), 1);
     d.words = (d.card + 63) / 64;
   }
   TRY(plan_segment_arrays(cx));
