@@ -50,7 +50,7 @@ int pgpu_plan_scan_geometry(pgpu_plan P, int64_t* out16) try {
   out16[12] = L.tiles;
   out16[13] = L.alone ? 1 : 0;
   out16[14] = L.declined ? 1 : 0;
-  out16[15] = scan_variant(P);
+  out16[15] = P->variant;
   return 0;
 } PGPU_ABI_CATCH
 

@@ -240,6 +240,53 @@ struct KParamsDc : KParams {
   KDistinct dc;
 };
 
+// The instances of the fused scan kernel (scan_direct.h), one row of kScanInstances each.  The number is what a plan
+// reports as its instance (word 15 of pgpu_plan_scan_geometry), so a row keeps its place.
+//   0 sparse        any filter program, matched docs aggregated in per-lane batches
+//   1 dense         whole-group decode of dense tiles (plans of estimated selectivity >= dense_selectivity)
+//   2 dense simple  the dense one without LUT / dictionary gathers and double sums (aggregate_batch's SIMPLE)
+//   3 pair          the sparse one with the index + scan pair (bitdir_range): two-leaf ANDs with an in-place index leaf
+//   4 fast          the sparse one for pure-AND plans of <= kFastLeaves leaves (no general filter evaluator)
+//   5 fast wide     that one with 4-doc lane batches (plans of estimated selectivity >= 1/16)
+//   6, 7 FX         the sparse / dense instance of plans with SLOT_SUM_FX slots (filter_groupby_fx_kernel)
+//   8, 9 DC         the sparse / dense instance of plans with SLOT_DISTINCT slots (filter_groupby_dc_kernel); such
+//                   plans have dense key spaces, so there is none in MODE_HASH
+enum ScanVariant : int32_t { kScanSparse = 0, kScanDense, kScanDenseSimple, kScanPair, kScanFast, kScanFastWide,
+                             kScanFxSparse, kScanFxDense, kScanDcSparse, kScanDcDense };
+constexpr int kScanVariants = 10;
+// The kernel template of an instance, i.e. the parameter block it takes: KParams, KParamsFx, KParamsDc.
+enum ScanFamily : int32_t { SCAN_BASE = 0, SCAN_FX = 1, SCAN_DC = 2 };
+struct ScanInstance {
+  ScanFamily family;
+  uint32_t modes;                  // bit m: the instance exists in accumulator mode m
+  bool dense, simple, pair, fast;  // the template arguments (the FX and DC kernels take DENSE alone)
+  int lane_batch;
+};
+constexpr uint32_t kScanAllModes = 1u << MODE_LDS | 1u << MODE_GLOBAL | 1u << MODE_HASH;
+constexpr ScanInstance kScanInstances[kScanVariants] = {
+    {SCAN_BASE, kScanAllModes, false, false, false, false, 2},              // kScanSparse
+    {SCAN_BASE, kScanAllModes, true, false, false, false, 2},               // kScanDense
+    {SCAN_BASE, kScanAllModes, true, true, false, false, 2},                // kScanDenseSimple
+    {SCAN_BASE, kScanAllModes, false, false, true, false, 2},               // kScanPair
+    {SCAN_BASE, kScanAllModes, false, false, false, true, 2},               // kScanFast
+    {SCAN_BASE, kScanAllModes, false, false, false, true, 4},               // kScanFastWide
+    {SCAN_FX, kScanAllModes, false, false, false, false, 2},                // kScanFxSparse
+    {SCAN_FX, kScanAllModes, true, false, false, false, 2},                 // kScanFxDense
+    {SCAN_DC, 1u << MODE_LDS | 1u << MODE_GLOBAL, false, false, false, false, 2},  // kScanDcSparse
+    {SCAN_DC, 1u << MODE_LDS | 1u << MODE_GLOBAL, true, false, false, false, 2},   // kScanDcDense
+};
+
+// A kernel as its object hands it out: the host pointer hipLaunchKernel / the occupancy query take, and its block size.
+struct KernelEntry {
+  const void* fn;
+  int block;
+};
+// One object per (kernel, family, mode): k_direct.hip (the scan) and k_startree.hip (the star-tree document scan)
+// compiled with -DPGPU_FAMILY=f -DPGPU_MODE=m.  Each exports one function, named by this macro, that resolves its
+// kernels: KernelEntry scan_entry_f<f>_m<m>(ScanVariant), KernelEntry star_entry_f<f>_m<m>().
+#define PGPU_OBJECT_ENTRY_(kind, F, M) kind##_entry_f##F##_m##M
+#define PGPU_OBJECT_ENTRY(kind, F, M) PGPU_OBJECT_ENTRY_(kind, F, M)
+
 // leaf_masks_kernel work item: groups [group0, group0 + 256) of plan record `rec`; its leaves' masks go to
 // out + out_word + leaf * ceil(numDocs / 32) (STATS_GENERIC segments, replayed on the host).
 struct KMaskJob {
@@ -444,15 +491,13 @@ int launch_table_init(uint64_t* table, const int32_t* slot_kind, int32_t num_slo
 // 0 = none) has passed.
 int launch_expand_tiles(const uint8_t* segs, int32_t seg_stride, int32_t num_segs, int32_t* tile_seg,
                         uint64_t deadline, unsigned long long* stats, void* stream);
-// variant: 0 sparse instance, 1 dense, 2 dense "simple" (no LUT / dictionary gathers, no double sums), 3 - 5 the
-// sparse specialisations (k_direct.hip); 6 / 7: the sparse / dense instance of plans with SLOT_SUM_FX slots
-// (k_direct_fx.hip); 8 / 9: the sparse / dense instance of plans with SLOT_DISTINCT slots (k_direct_dc.hip)
-constexpr int kVariantFxSparse = 6, kVariantFxDense = 7, kVariantDcSparse = 8, kVariantDcDense = 9;
-int launch_filter_groupby(const KParams& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
-// The FX instances (variant kVariantFxSparse / kVariantFxDense).
-int launch_filter_groupby_fx(const KParamsFx& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
-// The DC instances (variant kVariantDcSparse / kVariantDcDense; MODE_LDS and MODE_GLOBAL only).
-int launch_filter_groupby_dc(const KParamsDc& p, int mode, int variant, int grid, size_t lds_bytes, void* stream);
+// The scan kernel's instance (mode, variant) of kScanInstances, or {nullptr, 0} where the table has none (a variant
+// out of range, a mode the instance does not exist in).  Launch and occupancy both resolve through it.
+KernelEntry scan_entry(int mode, int variant);
+// Launches it with its family's parameter block: p (SCAN_BASE), p then fx (SCAN_FX), p then dc (SCAN_DC).  -1 where
+// scan_entry has nothing.
+int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, int mode, int variant, int grid,
+                size_t lds_bytes, void* stream);
 // Row dc.slot[d] of table [num_slots][num_keys] <- per key the popcount of its words[d] bitmap words (0 where the
 // key's COUNT, row 0, is 0), for every d.
 int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_keys, void* stream);
@@ -460,8 +505,8 @@ int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_k
 // dc.slot[d] <- the popcount of the merged rows, with no gate on the COUNT row.  count 0 launches nothing.
 int launch_distinct_merge_popcount(const KDistinct& dc, const KDistinctRecv& rv, uint64_t* table, int64_t num_keys,
                                    int64_t begin, int64_t count, int nranks, void* stream);
-// Resident workgroups per CU of the direct kernel instance (< 0: query failed).
-int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes);
+// Resident workgroups per CU of the scan kernel's instance (< 0: no such instance, or the query failed).
+int occupancy_scan(int mode, int variant, size_t lds_bytes);
 int launch_reduce_slabs(const uint64_t* slab, const int32_t* slot_kind_dev, int32_t num_slots, int64_t num_keys,
                         int32_t num_blocks, uint64_t* out, void* stream);
 int launch_compact(const uint64_t* table, const unsigned long long* hash_keys, int32_t num_slots, int64_t num_keys,
@@ -542,7 +587,7 @@ constexpr int kStarMaxSegs = 4096;  // star-tree segments per K6 launch (their g
 int launch_deadline_gate(uint64_t deadline, unsigned long long* stats, void* stream);
 int launch_startree_traverse(const KStarSeg* segs, int32_t num_segs, int64_t* seg_total, uint64_t deadline,
                              unsigned long long* stats, void* stream);
-// fx: the instance for plans with SLOT_SUM_FX slots (k_startree_fx.hip)
+// fx: the instance for plans with SLOT_SUM_FX slots
 int launch_startree_scan(const KStarParams& p, int mode, bool fx, size_t lds_bytes, void* stream);
 // Synthetic generator (bench): positions of generated values in the sorted domain + presence bitmap, then pack.
 int launch_gen_positions(int32_t kind, uint64_t seed, int64_t lo, int64_t span, const double* cdf,

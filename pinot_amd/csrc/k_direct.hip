@@ -1,55 +1,45 @@
-// k_direct.hip — one accumulator mode of the direct-load scan kernel (compiled with -DPGPU_MODE=0|1|2).
+// k_direct.hip — the direct-load scan kernel's instances of one family in one accumulator mode: compiled with
+// -DPGPU_FAMILY=0|1|2 (ScanFamily: base, FX, DC) and -DPGPU_MODE=0|1|2 (LDS, GLOBAL, HASH).  Which instances those
+// are, and their template arguments, is kScanInstances' to say (internal.h).
+#include <utility>
+
 #include "scan_direct.h"
 
-#ifndef PGPU_MODE
-#error "compile with -DPGPU_MODE=0 (LDS), 1 (GLOBAL) or 2 (HASH)"
+#if !defined(PGPU_MODE) || !defined(PGPU_FAMILY)
+#error "compile with -DPGPU_FAMILY=0 (base), 1 (FX) or 2 (DC) and -DPGPU_MODE=0 (LDS), 1 (GLOBAL) or 2 (HASH)"
 #endif
-#define PGPU_CAT2(a, b) a##b
-#define PGPU_CAT(a, b) PGPU_CAT2(a, b)
+#if PGPU_FAMILY == 2 && PGPU_MODE == 2
+#error "the DC instances exist for MODE_LDS and MODE_GLOBAL only"
+#endif
 
 namespace pgpu {
 
-// variant: 0 the sparse instance, 1 the dense one, 2 the dense one for "simple" plans (aggregate_batch's SIMPLE),
-// 3 the sparse one with the index + scan pair (bitdir_range), 4 the sparse one for pure-AND plans (FAST), 5 that one
-// with 4-doc lane batches (plans of estimated selectivity >= 1/16).
-int PGPU_CAT(launch_direct_mode, PGPU_MODE)(const KParams& p, int variant, int grid, size_t lds_bytes, void* stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (variant == 5)
-    hipLaunchKernelGGL((filter_groupby_kernel<PGPU_MODE, false, false, false, true, 4>), dim3(grid), dim3(kBlock),
-                       lds_bytes, s, p);
-  else if (variant == 4)
-    hipLaunchKernelGGL((filter_groupby_kernel<PGPU_MODE, false, false, false, true>), dim3(grid), dim3(kBlock),
-                       lds_bytes, s, p);
-  else if (variant == 3)
-    hipLaunchKernelGGL((filter_groupby_kernel<PGPU_MODE, false, false, true>), dim3(grid), dim3(kBlock), lds_bytes, s,
-                       p);
-  else if (variant == 2)
-    hipLaunchKernelGGL((filter_groupby_kernel<PGPU_MODE, true, true>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
-  else if (variant == 1)
-    hipLaunchKernelGGL((filter_groupby_kernel<PGPU_MODE, true>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+// The kernel of row V, or null where the row is of another family or mode (a row not taken instantiates nothing).
+template <int V>
+static const void* instance() {
+  constexpr ScanInstance I = kScanInstances[V];
+  if constexpr (I.family != PGPU_FAMILY || !(I.modes >> PGPU_MODE & 1))
+    return nullptr;
+  else if constexpr (I.family == SCAN_FX)
+    return reinterpret_cast<const void*>(filter_groupby_fx_kernel<PGPU_MODE, I.dense>);
+  else if constexpr (I.family == SCAN_DC)
+    return reinterpret_cast<const void*>(filter_groupby_dc_kernel<PGPU_MODE, I.dense>);
   else
-    hipLaunchKernelGGL((filter_groupby_kernel<PGPU_MODE, false>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+    return reinterpret_cast<const void*>(
+        filter_groupby_kernel<PGPU_MODE, I.dense, I.simple, I.pair, I.fast, I.lane_batch>);
 }
 
-// Resident workgroups per CU of the instance (registers and LDS): the persistent grid is sized to exactly fill
-// the chip, since its tile ranges are assigned statically.
-int PGPU_CAT(occupancy_direct_mode, PGPU_MODE)(int variant, size_t lds_bytes) {
-  int n = 0;
-  const hipError_t e =
-      variant == 5 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                         &n, filter_groupby_kernel<PGPU_MODE, false, false, false, true, 4>, kBlock, lds_bytes)
-      : variant == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                         &n, filter_groupby_kernel<PGPU_MODE, false, false, false, true>, kBlock, lds_bytes)
-      : variant == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, filter_groupby_kernel<PGPU_MODE, false, false, true>,
-                                                                   kBlock, lds_bytes)
-      : variant == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, filter_groupby_kernel<PGPU_MODE, true, true>, kBlock,
-                                                                   lds_bytes)
-      : variant == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, filter_groupby_kernel<PGPU_MODE, true>, kBlock,
-                                                                     lds_bytes)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, filter_groupby_kernel<PGPU_MODE, false>, kBlock,
-                                                                    lds_bytes);
-  return e == hipSuccess ? n : -1;
+template <int... V>
+static const void* instance_of(int variant, std::integer_sequence<int, V...>) {
+  // (last row first: the kernels are laid out in the code object in the order they are named here, and this is the
+  // order they have always had)
+  static const void* const kernels[] = {instance<kScanVariants - 1 - V>()...};
+  return kernels[kScanVariants - 1 - variant];
+}
+
+// variant: in [0, kScanVariants) (scan_entry checks it).
+KernelEntry PGPU_OBJECT_ENTRY(scan, PGPU_FAMILY, PGPU_MODE)(ScanVariant variant) {
+  return {instance_of(variant, std::make_integer_sequence<int, kScanVariants>{}), kBlock};
 }
 
 }  // namespace pgpu

@@ -818,57 +818,61 @@ int launch_hash_unpack(uint64_t* table, const unsigned long long* hash_keys, int
   return PGPU_HIP_OK(hipGetLastError());
 }
 
-// One object per (kernel family, mode): k_direct.hip / k_startree.hip compiled with -DPGPU_MODE=0,1,2, and the
-// instances for plans with SLOT_SUM_FX slots beside them (k_direct_fx.hip / k_startree_fx.hip).
-#define PGPU_MODE_DECLS(M)                                                                                   \
-  int launch_direct_mode##M(const KParams& p, int variant, int grid, size_t lds_bytes, void* stream);        \
-  int occupancy_direct_mode##M(int variant, size_t lds_bytes);                                               \
-  int launch_direct_fx_mode##M(const KParamsFx& p, int variant, int grid, size_t lds_bytes, void* stream);   \
-  int occupancy_direct_fx_mode##M(int variant, size_t lds_bytes);                                            \
-  int launch_startree_scan_mode##M(const KStarParams& p, size_t lds_bytes, void* stream);                    \
-  int launch_startree_scan_fx_mode##M(const KStarParams& p, size_t lds_bytes, void* stream);
-PGPU_MODE_DECLS(0)
-PGPU_MODE_DECLS(1)
-PGPU_MODE_DECLS(2)
+// The per-(family, mode) objects of the scan and of the star-tree document scan (PGPU_OBJECT_ENTRY, internal.h).  Every
+// cell is declared; the objects that do not exist (DC x HASH, a star-tree DC family) are never referenced.
+#define PGPU_MODE_DECLS(F, M)                                     \
+  KernelEntry PGPU_OBJECT_ENTRY(scan, F, M)(ScanVariant variant); \
+  KernelEntry PGPU_OBJECT_ENTRY(star, F, M)();
+#define PGPU_FAMILY_DECLS(F) PGPU_MODE_DECLS(F, 0) PGPU_MODE_DECLS(F, 1) PGPU_MODE_DECLS(F, 2)
+PGPU_FAMILY_DECLS(0)
+PGPU_FAMILY_DECLS(1)
+PGPU_FAMILY_DECLS(2)
+#undef PGPU_FAMILY_DECLS
 #undef PGPU_MODE_DECLS
-// The instances for plans with SLOT_DISTINCT slots (k_direct_dc.hip: dense key spaces, -DPGPU_MODE=0,1).
-int launch_direct_dc_mode0(const KParamsDc& p, int variant, int grid, size_t lds_bytes, void* stream);
-int launch_direct_dc_mode1(const KParamsDc& p, int variant, int grid, size_t lds_bytes, void* stream);
-int occupancy_direct_dc_mode0(int variant, size_t lds_bytes);
-int occupancy_direct_dc_mode1(int variant, size_t lds_bytes);
+static KernelEntry (*const kScanObjects[3][3])(ScanVariant) = {  // [ScanFamily][Mode]
+    {scan_entry_f0_m0, scan_entry_f0_m1, scan_entry_f0_m2},
+    {scan_entry_f1_m0, scan_entry_f1_m1, scan_entry_f1_m2},
+    {scan_entry_f2_m0, scan_entry_f2_m1, nullptr}};
+static KernelEntry (*const kStarObjects[2][3])() = {  // [fx][Mode]
+    {star_entry_f0_m0, star_entry_f0_m1, star_entry_f0_m2}, {star_entry_f1_m0, star_entry_f1_m1, star_entry_f1_m2}};
+
+static int launch_entry(const KernelEntry& e, int grid, size_t lds_bytes, void* stream, const void* params) {
+  void* args[] = {const_cast<void*>(params)};  // every one of these kernels takes its parameter block by value
+  hipLaunchKernel(e.fn, dim3(grid), dim3(e.block), args, lds_bytes, S(stream));
+  return PGPU_HIP_OK(hipGetLastError());
+}
 
 int launch_startree_scan(const KStarParams& p, int mode, bool fx, size_t lds_bytes, void* stream) {
-  switch (mode) {
-    case MODE_LDS: return fx ? launch_startree_scan_fx_mode0(p, lds_bytes, stream) : launch_startree_scan_mode0(p, lds_bytes, stream);
-    case MODE_GLOBAL: return fx ? launch_startree_scan_fx_mode1(p, lds_bytes, stream) : launch_startree_scan_mode1(p, lds_bytes, stream);
-    default: return fx ? launch_startree_scan_fx_mode2(p, lds_bytes, stream) : launch_startree_scan_mode2(p, lds_bytes, stream);
-  }
+  if (p.num_wgs <= 0 || p.num_segs <= 0) return 0;
+  if (mode < MODE_LDS || mode > MODE_HASH) return -1;
+  return launch_entry(kStarObjects[fx][mode](), p.num_wgs, lds_bytes, stream, &p);
 }
 
-int launch_filter_groupby(const KParams& p, int mode, int variant, int grid, size_t lds_bytes, void* stream) {
-  if (variant >= kVariantFxSparse) return -1;  // the FX instances take a KParamsFx (launch_filter_groupby_fx)
-  switch (mode) {
-    case MODE_LDS: return launch_direct_mode0(p, variant, grid, lds_bytes, stream);
-    case MODE_GLOBAL: return launch_direct_mode1(p, variant, grid, lds_bytes, stream);
-    default: return launch_direct_mode2(p, variant, grid, lds_bytes, stream);
-  }
+KernelEntry scan_entry(int mode, int variant) {
+  if (variant < 0 || variant >= kScanVariants || mode < MODE_LDS || mode > MODE_HASH) return {nullptr, 0};
+  const ScanInstance& I = kScanInstances[variant];
+  if (!(I.modes >> mode & 1)) return {nullptr, 0};  // (hash-mode plans with DISTINCTCOUNT are declined at plan time)
+  return kScanObjects[I.family][mode]((ScanVariant)variant);
 }
 
-int launch_filter_groupby_fx(const KParamsFx& p, int mode, int variant, int grid, size_t lds_bytes, void* stream) {
-  switch (mode) {
-    case MODE_LDS: return launch_direct_fx_mode0(p, variant, grid, lds_bytes, stream);
-    case MODE_GLOBAL: return launch_direct_fx_mode1(p, variant, grid, lds_bytes, stream);
-    default: return launch_direct_fx_mode2(p, variant, grid, lds_bytes, stream);
-  }
-}
-
-int launch_filter_groupby_dc(const KParamsDc& p, int mode, int variant, int grid, size_t lds_bytes, void* stream) {
-  if (variant != kVariantDcSparse && variant != kVariantDcDense) return -1;
-  if (p.dc.n < 0 || p.dc.n > kMaxDistinct) return -1;
-  switch (mode) {
-    case MODE_LDS: return launch_direct_dc_mode0(p, variant, grid, lds_bytes, stream);
-    case MODE_GLOBAL: return launch_direct_dc_mode1(p, variant, grid, lds_bytes, stream);
-    default: return -1;  // hash-mode plans with DISTINCTCOUNT are declined at plan time
+int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, int mode, int variant, int grid,
+                size_t lds_bytes, void* stream) {
+  const KernelEntry e = scan_entry(mode, variant);
+  if (!e.fn) return -1;
+  KParamsFx kf;
+  KParamsDc kd;
+  switch (kScanInstances[variant].family) {
+    case SCAN_FX:
+      static_cast<KParams&>(kf) = p;
+      kf.fx = fx;
+      return launch_entry(e, grid, lds_bytes, stream, &kf);
+    case SCAN_DC:
+      if (dc.n < 0 || dc.n > kMaxDistinct) return -1;
+      static_cast<KParams&>(kd) = p;
+      kd.dc = dc;
+      return launch_entry(e, grid, lds_bytes, stream, &kd);
+    default:
+      return launch_entry(e, grid, lds_bytes, stream, &p);
   }
 }
 
@@ -949,16 +953,13 @@ int launch_distinct_merge_popcount(const KDistinct& dc, const KDistinctRecv& rv,
   return PGPU_HIP_OK(hipGetLastError());
 }
 
-int occupancy_filter_groupby(int mode, int variant, size_t lds_bytes) {
-  if (variant >= kVariantDcSparse)
-    return mode == MODE_LDS ? occupancy_direct_dc_mode0(variant, lds_bytes)
-           : mode == MODE_GLOBAL ? occupancy_direct_dc_mode1(variant, lds_bytes) : -1;
-  const bool fx = variant >= kVariantFxSparse;
-  switch (mode) {
-    case MODE_LDS: return fx ? occupancy_direct_fx_mode0(variant, lds_bytes) : occupancy_direct_mode0(variant, lds_bytes);
-    case MODE_GLOBAL: return fx ? occupancy_direct_fx_mode1(variant, lds_bytes) : occupancy_direct_mode1(variant, lds_bytes);
-    default: return fx ? occupancy_direct_fx_mode2(variant, lds_bytes) : occupancy_direct_mode2(variant, lds_bytes);
-  }
+// Registers and LDS of the instance: the persistent grid is sized to exactly fill the chip, since its tile ranges are
+// assigned statically.
+int occupancy_scan(int mode, int variant, size_t lds_bytes) {
+  const KernelEntry e = scan_entry(mode, variant);
+  int n = 0;
+  if (!e.fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, e.fn, e.block, lds_bytes) != hipSuccess) return -1;
+  return n;
 }
 
 int launch_expand_tiles(const uint8_t* segs, int32_t seg_stride, int32_t num_segs, int32_t* tile_seg,

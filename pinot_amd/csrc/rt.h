@@ -740,14 +740,12 @@ struct pgpu_plan_s {
   std::vector<uint8_t> seg_scanned;       // per plan segment: 1 = scanned (filter not folded to empty)
   int grid = 0;
   size_t lds_bytes = 0;
+  ScanVariant variant = kScanSparse;      // the scan kernel's instance the plan launches (configure_scan_grid)
   bool dense = false;                     // direct kernel instance with whole-group decode (dense tiles)
-  // dense plans whose group-by columns need no LUT and whose operands no dictionary lookup in any segment, with no
-  // double sums: the dense instance compiled without those gathers (aggregate_batch's SIMPLE; fewer registers)
-  bool dense_simple = false;
   bool gathers = false;                   // some segment's key LUT or operand dictionary is read (not simple)
-  bool pair_variant = false;              // sparse instance with the index + scan pair (variant 3)
-  bool fast_variant = false;              // sparse instance for pure-AND plans of <= kFastLeaves leaves (variant 4)
-  bool fast_wide = false;                 // ... with 4-doc lane batches: estimated selectivity >= 1/16 (variant 5)
+  // a pure-AND plan of <= kFastLeaves leaves, no index + scan pair, estimated selectivity >= 1/16.  A property of the
+  // plan's filter, not of the launched instance: FX and DC plans have it too (fill_kparams' tile_chunks)
+  bool fast_wide = false;
   bool partitioned = false;               // large dense table: partitioned group-by (partition.h) instead of atomics
   std::vector<LaunchChunk> chunks;        // scan launches (one unless the plan was streamed)
   int launches_done = 0;

@@ -90,7 +90,6 @@ int launch_raw_leaves(const pgpu_plan_s* P, Scratch* sc, hipStream_t stream);
 int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chunks, ExecCtx& X);
 int exec_upload_chunk(pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, const LaunchChunk& C);
 bool check_launch_on();
-int scan_variant(const pgpu_plan_s* P);
 bool set_slot_weights(KParams& kp, int grid, int num_cus, double step, int64_t max_run);
 void inflight_end(pgpu_plan_s* P);
 int exec_launch_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, const LaunchChunk& C, int c);

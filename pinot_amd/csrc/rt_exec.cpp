@@ -358,7 +358,7 @@ static void fill_kparams(const pgpu_plan_s* P, uint64_t deadline, ExecCtx& X) {
 #ifdef PGPU_CHUNK_ALL  // (an A/B build of the library: contiguous runs for the dense and wide plans too)
   kp.tile_chunks = 1;
 #else
-  kp.tile_chunks = P->dense || P->fast_wide ? 0 : 1;
+  kp.tile_chunks = P->dense || P->fast_wide ? 0 : 1;  // (the plan's property, not P->variant: FX / DC plans differ)
 #endif
   kp.num_slots = nslots;
   for (int sl = 0; sl < nslots; ++sl) { kp.slot_kind[sl] = P->slot_kind[sl]; kp.slot_col[sl] = P->slot_col[sl]; }
@@ -526,8 +526,6 @@ static int check_launch_inputs(const pgpu_plan_s* P, hipStream_t stream, const E
   return 0;
 }
 
-// The scan instance a plan launches (k_direct.hip): 2 dense "simple", 1 dense, 3 index + scan pair, 5 / 4 pure-AND
-// sparse with 4 / 2-doc lane batches, 0 the general sparse one.
 // The split parameters of the plan's SLOT_SUM_FX slots (KParamsFx / KStarParams.fx).
 KFxSplit fx_split(const pgpu_plan_s* P) {
   KFxSplit x;
@@ -540,12 +538,6 @@ KFxSplit fx_split(const pgpu_plan_s* P) {
     x.j[sl] = (int8_t)P->slot_fx[sl];
   }
   return x;
-}
-
-int scan_variant(const pgpu_plan_s* P) {
-  if (!P->dc.empty()) return P->dense ? kVariantDcDense : kVariantDcSparse;  // plans with DISTINCTCOUNT: theirs
-  if (P->fx) return P->dense ? kVariantFxDense : kVariantFxSparse;  // plans with SLOT_SUM_FX slots: their own instances
-  return P->dense_simple ? 2 : P->dense ? 1 : P->pair_variant ? 3 : P->fast_wide ? 5 : P->fast_variant ? 4 : 0;
 }
 
 // PGPU_TRACE=wgtimes with a PGPU_DIAG_WG_TIMES build: every scan launch is synchronised and its workgroups' start /
@@ -812,21 +804,9 @@ static int launch_scan_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, KPa
   for (int s = 0; s < kMaxCuSlots; ++s) P->last_scan.slot_w[s] = kp.slot_n ? kp.slot_w[s] : 0;
   P->last_scan.alone = P->alone;
   P->last_scan.declined = !fits;
-  int rc;
-  if (!P->dc.empty()) {  // the DC instances: the launch's parameters and the side bitmaps
-    KParamsDc kd;
-    static_cast<KParams&>(kd) = kp;
-    kd.dc = X.dc;
-    rc = launch_filter_groupby_dc(kd, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
-  } else if (P->fx) {  // the FX instances: the launch's parameters and the split of the fixed-point slots
-    KParamsFx kf;
-    static_cast<KParams&>(kf) = kp;
-    kf.fx = fx_split(P);
-    rc = launch_filter_groupby_fx(kf, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
-  } else {
-    rc = launch_filter_groupby(kp, P->mode, scan_variant(P), grid, P->lds_bytes, stream);
-  }
-  if (rc) return fail(PGPU_ERR_DEVICE, "scan launch failed: %s", hipGetErrorString(hipGetLastError()));
+  // (the instance's family takes what it needs: the split of the fixed-point slots, the side bitmaps, or neither)
+  if (launch_scan(kp, fx_split(P), X.dc, P->mode, P->variant, grid, P->lds_bytes, stream))
+    return fail(PGPU_ERR_DEVICE, "scan launch failed: %s", hipGetErrorString(hipGetLastError()));
   X.mark("scan launched");
   if (wg_times) TRY(diag_wg_times_report(P->table, kp, grid, stream));
   return 0;

@@ -1055,21 +1055,30 @@ void configure_scan_grid(PlanCtx& cx, int64_t tile_base) {
   P->dense = P->mode != MODE_HASH && P->sel_estimate >= P->cfg.dense_selectivity;
   bool f64 = false;
   for (int k : P->slot_kind) f64 |= k == SLOT_SUM_F64;
-  // (a streamed plan configures before its later chunks are planned: never simple)
-  P->dense_simple = P->dense && !P->gathers && !f64 && !P->fx && P->dc.empty() && P->tile_bound == 0;
+  // dense plans whose group-by columns need no LUT and whose operands no dictionary lookup in any segment, with no
+  // double sums (a streamed plan configures before its later chunks are planned: never simple)
+  const bool dense_simple = P->dense && !P->gathers && !f64 && !P->fx && P->dc.empty() && P->tile_bound == 0;
   // the sparse instance with the index + scan pair: two-leaf AND plans with an in-place index leaf
-  P->pair_variant = !P->dense && P->pure_and && P->num_leaves == 2 && P->leaf_kinds[LEAF_BITDIR] > 0;
-  P->fast_variant = !P->dense && !P->pair_variant && P->pure_and && P->num_leaves <= kFastLeaves;
-  P->fast_wide = P->fast_variant && P->sel_estimate >= 1.0 / 16;
-  const int variant = scan_variant(P);
+  const bool pair = !P->dense && P->pure_and && P->num_leaves == 2 && P->leaf_kinds[LEAF_BITDIR] > 0;
+  const bool fast = !P->dense && !pair && P->pure_and && P->num_leaves <= kFastLeaves;
+  P->fast_wide = fast && P->sel_estimate >= 1.0 / 16;
+  // plans with DISTINCTCOUNT and plans with SLOT_SUM_FX slots launch their own instances whatever the filter
+  P->variant = !P->dc.empty() ? (P->dense ? kScanDcDense : kScanDcSparse)
+               : P->fx        ? (P->dense ? kScanFxDense : kScanFxSparse)
+               : dense_simple ? kScanDenseSimple
+               : P->dense     ? kScanDense
+               : pair         ? kScanPair
+               : P->fast_wide ? kScanFastWide
+               : fast         ? kScanFast
+                              : kScanSparse;
   int per_cu;  // resident workgroups per CU
   {
     static std::mutex occ_mu;
-    static std::map<std::tuple<int, int, int, size_t>, int> occ_cache;  // (device, mode, dense, lds) -> per CU
+    static std::map<std::tuple<int, int, int, size_t>, int> occ_cache;  // (device, mode, variant, lds) -> per CU
     std::lock_guard<std::mutex> g(occ_mu);
-    const auto k = std::make_tuple(t->device, (int)P->mode, variant, P->lds_bytes);
+    const auto k = std::make_tuple(t->device, (int)P->mode, (int)P->variant, P->lds_bytes);
     auto it = occ_cache.find(k);
-    if (it == occ_cache.end()) it = occ_cache.emplace(k, occupancy_filter_groupby(P->mode, variant, P->lds_bytes)).first;
+    if (it == occ_cache.end()) it = occ_cache.emplace(k, occupancy_scan(P->mode, P->variant, P->lds_bytes)).first;
     per_cu = it->second;
   }
   if (per_cu <= 0) per_cu = 1;

@@ -1,5 +1,5 @@
 // scan_direct.h — the fused filter / group-by / aggregation scan (K1+K2+K3) with direct loads: the kernel of
-// the path.  Instantiated once per accumulator mode in k_direct.hip.
+// the path.  Instantiated per family and accumulator mode in k_direct.hip, from kScanInstances (internal.h).
 #pragma once
 #include "device.h"
 
@@ -51,9 +51,9 @@ __device__ __forceinline__ uint32_t leap2_entries(uint8_t* __restrict__ maps, in
 // instance for plans of estimated selectivity >= 1/16 (C4's scan path at 15 %: 174 -> 150 us), 2 elsewhere (4 cost
 // C3, where that path is rare, 1.5 % -- 710 -> 722 us -- and the dense instance's C2 2 %).
 // FX: the instances of plans with fixed-point FLOAT / DOUBLE sums (SLOT_SUM_FX slots, fx_sum.h) -- kernels of their
-// own (filter_groupby_fx_kernel, k_direct_fx.hip, with KParamsFx), so the others keep their registers and arguments.
+// own (filter_groupby_fx_kernel, family SCAN_FX, with KParamsFx), so the others keep their registers and arguments.
 // DC: the instances of plans with DISTINCTCOUNT aggregations (SLOT_DISTINCT slots and their side bitmaps) -- kernels of
-// their own again (filter_groupby_dc_kernel, k_direct_dc.hip, with KParamsDc).
+// their own again (filter_groupby_dc_kernel, family SCAN_DC, with KParamsDc).
 // The kernels share their body as text (scan_direct_body.inc): a body function inlined into them changed the
 // scalar register allocation of the existing instances.
 #ifndef PGPU_MIN_WAVES

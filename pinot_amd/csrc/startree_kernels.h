@@ -23,7 +23,7 @@ __device__ __forceinline__ int64_t double_key_dev(double d) {  // order-preservi
   return b >= 0 ? b : (b ^ INT64_MAX);
 }
 
-#if PGPU_MODE == 0 && !defined(PGPU_STAR_SCAN_ONLY)  // one definition: the mode-0 object of k_startree.hip
+#if PGPU_MODE == 0 && !defined(PGPU_STAR_SCAN_ONLY)  // one definition: the plain mode-0 object of k_startree.hip
 __global__ __launch_bounds__(256) void startree_traverse_kernel(const KStarSeg* __restrict__ segs,
                                                                 int64_t* __restrict__ seg_total, uint64_t deadline,
                                                                 unsigned long long* __restrict__ stats) {
@@ -456,7 +456,7 @@ template <int MODE>
 __global__ __launch_bounds__(StarBlock<MODE>::value) void startree_scan_kernel(const KStarParams p) {
   startree_scan_body<MODE, false>(p);
 }
-// The instance for plans with SLOT_SUM_FX slots (k_startree_fx.hip).
+// The instance for plans with SLOT_SUM_FX slots (k_startree.hip compiled with -DPGPU_FAMILY=1).
 template <int MODE>
 __global__ __launch_bounds__(StarBlock<MODE>::value) void startree_scan_fx_kernel(const KStarParams p) {
   startree_scan_body<MODE, true>(p);

@@ -1,7 +1,7 @@
 """DISTINCTCOUNT on the GPU group-by path: the reference's recorded answers (InterSegmentAggregationSingleValueQueriesTest.
 testDistinctCount, tests/golden/kat_inter_distinct.json) and a brute-force numpy set count (distinct_common.py) -- the
 oracle has no DISTINCTCOUNT.  Counts are integers and compared exactly.  Each test asserts through Plan.group_path /
-Plan.scan_geometry()["variant"] (8 sparse, 9 dense: the instances of k_direct_dc.hip) the path it means to cover."""
+Plan.scan_geometry()["variant"] (8 sparse, 9 dense: the DC instances of k_direct.hip) the path it means to cover."""
 import numpy as np
 import pytest
 

@@ -91,3 +91,4 @@ def test_host_parsers_under_sanitizers(oracle, harness, tmp_path):
     assert res.returncode == 0, out[-6000:]
     assert "runtime error" not in out and "AddressSanitizer" not in out, out[-6000:]
     assert "host_fuzz calls:" in out
+    assert "scan instances resolved: 28 of 3 x 10 cells" in out  # every (mode, variant) cell but DC x HASH

@@ -15,6 +15,7 @@
 // mutations (bit flips, random bytes, boundary int32 / int64 values, truncation, splices) and hands the result to the
 // entry point in a buffer of exactly its size, so any read past it is reported.  The return codes are not checked
 // (most mutants must be rejected); the sanitizers are the oracle, and exit status 0 means no report.
+// One check is not a fuzz: the scan kernel's (mode, variant) dispatch against its support matrix (exit status 5).
 //
 // usage: host_fuzz <corpus_dir> <iterations per target> <seed>
 #include <dirent.h>
@@ -27,9 +28,35 @@
 #include <string>
 #include <vector>
 
+#include "../pinot_amd/csrc/internal.h"
 #include "pinotgpu.h"
 
 namespace {
+
+// The scan kernel's dispatch (scan_entry, kernels.hip) over every (mode, variant) cell and one variant past each end:
+// an entry exactly where kScanInstances has one -- 28 cells, all but DC x HASH.  Resolves only; nothing is launched.
+int scan_cells_resolved() {
+  std::vector<const void*> seen;
+  int resolved = 0;
+  for (int mode = pgpu::MODE_LDS; mode <= pgpu::MODE_HASH; ++mode)
+    for (int v = -1; v <= pgpu::kScanVariants; ++v) {
+      const bool want = v >= 0 && v < pgpu::kScanVariants &&
+                        !(mode == pgpu::MODE_HASH && (v == pgpu::kScanDcSparse || v == pgpu::kScanDcDense));
+      const pgpu::KernelEntry e = pgpu::scan_entry(mode, v);
+      if ((e.fn != nullptr) != want || (want && e.block != pgpu::kBlock)) {
+        fprintf(stderr, "scan_entry(mode %d, variant %d): %s\n", mode, v, want ? "no entry" : "an entry");
+        exit(5);
+      }
+      if (want) seen.push_back(e.fn);
+      resolved += want;
+    }
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) {
+    fprintf(stderr, "scan_entry: two cells resolve to one kernel\n");
+    exit(5);
+  }
+  return resolved;
+}
 
 struct Rng {
   uint64_t s;
@@ -409,7 +436,10 @@ int main(int argc, char** argv) {
   const long inv = timed("inv", [&] { return fuzz_inv(iters, r); });
   const long stb = timed("stb", [&] { return fuzz_startree_build(iters / 4 + 1, r); });
   const long flt = timed("flt", [&] { return fuzz_filter(iters, r); });
+  const int cells = scan_cells_resolved();
+  printf("scan instances resolved: %d of 3 x %d cells\n", cells, pgpu::kScanVariants);
   printf("host_fuzz calls: raw %ld dt %ld st %ld invf %ld inv %ld stb %ld flt %ld\n", raw, dt, st, invf, inv, stb,
          flt);
+  if (cells != 28) return 5;
   return (raw > 0 && dt > 0 && st > 0 && invf > 0) ? 0 : 3;  // 3: a seed family is missing from the corpus
 }

@@ -1,5 +1,5 @@
 """Register report of one library source's kernels (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel:
-VGPRs, AGPRs, spills, occupancy, LDS.  Usage: python tools/vgpr_report.py k_direct.hip -DPGPU_MODE=0 [-DX=1 ...]"""
+VGPRs, AGPRs, spills, occupancy, LDS.  Usage: python tools/vgpr_report.py k_direct.hip -DPGPU_FAMILY=0 -DPGPU_MODE=0 [-DX=1 ...]"""
 import os
 import re
 import subprocess
