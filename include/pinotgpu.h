@@ -228,8 +228,41 @@ typedef struct {
  * PGPU_COMBINE_REDUCE_SCATTER on the plan's own table (d_table NULL), as DistinctCountAggregationFunction.merge does
  * (the union of the sets) -- see pgpu_plan_combine.  The ranks union the dictionaries of the distinct columns, like
  * those of the group-by columns, first (pgpu_table_add_dictionary_values): bit i must mean one value everywhere. */
+/* PGPU_AGG_PERCENTILE_OF(p_e4)(col): the exact percentile of a dictionary-encoded single-value numeric column per group
+ * -- PercentileAggregationFunction.java:83-165 collects the matched values of a group, sorts them and returns the one
+ * at index size - 1 for the 100th percentile, else (int)((double)size * percentile / 100.0), size being the group's
+ * matched docs; the product and the quotient are IEEE doubles, each rounded on its own (10000 docs at 0.57 give index
+ * 56).  The percentile travels inside pgpu_agg.fn: bits 0..7 hold the function code PGPU_AGG_PERCENTILE, bits 8..31
+ * the percentile in ten-thousandths, 0 .. 1000000 (PERCENTILE95 = PGPU_AGG_PERCENTILE_OF(950000), PERCENTILE(x, 99.9)
+ * = PGPU_AGG_PERCENTILE_OF(999000)); the double the arithmetic uses is p_e4 / 10000.0, which equals the double of the
+ * decimal literal for every code.  Codes 0..5 have zero upper bits; PGPU_AGG_FN / PGPU_AGG_PERCENTILE_E4 take a
+ * pgpu_agg.fn apart.  Being part of fn, the percentile is part of the plan-cache key.
+ * Here the per-group sorted list is a histogram over the column's table-global dictIds (dictionary order is value
+ * order), filled with one 32-bit add per matched doc; segments merge by addition in any order and the answer is exact.
+ * The result is the selected value as a double ((double)value for INT / LONG): pgpu_result_values returns it; ORDER BY
+ * and both trims compare it as a double, the PQL trim largest first (as MAX).  A group without a match is absent; an
+ * aggregation-only query without a matched doc leaves the caller Pinot's default, -inf.  The column counts as
+ * projected (numEntriesScannedPostFilter), also for an unfiltered aggregation-only query, which is scanned (no
+ * dictionary-based answer: AggregationPlanNode's exemption is for MIN / MAX / DISTINCTCOUNT); a segment carrying a
+ * star-tree is scanned.  All percentiles of one column share its histogram; in a plan with a PERCENTILE the columns of
+ * DISTINCTCOUNT aggregations are counted from histograms too (the number of non-zero cells).
+ * Supported: dense key spaces (the LDS and global group tables, aggregation-only queries included); planned as with
+ * pgpu_config.partitioned_group_by = 0, hash_partitions = 0 and stream_chunks = 1.
+ * Declined -- a code above 1000000 with PGPU_ERR_INVALID_ARGUMENT, the rest with PGPU_ERR_UNSUPPORTED (the message
+ * names PERCENTILE): side histograms (keys x cardinality rounded up to 4 x 4 bytes per distinct column, those of
+ * DISTINCTCOUNT columns included) above 1 GiB in one plan; plans whose segments hold 2^32 docs or more (a cell could
+ * wrap); a STRING column; a raw (no-dictionary) column; key spaces that take the hash table (past 2^26 keys, or
+ * ARRAY_MAP stages); numGroupsLimit plans that split per segment; more than 8 side columns (histograms) in one query;
+ * the combination with PGPU_OPT_EXACT_FP_SUM; every cross-GPU or external-merge entry point (pgpu_plan_combine_mode,
+ * pgpu_plan_combine, pgpu_plan_exchange_*, pgpu_plan_finalize_range, an external d_table, pgpu_result_exchange_rows /
+ * merge_rows / combine_rows: per-rank percentiles do not merge) and pgpu_result_datatable (Pinot ships the value list
+ * as an OBJECT). */
 enum pgpu_agg_fn { PGPU_AGG_COUNT = 0, PGPU_AGG_SUM = 1, PGPU_AGG_MIN = 2, PGPU_AGG_MAX = 3, PGPU_AGG_AVG = 4,
-                   PGPU_AGG_DISTINCTCOUNT = 5 };
+                   PGPU_AGG_DISTINCTCOUNT = 5, PGPU_AGG_PERCENTILE = 6 };
+#define PGPU_AGG_PERCENTILE_MAX_E4 1000000
+#define PGPU_AGG_PERCENTILE_OF(p_e4) ((int32_t)(PGPU_AGG_PERCENTILE | ((int32_t)(p_e4) << 8)))
+#define PGPU_AGG_FN(fn) ((int32_t)((fn) & 0xFF))                           /* the function code of a pgpu_agg.fn */
+#define PGPU_AGG_PERCENTILE_E4(fn) ((int32_t)(((uint32_t)(fn)) >> 8))      /* its percentile in ten-thousandths */
 typedef struct {
   int32_t fn;
   int32_t column;   /* -1 for COUNT(*) */
@@ -516,7 +549,8 @@ int pgpu_plan_star_work(pgpu_plan plan, int64_t* out3);
  * was in flight (weights are for such launches only), [14] 1 = weights were declined because the longest weighted
  * run could pass [2]; [15] the scan kernel's instance: 0 sparse, 1 dense, 2 dense without gathers, 3 - 5 the sparse
  * specialisations (index + scan pair, pure AND, pure AND with 4-doc batches), 6 / 7 the sparse / dense instance of
- * plans with fixed-point sums (PGPU_OPT_EXACT_FP_SUM), 8 / 9: sparse / dense of plans with PGPU_AGG_DISTINCTCOUNT. */
+ * plans with fixed-point sums (PGPU_OPT_EXACT_FP_SUM), 8 / 9: sparse / dense of plans with PGPU_AGG_DISTINCTCOUNT,
+ * 10 / 11: sparse / dense of plans with PGPU_AGG_PERCENTILE (side histograms). */
 int pgpu_plan_scan_geometry(pgpu_plan plan, int64_t* out16);
 /* Bytes of the star-tree metric arrays the last execution's document scan read (after finalize): the 64-byte
  * sectors holding at least one matched document, summed over the arrays read; -1 where finalize did not read the

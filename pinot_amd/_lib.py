@@ -37,7 +37,7 @@ PRED_EQ, PRED_NOT_EQ, PRED_IN, PRED_NOT_IN, PRED_RANGE = 0, 1, 2, 3, 4
 OP_PRED, OP_AND, OP_OR, OP_NOT = 0, 1, 2, 3
 LEAF_KIND_NAMES = ("none", "all", "range", "set", "docrange", "bitmap", "raw_range", "raw_in", "bitdir")
 GROUP_PATH_NAMES = ("lds", "global", "hash", "partitioned", "hash_partitioned")  # enum pgpu_group_path
-AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG, AGG_DISTINCTCOUNT = 0, 1, 2, 3, 4, 5
+AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG, AGG_DISTINCTCOUNT, AGG_PERCENTILE = 0, 1, 2, 3, 4, 5, 6
 SLOT_COUNT, SLOT_SUM_I64, SLOT_SUM_F64, SLOT_MIN_KEY, SLOT_MAX_KEY = 0, 1, 2, 3, 4
 GEN_UNIFORM, GEN_ZIPF, GEN_TABLE = 0, 1, 2
 COMM_RCCL, COMM_HOST = 0, 1

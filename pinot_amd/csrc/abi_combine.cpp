@@ -7,6 +7,7 @@ extern "C" {
 namespace {
 int exchangeable(pgpu_plan P) {
   if (!P) return fail(PGPU_ERR_INVALID_ARGUMENT, "null plan");
+  if (plan_has_percentile(P)) return percentile_decline("a cross-GPU exchange");
   if (plan_has_distinct(P)) return distinct_decline("a cross-GPU exchange");
   if (P->composite) return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit plan: exchange its finalized result rows");
   if (!P->hash) return fail(PGPU_ERR_UNSUPPORTED, "dense group tables merge element-wise (all-reduce / reduce-scatter)");
@@ -193,6 +194,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
   PGPU_ABI_GUARD;
   if (!r || nparts < 1 || nparts > (1 << 20) || !counts || (r->n > 0 && !rows))
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_has_percentile(r)) return percentile_decline("a cross-GPU exchange of rows");
   if (result_has_distinct(r)) return distinct_decline("a cross-GPU exchange of rows");
   TRY(fx_rows_ready(r, "a cross-GPU exchange of rows"));
   if ((int)r->slot_kind.size() != r->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
@@ -228,6 +230,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
 int pgpu_result_merge_rows(pgpu_result tmpl, const int64_t* rows, int64_t n, const int32_t* kinds, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!tmpl || !out || n < 0 || (n > 0 && !rows)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_has_percentile(tmpl)) return percentile_decline("a cross-GPU merge of rows");
   if (result_has_distinct(tmpl)) return distinct_decline("a cross-GPU merge of rows");
   TRY(fx_rows_ready(tmpl, "a cross-GPU merge of rows"));
   if ((int)tmpl->slot_kind.size() != tmpl->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
@@ -640,6 +643,7 @@ int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_
   PGPU_ABI_GUARD;
   if (!P || !c || !mode) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
+  if (plan_has_percentile(P)) return percentile_decline("a cross-GPU combine");  // (... and the function)
   pgpu::CommWaitScope wait_limits(P->end_time_ms, &P->cancel);
   const int N = c->impl->nranks;
   int local;
@@ -710,6 +714,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   PGPU_ABI_GUARD;
   if (!P || !c) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
+  if (plan_has_percentile(P)) return percentile_decline("a cross-GPU combine");  // (... and the function)
   // DISTINCTCOUNT: the side bitmaps belong to the plan's own table (a caller table is declined at execute already)
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");  // (every rank passes one or none)
   P->k8d_counts = false;
@@ -861,6 +866,7 @@ int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
   PGPU_ABI_GUARD;
   if (!r || !c || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (result_fx_local(r)) return fx_decline("a cross-GPU combine of rows");  // every rank's query carries the option
+  if (result_has_percentile(r)) return percentile_decline("a cross-GPU combine of rows");
   if (result_has_distinct(r)) return distinct_decline("a cross-GPU combine of rows");
   pgpu::Comm* C = c->impl.get();
   const int N = C->nranks, me = C->rank;

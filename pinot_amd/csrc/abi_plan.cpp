@@ -483,6 +483,7 @@ int pgpu_plan_create_execute(pgpu_table t, const int64_t* handles, int32_t nsegs
   }
   if (d_table && (q->options & PGPU_OPT_EXACT_FP_SUM))
     return fail(PGPU_ERR_UNSUPPORTED, "external table with PGPU_OPT_EXACT_FP_SUM: ranks would have to agree on the fixed-point format first");
+  if (d_table && query_has_percentile(q)) return percentile_decline("external table");
   if (d_table && query_has_distinct(q)) return distinct_decline("external table");
   StreamExec se;
   se.stream = stream ? reinterpret_cast<hipStream_t>(stream) : t->stream;
@@ -529,6 +530,7 @@ int pgpu_plan_execute(pgpu_plan P, void* stream, void* d_table) try {
   }
   if (P->hash && d_table) return fail(PGPU_ERR_UNSUPPORTED, "external table with a hash-mode plan");
   if (d_table && plan_fx_local(P)) return fx_decline("external table");
+  if (d_table && plan_has_percentile(P)) return percentile_decline("external table");
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
@@ -539,6 +541,7 @@ int pgpu_plan_finalize(pgpu_plan P, void* stream, const void* d_table, pgpu_resu
   PGPU_ABI_GUARD;
   if (!P || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (d_table && plan_fx_local(P)) return fx_decline("external table");
+  if (d_table && plan_has_percentile(P)) return percentile_decline("external table");
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
@@ -563,6 +566,7 @@ int pgpu_plan_finalize_range(pgpu_plan P, void* stream, const void* d_table_shar
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (P->hash) return fail(PGPU_ERR_UNSUPPORTED, "hash-mode group tables are not key-range shardable");
   if (plan_fx_local(P)) return fx_decline("a key-range shard");
+  if (plan_has_percentile(P)) return percentile_decline("a key-range shard");
   if (plan_has_distinct(P)) return distinct_decline("a key-range shard");
   if (P->composite)
     return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit below the key space: finalize the whole table");

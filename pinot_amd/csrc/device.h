@@ -484,6 +484,20 @@ __device__ __forceinline__ void distinct_mark(unsigned long long* __restrict__ r
   if (!(*gp(w) & m)) atomicOr(w, m);
 }
 
+// The side histograms of the SLOT_PERCENTILE slots: p is the KParamsHist of a histogram instance (the only callers).
+__device__ __forceinline__ const KHist& side_hists(const KParams& p) { return static_cast<const KParamsHist&>(p).hs; }
+
+// One matched doc of global dictId `gid` in a group's histogram row (`row`: the group's first cell).  Every doc adds;
+// the result is not used, so the add is an atomic without return.
+__device__ __forceinline__ void hist_add(uint32_t* __restrict__ row, uint32_t gid) { atomicAdd(row + gid, 1u); }
+
+// DC (the template argument of the aggregate functions below): kSideNone, kSideBitmap (the DC instances: SLOT_DISTINCT
+// rows and side bitmaps) or kSideHist (the histogram instances: SLOT_PERCENTILE rows and side histograms).
+constexpr int kSideNone = 0, kSideBitmap = 1, kSideHist = 2;
+// The slot kind the instance's slot loop skips: its side structure's rows.
+template <int DC>
+__device__ __forceinline__ constexpr int side_slot_kind() { return DC == kSideHist ? SLOT_PERCENTILE : SLOT_DISTINCT; }
+
 template <int MODE>
 __device__ __forceinline__ void accumulate(uint64_t* __restrict__ base, int64_t idx, int kind, int64_t ikey,
                                            double dval) {
@@ -592,7 +606,9 @@ __device__ __forceinline__ int64_t slot_fold(int kind, int64_t a, int64_t v) {
 // fixed-point digit (fx_sum.h, KParams.fx_*) and added as an integer SUM.
 // DC (instances of plans with DISTINCTCOUNT): SLOT_DISTINCT slots are skipped by the slot loop; each aggregation's
 // column is mapped to its global dictId, whose bit is set in the group's row of the side bitmap (distinct_mark).
-template <int MODE, int NB, bool SIMPLE = false, bool FX = false, bool DC = false>
+// DC == kSideHist (instances of plans with PERCENTILE): SLOT_PERCENTILE slots are skipped likewise; each histogram's
+// column is mapped to its global dictId, whose cell of the group's histogram row takes one more doc (hist_add).
+template <int MODE, int NB, bool SIMPLE = false, bool FX = false, int DC = kSideNone>
 __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView (&S)[NB], const int64_t (&doc)[NB],
                                                 const bool (&ok)[NB], uint64_t* __restrict__ tbl, int64_t G) {
   int64_t key[NB];
@@ -644,8 +660,8 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
   int prev_col = -1;
   for (int s = 0; s < p.num_slots; ++s) {
     const int kind = p.slot_kind[s];
-    if constexpr (DC) {
-      if (kind == SLOT_DISTINCT) continue;  // the row is distinct_popcount_kernel's
+    if constexpr (DC != kSideNone) {
+      if (kind == side_slot_kind<DC>()) continue;  // the row is distinct_popcount_kernel's / percentile_select_kernel's
     }
     int64_t ikey[NB];
     double dval[NB];
@@ -707,7 +723,29 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
     for (int b = 0; b < NB; ++b)
       if (live[b]) accumulate<MODE>(tbl, (int64_t)s * G + idx[b], akind, ikey[b], dval[b]);
   }
-  if constexpr (DC) {
+  if constexpr (DC == kSideHist) {
+    // dense key spaces only: idx is the composite key in [0, G) (0 in a single-row table)
+    const KHist& H = side_hists(p);
+    for (int h = 0; h < H.n; ++h) {
+      const int col = H.col[h];
+      const int64_t W = H.stride[h];
+      uint32_t did[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        KColC& c = S[b].cols[col];
+        did[b] = gather_id(c.fwd, c.bits, ok[b] ? doc[b] : 0);
+      }
+      uint32_t g[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {  // local -> global dictId, as a group-by key's
+        KColC& c = S[b].cols[col];
+        g[b] = c.lut ? (uint32_t)gp(c.lut)[did[b]] : did[b] + (uint32_t)c.lut_off;
+      }
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+        if (live[b]) hist_add(H.cells[h] + idx[b] * W, g[b]);
+    }
+  } else if constexpr (DC == kSideBitmap) {
     // dense key spaces only: idx is the composite key in [0, G) (0 in a single-row table)
     const KDistinct& D = dc_bitmaps(p);
     for (int d = 0; d < D.n; ++d) {
@@ -866,7 +904,7 @@ __device__ __forceinline__ void accumulate16_f(uint64_t* __restrict__ row, const
 }
 
 // One half (docs H..H+15 of the lane's group) of aggregate_group.
-template <int MODE, int H, bool SIMPLE = false, bool FX = false, bool DC = false>
+template <int MODE, int H, bool SIMPLE = false, bool FX = false, int DC = kSideNone>
 __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
                                                uint64_t* __restrict__ tbl, int64_t G) {
   const uint32_t m = (mask >> H) & 0xFFFFu;
@@ -906,8 +944,8 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
       ++s;
       continue;
     }
-    if constexpr (DC) {
-      if (kind == SLOT_DISTINCT) {  // the row is distinct_popcount_kernel's (the bitmaps: below)
+    if constexpr (DC != kSideNone) {
+      if (kind == side_slot_kind<DC>()) {  // the row is distinct_popcount_kernel's (the bitmaps / histograms: below)
         ++s;
         continue;
       }
@@ -917,7 +955,7 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
     // (FX: a SLOT_SUM_FX slot reads the doubles as a float64 SUM does)
     auto is_f = [](int k) { return k == SLOT_SUM_F64 || (FX && k == SLOT_SUM_FX); };
     bool need_i = !is_f(kind), need_f = is_f(kind);
-    while (e < p.num_slots && p.slot_kind[e] != SLOT_COUNT && !(DC && p.slot_kind[e] == SLOT_DISTINCT) &&
+    while (e < p.num_slots && p.slot_kind[e] != SLOT_COUNT && !(DC != kSideNone && p.slot_kind[e] == side_slot_kind<DC>()) &&
            p.slot_col[e] == col) {
       need_i |= !is_f(p.slot_kind[e]);
       need_f |= is_f(p.slot_kind[e]);
@@ -1014,7 +1052,25 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
     }
     s = e;
   }
-  if constexpr (DC) {
+  if constexpr (DC == kSideHist) {
+    const KHist& HS = side_hists(p);
+    for (int h = 0; h < HS.n; ++h) {
+      KColC& c = S.cols[HS.col[h]];
+      const int64_t W = HS.stride[h];
+      decode_group<H>(c.fwd, c.bits, group, ids);
+      if (c.lut) {  // segment-uniform: local -> global dictId, as a group-by key's
+        gmem<int32_t>* __restrict__ lut = gp(c.lut);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ids[i] = (uint32_t)lut[ids[i]];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ids[i] += (uint32_t)c.lut_off;
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if ((m >> i) & 1u) hist_add(HS.cells[h] + (int64_t)key[i] * W, ids[i]);
+    }
+  } else if constexpr (DC == kSideBitmap) {
     const KDistinct& D = dc_bitmaps(p);
     for (int d = 0; d < D.n; ++d) {
       KColC& c = S.cols[D.col[d]];
@@ -1038,7 +1094,7 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
 // Aggregates the matched docs (bits of `mask`) of this lane's 32-doc group `group` of segment S, 16 docs at a
 // time.  Dense key spaces only (MODE_LDS / MODE_GLOBAL: composite keys < 2^31).  Docs beyond numDocs decode from
 // the zero padding to dictId 0 (in bounds) and are never in `mask`.
-template <int MODE, bool SIMPLE = false, bool FX = false, bool DC = false>
+template <int MODE, bool SIMPLE = false, bool FX = false, int DC = kSideNone>
 __device__ __forceinline__ void aggregate_group(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
                                                 uint64_t* __restrict__ tbl, int64_t G) {
   // wave-uniform conditions: the single-row (G == 1) fold inside uses cross-lane shuffles
@@ -1047,7 +1103,7 @@ __device__ __forceinline__ void aggregate_group(const KParams& p, const SegView&
 }
 
 // Drains a wave's queue of matched (segment, doc) entries: 2 per lane per batch.
-template <int MODE, bool SIMPLE = false, bool FX = false, bool DC = false>
+template <int MODE, bool SIMPLE = false, bool FX = false, int DC = kSideNone>
 __device__ __forceinline__ void flush_wave_queue(const KParams& p, const uint32_t* qd, const uint32_t* qs, uint32_t qn,
                                                  int lane, uint64_t* __restrict__ tbl, int64_t G) {
   for (uint32_t base = 0; base < qn; base += 128) {

@@ -56,8 +56,12 @@ enum OpCode : int32_t { OP_LEAF = 0, OP_AND = 1, OP_OR = 2, OP_NOT = 3 };
 // Only the DC instances of the scan see the kind (KParamsDc.slot_kind): they leave the row alone (it starts at 0) and
 // set the docs' global dictIds in the aggregation's side bitmap (KDistinct); distinct_popcount_kernel then stores the
 // per-key popcounts into the row.  To everything else the word is an int64 SUM (pgpu_plan_s::slot_dc tells them apart).
+// SLOT_PERCENTILE (plans with PERCENTILE aggregations): a row the histogram instances of the scan leave alone -- a
+// PERCENTILE aggregation's row (a float64 SUM to everything else: percentile_select_kernel stores the selected value's
+// double) or, in such a plan, a DISTINCTCOUNT row (an int64 SUM: the kernel stores the number of non-zero cells).  The
+// scan adds 1 to the cell (group, global dictId) of the column's side histogram (KHist) per matched doc.
 enum SlotKind : int32_t { SLOT_COUNT = 0, SLOT_SUM_I64 = 1, SLOT_SUM_F64 = 2, SLOT_MIN_KEY = 3, SLOT_MAX_KEY = 4,
-                          SLOT_SUM_FX = 5, SLOT_DISTINCT = 6 };
+                          SLOT_SUM_FX = 5, SLOT_DISTINCT = 6, SLOT_PERCENTILE = 7 };
 enum Mode : int32_t { MODE_LDS = 0, MODE_GLOBAL = 1, MODE_HASH = 2 };
 
 // The statistics block of one execution (KParams.stats / KStarParams.stats): kStatsWords u64, zeroed by the prologue,
@@ -240,6 +244,38 @@ struct KParamsDc : KParams {
   KDistinct dc;
 };
 
+// The side histograms of a plan with PERCENTILE aggregations, one per distinct column (its PERCENTILE aggregations of
+// every percentile share it, and in such a plan a DISTINCTCOUNT of the column does too; at most kMaxDistinct): num_keys
+// x stride[h] uint32 cells at cells[h], stride[h] = the plan's snapshot of the column's global cardinality rounded up
+// to 4 cells (rows start 16-byte aligned; the padding stays 0).  Cell key * stride[h] + gid = matched docs of group
+// `key` whose value has global dictId gid: the group's sorted values in run-length form.  col[h]: the column's record
+// index (its KCol carries the local -> global mapping).  Zeroed on the stream before every execution, written with
+// atomicAdd only (a plan's segments hold fewer than 2^32 docs: no cell wraps), read by percentile_select_kernel.
+struct KHist {
+  uint32_t* cells[kMaxDistinct];
+  int32_t stride[kMaxDistinct];
+  int32_t col[kMaxDistinct];
+  int32_t n;
+  int32_t pad;
+};
+// The parameters of the scan's histogram instances (filter_groupby_hist_kernel): KParams and the histograms.  A type
+// of its own, as KParamsFx and KParamsDc are.
+struct KParamsHist : KParams {
+  KHist hs;
+};
+// What percentile_select_kernel resolves from the histograms: per histogram the column's global values as doubles
+// (null where only a DISTINCTCOUNT reads it) and the row of its DISTINCTCOUNT (-1: none); per PERCENTILE aggregation
+// its row, its histogram and its percentile in ten-thousandths (pgpu_agg.fn bits 8..31).
+struct KPctSelect {
+  const double* values[kMaxDistinct];
+  int32_t dc_slot[kMaxDistinct];
+  int32_t npct;
+  int32_t pad;
+  int32_t pct_slot[kMaxSlots];
+  int32_t pct_hist[kMaxSlots];
+  int32_t pct_e4[kMaxSlots];
+};
+
 // The instances of the fused scan kernel (scan_direct.h), one row of kScanInstances each.  The number is what a plan
 // reports as its instance (word 15 of pgpu_plan_scan_geometry), so a row keeps its place.
 //   0 sparse        any filter program, matched docs aggregated in per-lane batches
@@ -251,11 +287,14 @@ struct KParamsDc : KParams {
 //   6, 7 FX         the sparse / dense instance of plans with SLOT_SUM_FX slots (filter_groupby_fx_kernel)
 //   8, 9 DC         the sparse / dense instance of plans with SLOT_DISTINCT slots (filter_groupby_dc_kernel); such
 //                   plans have dense key spaces, so there is none in MODE_HASH
+//   10, 11 HIST     the sparse / dense instance of plans with PERCENTILE aggregations (SLOT_PERCENTILE rows and side
+//                   histograms, filter_groupby_hist_kernel); dense key spaces again
 enum ScanVariant : int32_t { kScanSparse = 0, kScanDense, kScanDenseSimple, kScanPair, kScanFast, kScanFastWide,
-                             kScanFxSparse, kScanFxDense, kScanDcSparse, kScanDcDense };
-constexpr int kScanVariants = 10;
-// The kernel template of an instance, i.e. the parameter block it takes: KParams, KParamsFx, KParamsDc.
-enum ScanFamily : int32_t { SCAN_BASE = 0, SCAN_FX = 1, SCAN_DC = 2 };
+                             kScanFxSparse, kScanFxDense, kScanDcSparse, kScanDcDense, kScanHistSparse, kScanHistDense };
+constexpr int kScanVariants = 12;
+// The kernel template of an instance, i.e. the parameter block it takes: KParams, KParamsFx, KParamsDc, KParamsHist.
+enum ScanFamily : int32_t { SCAN_BASE = 0, SCAN_FX = 1, SCAN_DC = 2, SCAN_HIST = 3 };
+constexpr int kScanFamilies = 4;
 struct ScanInstance {
   ScanFamily family;
   uint32_t modes;                  // bit m: the instance exists in accumulator mode m
@@ -274,6 +313,8 @@ constexpr ScanInstance kScanInstances[kScanVariants] = {
     {SCAN_FX, kScanAllModes, true, false, false, false, 2},                 // kScanFxDense
     {SCAN_DC, 1u << MODE_LDS | 1u << MODE_GLOBAL, false, false, false, false, 2},  // kScanDcSparse
     {SCAN_DC, 1u << MODE_LDS | 1u << MODE_GLOBAL, true, false, false, false, 2},   // kScanDcDense
+    {SCAN_HIST, 1u << MODE_LDS | 1u << MODE_GLOBAL, false, false, false, false, 2},  // kScanHistSparse
+    {SCAN_HIST, 1u << MODE_LDS | 1u << MODE_GLOBAL, true, false, false, false, 2},   // kScanHistDense
 };
 
 // A kernel as its object hands it out: the host pointer hipLaunchKernel / the occupancy query take, and its block size.
@@ -494,10 +535,14 @@ int launch_expand_tiles(const uint8_t* segs, int32_t seg_stride, int32_t num_seg
 // The scan kernel's instance (mode, variant) of kScanInstances, or {nullptr, 0} where the table has none (a variant
 // out of range, a mode the instance does not exist in).  Launch and occupancy both resolve through it.
 KernelEntry scan_entry(int mode, int variant);
-// Launches it with its family's parameter block: p (SCAN_BASE), p then fx (SCAN_FX), p then dc (SCAN_DC).  -1 where
-// scan_entry has nothing.
-int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, int mode, int variant, int grid,
-                size_t lds_bytes, void* stream);
+// Launches it with its family's parameter block: p (SCAN_BASE), p then fx (SCAN_FX), p then dc (SCAN_DC), p then hs
+// (SCAN_HIST).  -1 where scan_entry has nothing.
+int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, const KHist& hs, int mode, int variant,
+                int grid, size_t lds_bytes, void* stream);
+// PERCENTILE's final step over table [num_slots][num_keys]: per key with docs (COUNT, row 0, not 0) row
+// sel.pct_slot[a] <- the double of the value at the aggregation's target index of the key's sorted values, read off
+// the key's histogram row; row sel.dc_slot[h] <- the row's non-zero cells.  A key without docs keeps its zeros.
+int launch_percentile_select(const KHist& hs, const KPctSelect& sel, uint64_t* table, int64_t num_keys, void* stream);
 // Row dc.slot[d] of table [num_slots][num_keys] <- per key the popcount of its words[d] bitmap words (0 where the
 // key's COUNT, row 0, is 0), for every d.
 int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_keys, void* stream);

@@ -819,7 +819,7 @@ int launch_hash_unpack(uint64_t* table, const unsigned long long* hash_keys, int
 }
 
 // The per-(family, mode) objects of the scan and of the star-tree document scan (PGPU_OBJECT_ENTRY, internal.h).  Every
-// cell is declared; the objects that do not exist (DC x HASH, a star-tree DC family) are never referenced.
+// cell is declared; the objects that do not exist (DC / HIST x HASH, a star-tree DC or HIST family) are never referenced.
 #define PGPU_MODE_DECLS(F, M)                                     \
   KernelEntry PGPU_OBJECT_ENTRY(scan, F, M)(ScanVariant variant); \
   KernelEntry PGPU_OBJECT_ENTRY(star, F, M)();
@@ -827,12 +827,14 @@ int launch_hash_unpack(uint64_t* table, const unsigned long long* hash_keys, int
 PGPU_FAMILY_DECLS(0)
 PGPU_FAMILY_DECLS(1)
 PGPU_FAMILY_DECLS(2)
+PGPU_FAMILY_DECLS(3)
 #undef PGPU_FAMILY_DECLS
 #undef PGPU_MODE_DECLS
-static KernelEntry (*const kScanObjects[3][3])(ScanVariant) = {  // [ScanFamily][Mode]
+static KernelEntry (*const kScanObjects[kScanFamilies][3])(ScanVariant) = {  // [ScanFamily][Mode]
     {scan_entry_f0_m0, scan_entry_f0_m1, scan_entry_f0_m2},
     {scan_entry_f1_m0, scan_entry_f1_m1, scan_entry_f1_m2},
-    {scan_entry_f2_m0, scan_entry_f2_m1, nullptr}};
+    {scan_entry_f2_m0, scan_entry_f2_m1, nullptr},
+    {scan_entry_f3_m0, scan_entry_f3_m1, nullptr}};
 static KernelEntry (*const kStarObjects[2][3])() = {  // [fx][Mode]
     {star_entry_f0_m0, star_entry_f0_m1, star_entry_f0_m2}, {star_entry_f1_m0, star_entry_f1_m1, star_entry_f1_m2}};
 
@@ -855,12 +857,13 @@ KernelEntry scan_entry(int mode, int variant) {
   return kScanObjects[I.family][mode]((ScanVariant)variant);
 }
 
-int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, int mode, int variant, int grid,
-                size_t lds_bytes, void* stream) {
+int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, const KHist& hs, int mode, int variant,
+                int grid, size_t lds_bytes, void* stream) {
   const KernelEntry e = scan_entry(mode, variant);
   if (!e.fn) return -1;
   KParamsFx kf;
   KParamsDc kd;
+  KParamsHist kh;
   switch (kScanInstances[variant].family) {
     case SCAN_FX:
       static_cast<KParams&>(kf) = p;
@@ -871,6 +874,11 @@ int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, int m
       static_cast<KParams&>(kd) = p;
       kd.dc = dc;
       return launch_entry(e, grid, lds_bytes, stream, &kd);
+    case SCAN_HIST:
+      if (hs.n <= 0 || hs.n > kMaxDistinct) return -1;
+      static_cast<KParams&>(kh) = p;
+      kh.hs = hs;
+      return launch_entry(e, grid, lds_bytes, stream, &kh);
     default:
       return launch_entry(e, grid, lds_bytes, stream, &p);
   }
@@ -906,6 +914,141 @@ int launch_distinct_popcount(const KDistinct& dc, uint64_t* table, int64_t num_k
   int64_t grid = (num_keys + 3) / 4;
   if (grid > 16384) grid = 16384;
   hipLaunchKernelGGL(distinct_popcount_kernel, dim3((unsigned)grid), dim3(256), 0, S(stream), dc, table, num_keys);
+  return PGPU_HIP_OK(hipGetLastError());
+}
+
+// The target index of a percentile in a group's sorted values, as PercentileAggregationFunction.extractFinalResult
+// (:152-165) computes it: size - 1 for the 100th, else (int)((double)size * p / 100.0) in IEEE double arithmetic (each
+// operation rounded on its own: 10000 docs at p = 0.57 give 56, as 10000 * 0.57 is 5699.99...), p = p_e4 / 10000.0
+// being the double of the decimal literal.  (int) saturates as Java's cast does; the index stays below size.
+__device__ __forceinline__ int64_t percentile_index(int64_t size, int32_t p_e4) {
+  if (p_e4 >= 1000000) return size - 1;
+  const double p = __ddiv_rn((double)p_e4, 10000.0);
+  const double x = __ddiv_rn(__dmul_rn((double)size, p), 100.0);
+  const int64_t r = x >= 2147483647.0 ? (int64_t)2147483647 : (int64_t)x;
+  return r < size - 1 ? r : size - 1;
+}
+
+// PERCENTILE's final step (and, in such a plan, DISTINCTCOUNT's): one wave per key walks the key's histogram row of
+// each column in ascending global dictId -- the sorted values in run-length form.  A step covers kPctStepCells = 256
+// cells, one 16-byte load of 4 cells per lane (rows start 16-byte aligned and are padded to 4 cells with zeros); the
+// loads of kPctBatch = 8 steps are issued together, so the walk waits for memory once per 2048 cells, not once per
+// step (a wave's walk is one dependent chain: with one load in flight C3's 100 000-cell rows took 396 us, §6.6).  Per
+// step: the lane's 4-cell sum, a wave-wide inclusive prefix sum, the running total of the steps before.  An aggregation of
+// target index r resolves in the step whose running total first exceeds r: the selected dictId is the smallest g with
+// sum(cells[0..g]) > r; lane 0 reads the column's global value of g as a double and stores it into the aggregation's
+// row.  All percentiles of a column resolve in the one walk, which ends (wave-uniformly) with the step that resolves
+// the last one, unless a DISTINCTCOUNT of the column counts the row's non-zero cells to its end.  A key without docs
+// (COUNT 0) reads and stores nothing.  No LDS.  Bytes: at most G x stride x 4 read per column, G x 8 written per row.
+constexpr int kPctStepCells = 256;
+constexpr int kPctBatch = 8;
+__global__ __launch_bounds__(256) void percentile_select_kernel(const KHist hs, const KPctSelect sel,
+                                                                uint64_t* __restrict__ table, int64_t num_keys) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t key = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); key < num_keys; key += nwaves) {
+    const int64_t size = (int64_t)table[key];  // the COUNT row: wave-uniform
+    if (size <= 0) continue;
+    for (int h = 0; h < hs.n; ++h) {
+      uint32_t pending = 0;  // this column's aggregations still to resolve (bit a; npct <= kMaxSlots = 24)
+      for (int a = 0; a < sel.npct; ++a)
+        if (sel.pct_hist[a] == h) pending |= 1u << a;
+      const bool count_cells = sel.dc_slot[h] >= 0;
+      if (!pending && !count_cells) continue;
+      const int stride = hs.stride[h];
+      const uint4* __restrict__ row = reinterpret_cast<const uint4*>(hs.cells[h] + key * (int64_t)stride);
+      const int nvec = stride >> 2;
+      int64_t before = 0;  // docs in the cells of the steps before
+      int64_t nonzero = 0;
+      // the smallest outstanding target index: a step whose running total stays at or below it resolves nothing
+      auto smallest = [&](uint32_t outstanding) {
+        int64_t m = INT64_MAX;
+        for (; outstanding; outstanding &= outstanding - 1) {
+          const int64_t r = percentile_index(size, sel.pct_e4[__ffs(outstanding) - 1]);
+          m = r < m ? r : m;
+        }
+        return m;
+      };
+      int64_t min_r = smallest(pending);
+      for (int b0 = 0; b0 < nvec && (pending || count_cells); b0 += 64 * kPctBatch) {
+        uint4 batch[kPctBatch];
+#pragma unroll
+        for (int j = 0; j < kPctBatch; ++j) {
+          const int vi = b0 + j * 64 + lane;
+          batch[j] = vi < nvec ? row[vi] : make_uint4(0, 0, 0, 0);
+        }
+        // a batch whose cells hold no outstanding target is summed as a whole (one wave reduction), not step by step:
+        // the prefix sums below are a chain of cross-lane moves, the walk's cost once the loads overlap
+        int64_t lane_docs = 0;
+#pragma unroll
+        for (int j = 0; j < kPctBatch; ++j) {
+          lane_docs += (int64_t)batch[j].x + batch[j].y + batch[j].z + batch[j].w;
+          if (count_cells)
+            nonzero += (batch[j].x != 0) + (batch[j].y != 0) + (batch[j].z != 0) + (batch[j].w != 0);
+        }
+        const int64_t batch_docs = wave_sum_i64(lane_docs);
+        if (min_r - before >= batch_docs) {  // wave-uniform (also when nothing is pending: min_r is INT64_MAX)
+          before += batch_docs;
+          continue;
+        }
+#pragma unroll
+        for (int j = 0; j < kPctBatch; ++j) {
+          const int v0 = b0 + j * 64;
+          if (v0 >= nvec || !pending) break;  // wave-uniform
+          const uint4 c = batch[j];
+          const int64_t mine = (int64_t)c.x + c.y + c.z + c.w;
+          int64_t incl = mine;  // inclusive prefix sum over the lanes
+#pragma unroll
+          for (int o = 1; o < 64; o <<= 1) {
+            const int64_t up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+          }
+          const int64_t total = __shfl(incl, 63);
+          for (uint32_t todo = min_r - before < total ? pending : 0u; todo;) {
+            const int a = __ffs(todo) - 1;
+            todo &= todo - 1;
+            const int64_t r = percentile_index(size, sel.pct_e4[a]) - before;  // within this step's cells when < total
+            if (r >= total) continue;
+            pending &= ~(1u << a);
+            min_r = smallest(pending);
+            // the first lane whose inclusive sum exceeds r holds the cell
+            const unsigned long long over = __ballot(incl > r);
+            const int src = __ffsll(over) - 1;
+            int64_t skip = incl - mine;  // docs before this lane's cells
+            int g = (v0 + lane) * 4;
+            if (r >= skip + c.x) { skip += c.x; ++g;
+              if (r >= skip + c.y) { skip += c.y; ++g;
+                if (r >= skip + c.z) ++g; } }
+            g = __shfl(g, src);
+            if (lane == 0) {
+              const double val = sel.values[h][g];
+              table[(int64_t)sel.pct_slot[a] * num_keys + key] = (uint64_t)__double_as_longlong(val);
+            }
+          }
+          before += total;
+        }
+      }
+      if (count_cells) {
+        nonzero = wave_sum_i64(nonzero);
+        if (lane == 0) table[(int64_t)sel.dc_slot[h] * num_keys + key] = (uint64_t)nonzero;
+      }
+    }
+  }
+}
+
+int launch_percentile_select(const KHist& hs, const KPctSelect& sel, uint64_t* table, int64_t num_keys, void* stream) {
+  if (hs.n <= 0 || num_keys <= 0) return 0;
+  if (hs.n > kMaxDistinct || sel.npct < 0 || sel.npct > kMaxSlots || !table) return -1;
+  for (int h = 0; h < hs.n; ++h)
+    if (!hs.cells[h] || hs.stride[h] <= 0 || (hs.stride[h] & 3) || sel.dc_slot[h] == 0 || sel.dc_slot[h] >= kMaxSlots)
+      return -1;
+  for (int a = 0; a < sel.npct; ++a)
+    if (sel.pct_slot[a] <= 0 || sel.pct_slot[a] >= kMaxSlots || sel.pct_hist[a] < 0 || sel.pct_hist[a] >= hs.n ||
+        !sel.values[sel.pct_hist[a]] || sel.pct_e4[a] < 0 || sel.pct_e4[a] > 1000000)
+      return -1;
+  int64_t grid = (num_keys + 3) / 4;
+  if (grid > 16384) grid = 16384;
+  hipLaunchKernelGGL(percentile_select_kernel, dim3((unsigned)grid), dim3(256), 0, S(stream), hs, sel, table, num_keys);
   return PGPU_HIP_OK(hipGetLastError());
 }
 

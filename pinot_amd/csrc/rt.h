@@ -698,6 +698,28 @@ struct pgpu_plan_s {
   std::vector<Distinct> dc;
   std::vector<int32_t> slot_dc;
   std::vector<KeyLut> dc_lut;
+  // PERCENTILE aggregations.  pct: one entry per aggregation -- its own row of the group table (slot_kind says
+  // SLOT_SUM_F64: after percentile_select_kernel the row holds the selected values' doubles; the histogram scan
+  // instances alone see SLOT_PERCENTILE), its histogram and its percentile in ten-thousandths.  hist: one side
+  // histogram per distinct column, num_keys x stride uint32 cells (stride: the snapshot's cardinality rounded up to 4),
+  // shared by the column's percentiles; a plan with a PERCENTILE keeps histograms only, so the columns of its
+  // DISTINCTCOUNT aggregations (dc, whose bitmaps such a plan never allocates) get one too and dc_slot names their row.
+  // values: the snapshot's values as doubles on the device ((double) of an INT / LONG value; none for a column only a
+  // DISTINCTCOUNT reads).  slot_pct: per slot its pct entry, -1 for every other slot.  hist_lut: [segment][histogram]
+  // the local -> global dictId mapping as planned, as dc_lut.
+  struct Percentile { int32_t slot = 0, hist = 0, p_e4 = 0; };
+  struct Hist {
+    int32_t tcol = 0, qcol = 0, dc_slot = -1;
+    int64_t card = 0, stride = 0;
+    std::shared_ptr<const Dict> dict;
+    std::shared_ptr<DevMem> values;
+  };
+  std::vector<Percentile> pct;
+  std::vector<Hist> hist;
+  std::vector<int32_t> slot_pct;
+  std::vector<KeyLut> hist_lut;
+  // a row the scan leaves to a post-scan kernel (distinct_popcount_kernel / percentile_select_kernel): reads no values
+  bool side_slot(size_t s) const { return slot_dc[s] >= 0 || slot_pct[s] >= 0; }
   std::vector<int32_t> agg_fn, agg_slot, agg_col;   // per aggregation: fn, value slot (or -1), table column
   int num_projected = 0;
   // per-segment compiled data
@@ -859,7 +881,7 @@ inline bool result_fx_local(const pgpu_result_s* r) { return !r->fx_agreed && re
 // other cross-GPU or external-merge entry point declines them (distinct_decline).
 inline bool query_has_distinct(const pgpu_query* q) {
   for (int i = 0; q && q->aggs && i < q->num_aggs; ++i)
-    if (q->aggs[i].fn == PGPU_AGG_DISTINCTCOUNT) return true;
+    if (PGPU_AGG_FN(q->aggs[i].fn) == PGPU_AGG_DISTINCTCOUNT) return true;
   return false;
 }
 inline bool plan_has_distinct(const pgpu_plan_s* P) {
@@ -874,6 +896,26 @@ inline bool result_has_distinct(const pgpu_result_s* r) {
 inline int distinct_decline(const char* what) {
   return fail(PGPU_ERR_UNSUPPORTED, "%s with DISTINCTCOUNT: per-rank distinct counts do not add (the value sets would "
                          "have to be merged)", what);
+}
+// Plans / results with PERCENTILE aggregations: every cross-GPU or external-merge entry point declines them
+// (percentile_decline) -- a rank's percentiles do not merge, and the histogram all-reduce that would is not built.
+inline bool query_has_percentile(const pgpu_query* q) {
+  for (int i = 0; q && q->aggs && i < q->num_aggs; ++i)
+    if (PGPU_AGG_FN(q->aggs[i].fn) == PGPU_AGG_PERCENTILE) return true;
+  return false;
+}
+inline bool plan_has_percentile(const pgpu_plan_s* P) {
+  if (!P->pct.empty()) return true;
+  for (const auto& part : P->parts)
+    if (part.plan && !part.plan->pct.empty()) return true;
+  return false;
+}
+inline bool result_has_percentile(const pgpu_result_s* r) {
+  return std::find(r->agg_fn.begin(), r->agg_fn.end(), (int32_t)PGPU_AGG_PERCENTILE) != r->agg_fn.end();
+}
+inline int percentile_decline(const char* what) {
+  return fail(PGPU_ERR_UNSUPPORTED, "%s with PERCENTILE: per-rank percentiles do not merge (the value histograms would "
+                         "have to be added)", what);
 }
 inline int fx_decline(const char* what) {
   return fail(PGPU_ERR_UNSUPPORTED, "%s with PGPU_OPT_EXACT_FP_SUM: the ranks would have to agree on the "
@@ -950,6 +992,8 @@ int sorted_search(const std::vector<T>& a, T v) {
 struct ExecCtx {
   KParams kp;
   KDistinct dc{};  // the side bitmaps of the plan's DISTINCTCOUNT aggregations (n = 0: none)
+  KHist hs{};      // the side histograms of a plan with PERCENTILE aggregations (n = 0: none; then dc.n = 0)
+  KPctSelect sel{};  // ... and what percentile_select_kernel resolves from them
   // PGPU_TRACE=1: host time marks of the execution, printed when it took over a millisecond
   std::vector<std::pair<const char*, double>> marks;
   void mark(const char* what) { if (trace_on()) marks.emplace_back(what, now_us()); }

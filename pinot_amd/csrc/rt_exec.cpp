@@ -365,6 +365,10 @@ static void fill_kparams(const pgpu_plan_s* P, uint64_t deadline, ExecCtx& X) {
   for (int sl = 0; sl < nslots && P->fx; ++sl)  // the scan's view of the fixed-point digits (fx_split has the rest)
     if (P->slot_fx[sl] >= 0) kp.slot_kind[sl] = SLOT_SUM_FX;
   for (const pgpu_plan_s::Distinct& d : P->dc) kp.slot_kind[d.slot] = SLOT_DISTINCT;  // (X.dc has the bitmaps)
+  if (!P->pct.empty()) {  // histograms only (X.hs): the rows the post-scan kernel writes, DISTINCTCOUNT's among them
+    for (const pgpu_plan_s::Distinct& d : P->dc) kp.slot_kind[d.slot] = SLOT_PERCENTILE;
+    for (const pgpu_plan_s::Percentile& e : P->pct) kp.slot_kind[e.slot] = SLOT_PERCENTILE;
+  }
   kp.pair_leaves = 1;
   dense_lds_forms(P, &kp.pack_slot, &kp.narrow);
   kp.pack_shift = P->pack_shift;
@@ -373,8 +377,12 @@ static void fill_kparams(const pgpu_plan_s* P, uint64_t deadline, ExecCtx& X) {
 
 // DISTINCTCOUNT: the aggregations' side bitmaps (X.dc), back to back in the arena's buffer and zeroed on the stream
 // for this execution.
+static int exec_histograms(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X);
 static int exec_distinct_bitmaps(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
   memset(&X.dc, 0, sizeof X.dc);
+  memset(&X.hs, 0, sizeof X.hs);
+  memset(&X.sel, 0, sizeof X.sel);
+  if (!P->pct.empty()) return exec_histograms(P, stream, X);  // a plan with a PERCENTILE keeps histograms only
   if (P->dc.empty()) return 0;
   if (P->mode == MODE_HASH || (int)P->dc.size() > kMaxDistinct)
     return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT outside the dense group tables");
@@ -393,6 +401,39 @@ static int exec_distinct_bitmaps(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X)
     X.dc.col[i] = d.qcol;
     X.dc.slot[i] = d.slot;
     off += P->num_keys * d.words;
+  }
+  return 0;
+}
+
+// PERCENTILE: the side histograms (X.hs) and what the selection kernel resolves from them (X.sel).  The histograms lie
+// back to back in the arena's buffer for side structures (rows 16-byte aligned: strides are multiples of 4 cells)
+// and are zeroed on the stream for this execution.
+static int exec_histograms(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
+  if (P->mode == MODE_HASH || (int)P->hist.size() > kMaxDistinct || (int)P->pct.size() > kMaxSlots)
+    return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE outside the dense group tables");
+  Scratch* sc = P->scratch;
+  int64_t cells = 0;
+  for (const pgpu_plan_s::Hist& h : P->hist) cells += P->num_keys * h.stride;
+  if (cells * 4 > kDistinctMaxBytes) return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE histograms above the cap");
+  TRY(sc->dc_bits.ensure((size_t)cells * 4));
+  HIP_TRY(hipMemsetAsync(sc->dc_bits.p, 0, (size_t)cells * 4, stream));
+  int64_t off = 0;
+  X.hs.n = (int32_t)P->hist.size();
+  for (size_t i = 0; i < P->hist.size(); ++i) {
+    const pgpu_plan_s::Hist& h = P->hist[i];
+    X.hs.cells[i] = sc->dc_bits.as<uint32_t>() + off;
+    X.hs.stride[i] = (int32_t)h.stride;
+    X.hs.col[i] = h.qcol;
+    X.sel.values[i] = h.values ? reinterpret_cast<const double*>(h.values->p) : nullptr;
+    X.sel.dc_slot[i] = h.dc_slot;
+    off += P->num_keys * h.stride;
+  }
+  for (size_t i = P->hist.size(); i < (size_t)kMaxDistinct; ++i) X.sel.dc_slot[i] = -1;
+  X.sel.npct = (int32_t)P->pct.size();
+  for (size_t a = 0; a < P->pct.size(); ++a) {
+    X.sel.pct_slot[a] = P->pct[a].slot;
+    X.sel.pct_hist[a] = P->pct[a].hist;
+    X.sel.pct_e4[a] = P->pct[a].p_e4;
   }
   return 0;
 }
@@ -805,7 +846,7 @@ static int launch_scan_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, KPa
   P->last_scan.alone = P->alone;
   P->last_scan.declined = !fits;
   // (the instance's family takes what it needs: the split of the fixed-point slots, the side bitmaps, or neither)
-  if (launch_scan(kp, fx_split(P), X.dc, P->mode, P->variant, grid, P->lds_bytes, stream))
+  if (launch_scan(kp, fx_split(P), X.dc, X.hs, P->mode, P->variant, grid, P->lds_bytes, stream))
     return fail(PGPU_ERR_DEVICE, "scan launch failed: %s", hipGetErrorString(hipGetLastError()));
   X.mark("scan launched");
   if (wg_times) TRY(diag_wg_times_report(P->table, kp, grid, stream));
@@ -997,6 +1038,10 @@ int exec_epilogue(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
   // DISTINCTCOUNT: the table is whole (slabs folded) -- its rows take the per-key popcounts of the side bitmaps
   if (X.dc.n > 0 && launch_distinct_popcount(X.dc, X.table, P->num_keys, stream))
     return fail(PGPU_ERR_DEVICE, "distinct popcount launch failed: %s", hipGetErrorString(hipGetLastError()));
+  // PERCENTILE: likewise -- its rows take the values selected from the side histograms (and DISTINCTCOUNT's the
+  // non-zero cells)
+  if (X.hs.n > 0 && launch_percentile_select(X.hs, X.sel, X.table, P->num_keys, stream))
+    return fail(PGPU_ERR_DEVICE, "percentile selection launch failed: %s", hipGetErrorString(hipGetLastError()));
   if (X.leap_nsegs > 0 &&  // deferred but no fold ran (cannot happen for a plan with scan tiles; kept exact)
       launch_leap2_compose(X.leap_segs, P->seg_stride, X.leap_nsegs, kp.leap_maps, kp.stats, stream))
     return fail(PGPU_ERR_DEVICE, "filter statistics launch failed: %s", hipGetErrorString(hipGetLastError()));

@@ -422,6 +422,10 @@ void describe_result(const pgpu_plan_s* P, pgpu_result_s* R) {
     const int fn = P->agg_fn[a];
     if (fn == PGPU_AGG_COUNT) continue;  // CountAggregationFunction: exact count (held as double by Pinot)
     if (fn == PGPU_AGG_DISTINCTCOUNT) continue;  // the set's size (DistinctCountAggregationFunction.extractFinalResult)
+    if (fn == PGPU_AGG_PERCENTILE) {  // the selected value's double (percentile_select_kernel)
+      R->agg_conv[a] = RCONV_F64;
+      continue;
+    }
     if (fn == PGPU_AGG_SUM || fn == PGPU_AGG_AVG)
       R->agg_conv[a] = P->slot_kind[P->agg_slot[a]] == SLOT_SUM_I64 ? RCONV_I64 : RCONV_F64;
     else

@@ -21,6 +21,7 @@ struct PlanCtx {
   std::vector<int> qcol_key;   // per query column: its group-by key index (-1: none)
   std::vector<char> qcol_val;  // ... and whether an accumulator reads its values
   std::vector<int> qcol_dc;    // ... and its DISTINCTCOUNT entry (pgpu_plan_s::dc; -1: none)
+  std::vector<int> qcol_hist;  // ... and its histogram (pgpu_plan_s::hist; -1: none)
   std::vector<int> perm;       // order_leaves: evaluation position -> predicate
   double t_start = 0, tr[8] = {0};  // trace marks
   int ntr = 0;
@@ -156,12 +157,13 @@ void push_slot(pgpu_plan_s* P, int kind, int tcol, int fx_digit, const FxFormat&
   P->slot_fx.push_back(fx_digit);
   P->slot_fmt.push_back(fmt);
   P->slot_dc.push_back(-1);
+  P->slot_pct.push_back(-1);
 }
 
 // The slot of (kind, tcol), shared by the aggregations that need the same one.
 int add_slot(pgpu_plan_s* P, int kind, int tcol) {
   for (size_t s = 1; s < P->slot_kind.size(); ++s)
-    if (P->slot_kind[s] == kind && P->slot_tcol[s] == tcol && P->slot_fx[s] < 0 && P->slot_dc[s] < 0) return (int)s;
+    if (P->slot_kind[s] == kind && P->slot_tcol[s] == tcol && P->slot_fx[s] < 0 && !P->side_slot(s)) return (int)s;
   push_slot(P, kind, tcol, -1, FxFormat{});
   return (int)P->slot_kind.size() - 1;
 }
@@ -179,6 +181,31 @@ int add_distinct_slot(pgpu_plan_s* P, int tcol) {
   P->slot_dc[d.slot] = (int32_t)P->dc.size();
   P->dc.push_back(d);
   return d.slot;
+}
+
+// The histogram of table column tcol in a plan with PERCENTILE aggregations, shared by everything that reads the column.
+int add_hist(pgpu_plan_s* P, int tcol) {
+  for (size_t h = 0; h < P->hist.size(); ++h)
+    if (P->hist[h].tcol == tcol) return (int)h;
+  pgpu_plan_s::Hist h;
+  h.tcol = tcol;
+  h.qcol = query_col(P, tcol);
+  P->hist.push_back(h);
+  return (int)P->hist.size() - 1;
+}
+
+// The row of one PERCENTILE aggregation (its own: two percentiles of a column are two rows over one histogram): an
+// ordinary row of the group table that starts at 0 and that the scan never touches -- SLOT_SUM_F64 to everything but
+// the histogram scan instances (rt.h pct).
+int add_percentile_slot(pgpu_plan_s* P, int tcol, int32_t p_e4) {
+  push_slot(P, SLOT_SUM_F64, tcol, -1, FxFormat{});
+  pgpu_plan_s::Percentile e;
+  e.slot = (int32_t)P->slot_kind.size() - 1;
+  e.hist = add_hist(P, tcol);
+  e.p_e4 = p_e4;
+  P->slot_pct[e.slot] = (int32_t)P->pct.size();
+  P->pct.push_back(e);
+  return e.slot;
 }
 
 // The W digit slots of a fixed-point sum: adjacent, of the one column, shared by SUM and AVG of the column.
@@ -224,7 +251,7 @@ int agg_slot_for(PlanCtx& cx, int i, int* slot) {
   const pgpu_agg& a = q->aggs[i];
   const int type = cx.t->types[a.column];
   int kind;
-  switch (a.fn) {
+  switch (PGPU_AGG_FN(a.fn)) {
     case PGPU_AGG_SUM: case PGPU_AGG_AVG: {
       // Integer columns sum exactly in int64 unless the plan could overflow it: |sum| <= sum over segments of
       // numDocs x max |value| (the sorted dictionary's ends).  Past 2^62 the slot accumulates the doubles of
@@ -266,11 +293,28 @@ int assign_slots(PlanCtx& cx) {
   }
   for (int i = 0; i < q->num_aggs; ++i) {
     const pgpu_agg& a = q->aggs[i];
-    P->agg_fn.push_back(a.fn);
+    // the function code (bits 0..7; a PERCENTILE carries its percentile above them, codes 0..5 nothing)
+    const int fn = PGPU_AGG_FN(a.fn);
+    if (fn != PGPU_AGG_PERCENTILE && a.fn != fn) return fail(PGPU_ERR_UNSUPPORTED, "aggregation function %d", a.fn);
+    P->agg_fn.push_back(fn);
     P->agg_col.push_back(a.column);
-    if (a.fn == PGPU_AGG_COUNT) { P->agg_slot.push_back(0); continue; }
+    if (fn == PGPU_AGG_COUNT) { P->agg_slot.push_back(0); continue; }
     if (a.column < 0 || a.column >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: bad column", i);
-    if (a.fn == PGPU_AGG_DISTINCTCOUNT) {  // any column type: the set is over dictIds
+    if (fn == PGPU_AGG_PERCENTILE) {
+      const int32_t p_e4 = PGPU_AGG_PERCENTILE_E4(a.fn);
+      if (p_e4 > PGPU_AGG_PERCENTILE_MAX_E4)
+        return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: PERCENTILE of %d ten-thousandths, above 100", i, p_e4);
+      if (q->options & PGPU_OPT_EXACT_FP_SUM)
+        return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE with PGPU_OPT_EXACT_FP_SUM");
+      if (cx.t->types[a.column] == PGPU_STRING)
+        return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE over STRING column %d", a.column);
+      for (const Segment* s : P->segs)
+        if (s->cols[a.column].raw)
+          return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE over raw (no-dictionary) column %d", a.column);
+      P->agg_slot.push_back(add_percentile_slot(P, a.column, p_e4));
+      continue;
+    }
+    if (fn == PGPU_AGG_DISTINCTCOUNT) {  // any column type: the set is over dictIds
       if (q->options & PGPU_OPT_EXACT_FP_SUM)
         return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT with PGPU_OPT_EXACT_FP_SUM");
       for (const Segment* s : P->segs)
@@ -302,6 +346,20 @@ int assign_slots(PlanCtx& cx) {
     if ((int)P->dc.size() > kMaxDistinct)
       return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT over more than %d columns in one query", kMaxDistinct);
     if (P->first_doc_slot) return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT in a numGroupsLimit (composite) plan");
+    P->cfg.partitioned_group_by = 0;
+    P->cfg.hash_partitions = 0;
+    P->cfg.stream_chunks = 1;
+  }
+  if (!P->pct.empty()) {
+    // histograms only: the plan's DISTINCTCOUNT columns are counted from one too (the non-zero cells of a row)
+    for (const pgpu_plan_s::Distinct& d : P->dc) P->hist[add_hist(P, d.tcol)].dc_slot = d.slot;
+    if ((int)P->hist.size() > kMaxDistinct)
+      return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE: more than %d side columns (histograms) in one query", kMaxDistinct);
+    if (P->first_doc_slot) return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE in a numGroupsLimit (composite) plan");
+    long double docs = 0;
+    for (const Segment* s : P->segs) docs += (long double)s->num_docs;
+    if (docs >= 4294967296.0L)
+      return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE over segments of 2^32 docs or more (a histogram cell could wrap)");
     P->cfg.partitioned_group_by = 0;
     P->cfg.hash_partitions = 0;
     P->cfg.stream_chunks = 1;
@@ -344,10 +402,11 @@ int plan_segment_arrays(PlanCtx& cx) {
   pgpu_plan_s* P = cx.P;
   const hipStream_t stream = t->stream;
   const size_t nk = P->key_cols.size();
-  const size_t nd = P->dc.size();
+  const size_t nd = P->dc.size(), nh = P->hist.size();
   P->key_lut.resize(P->segs.size() * nk);
   P->dc_lut.resize(P->segs.size() * nd);
-  P->refs->luts.reserve(P->segs.size() * (nk + nd));
+  P->hist_lut.resize(P->segs.size() * nh);
+  P->refs->luts.reserve(P->segs.size() * (nk + nd + nh));
   for (size_t i = 0; i < P->segs.size(); ++i) {
     Segment* s = P->segs[i];
     for (size_t j = 0; j < nk; ++j) {
@@ -360,7 +419,7 @@ int plan_segment_arrays(PlanCtx& cx) {
       kl.off = col.lut_off;
     }
     for (size_t k = 1; k < P->slot_kind.size(); ++k)
-      if (P->slot_tcol[k] != kDocIdColumn && P->slot_dc[k] < 0) TRY(ensure_values(t, *s, P->slot_tcol[k], stream));
+      if (P->slot_tcol[k] != kDocIdColumn && !P->side_slot(k)) TRY(ensure_values(t, *s, P->slot_tcol[k], stream));
     if (P->first_doc_slot) TRY(ensure_docid(t, s->num_docs, stream));
   }
   // the distinct columns' local -> global mapping, as a key column's (after the key LUTs: plan_star_segment indexes
@@ -375,6 +434,42 @@ int plan_segment_arrays(PlanCtx& cx) {
       kl.lut = col.lut_off >= 0 ? nullptr : reinterpret_cast<const int32_t*>(col.lut->p);
       kl.off = col.lut_off;
     }
+  // ... and the histogram columns' (of the same snapshot where a column has both)
+  for (size_t i = 0; i < P->segs.size(); ++i)
+    for (size_t h = 0; h < nh; ++h) {
+      const int c = P->hist[h].tcol;
+      TRY(ensure_lut(t, *P->segs[i], c, stream));
+      const Column& col = P->segs[i]->cols[c];
+      P->refs->luts.push_back(col.lut);
+      KeyLut& kl = P->hist_lut[i * nh + h];
+      kl.lut = col.lut_off >= 0 ? nullptr : reinterpret_cast<const int32_t*>(col.lut->p);
+      kl.off = col.lut_off;
+    }
+  return 0;
+}
+
+// (under the table mutex) the values percentile_select_kernel reads: each histogram column's snapshot of the global
+// dictionary as doubles -- (double)value of an INT / LONG column (PercentileAggregationFunction reads
+// getDoubleValuesSV), the value of a FLOAT / DOUBLE one.  A column that only a DISTINCTCOUNT reads has none.
+int plan_hist_values(PlanCtx& cx) {
+  pgpu_table_s* t = cx.t;
+  pgpu_plan_s* P = cx.P;
+  for (size_t h = 0; h < P->hist.size(); ++h) {
+    pgpu_plan_s::Hist& H = P->hist[h];
+    bool wanted = false;
+    for (const pgpu_plan_s::Percentile& e : P->pct) wanted |= e.hist == (int32_t)h;
+    if (!wanted) continue;
+    std::vector<double> v((size_t)H.card, 0.0);
+    if (is_int_type(H.dict->type))
+      for (size_t i = 0; i < H.dict->iv.size(); ++i) v[i] = (double)H.dict->iv[i];
+    else
+      for (size_t i = 0; i < H.dict->dv.size(); ++i) v[i] = H.dict->dv[i];
+    auto m = std::make_shared<DevMem>();
+    HIP_TRY(hipMalloc(&m->p, sizeof(double) * v.size()));
+    HIP_TRY(hipMemcpyAsync(m->p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    H.values = std::move(m);
+  }
   return 0;
 }
 
@@ -386,7 +481,7 @@ int plan_global_values(PlanCtx& cx) {
   P->val_cols.clear();
   for (size_t k = 1; k < P->slot_kind.size(); ++k) {
     const int c = P->slot_tcol[k];
-    if (P->slot_dc[k] >= 0) continue;  // a DISTINCTCOUNT row reads no values
+    if (P->side_slot(k)) continue;  // a DISTINCTCOUNT / PERCENTILE row reads no values in the scan
     if (c == kDocIdColumn || std::find(P->val_cols.begin(), P->val_cols.end(), c) != P->val_cols.end()) continue;
     bool any = false;
     for (Segment* s : P->segs) {
@@ -438,8 +533,14 @@ int build_device_arrays(PlanCtx& cx) {
     d.card = std::max<int64_t>((int64_t)d.dict->size(), 1);
     d.words = (d.card + 63) / 64;
   }
+  for (pgpu_plan_s::Hist& h : P->hist) {  // the histogram's width, likewise
+    h.dict = t->global[h.tcol];
+    h.card = std::max<int64_t>((int64_t)h.dict->size(), 1);
+    h.stride = (h.card + 3) & ~int64_t(3);
+  }
   TRY(plan_segment_arrays(cx));
   TRY(plan_global_values(cx));
+  TRY(plan_hist_values(cx));
   P->docid_fwd = t->d_docid_fwd;
   P->docid_key = t->d_docid_key;
   P->docid_bits = t->docid_bits;
@@ -625,6 +726,17 @@ void choose_table_mode(PlanCtx& cx) {
 // most kDistinctMaxBytes in all.
 int check_distinct_shape(const PlanCtx& cx) {
   const pgpu_plan_s* P = cx.P;
+  if (!P->pct.empty()) {  // histograms only (those of the plan's DISTINCTCOUNT columns among them)
+    if (P->mode == MODE_HASH)
+      return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE over a key space that takes the hash table (%s)",
+                  P->stage_end.empty() ? "past 2^26 keys" : "ARRAY_MAP stages");
+    long double bytes = 0;
+    for (const pgpu_plan_s::Hist& h : P->hist) bytes += (long double)P->num_keys * (long double)h.stride * 4.0L;
+    if (bytes > (long double)kDistinctMaxBytes)
+      return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE histograms of %.0Lf bytes (%lld keys), above the cap of %lld", bytes,
+                  (long long)P->num_keys, (long long)kDistinctMaxBytes);
+    return 0;
+  }
   if (P->dc.empty()) return 0;
   if (P->mode == MODE_HASH)
     return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT over a key space that takes the hash table (%s)",
@@ -653,7 +765,7 @@ int prepare_translation(PlanCtx& cx) {
     TRY(parse_predicate(t->types[q->predicates[l].column], q->predicates[l], &cx.parsed[l]));
   // (DISTINCTCOUNT: StarTreeUtils finds no function-column pair for it -- such a plan scans)
   cx.star_allowed = q->num_group_by > 0 && !(q->options & PGPU_OPT_NO_STAR_TREE) && P->stage_end.empty() &&
-                    P->dc.empty() && star_composites(P->ops, q, &cx.star_comps);
+                    P->dc.empty() && P->pct.empty() && star_composites(P->ops, q, &cx.star_comps);
   // Aggregation-only over a match-all segment: COUNT-only is answered from metadata, MIN / MAX / DISTINCTCOUNT-only
   // from the dictionaries (AggregationPlanNode.java:165-183, isFitForDictionaryBasedPlan :233-246; every dictionary
   // value occurs in its segment, so the scan gives the same set) -- same values, numEntriesScannedPostFilter 0
@@ -661,6 +773,7 @@ int prepare_translation(PlanCtx& cx) {
   if (q->num_group_by == 0 && q->num_aggs > 0) {
     bool all_count = true, all_minmax = true;
     for (int i = 0; i < q->num_aggs; ++i) {
+      // (a PERCENTILE is in neither: its unfiltered aggregation-only query scans -- fn carries upper bits besides)
       all_count &= q->aggs[i].fn == PGPU_AGG_COUNT;
       all_minmax &= q->aggs[i].fn == PGPU_AGG_MIN || q->aggs[i].fn == PGPU_AGG_MAX ||
                     q->aggs[i].fn == PGPU_AGG_DISTINCTCOUNT;
@@ -680,9 +793,11 @@ int prepare_translation(PlanCtx& cx) {
     for (size_t i = 0; i < P->query_cols.size(); ++i)
       if (P->query_cols[i] == P->key_cols[j]) cx.qcol_key[i] = (int)j;
   for (size_t k = 1; k < P->slot_col.size(); ++k)
-    if (P->slot_dc[k] < 0) cx.qcol_val[P->slot_col[k]] = 1;
+    if (!P->side_slot(k)) cx.qcol_val[P->slot_col[k]] = 1;
   cx.qcol_dc.assign(P->query_cols.size(), -1);
   for (size_t d = 0; d < P->dc.size(); ++d) cx.qcol_dc[P->dc[d].qcol] = (int)d;
+  cx.qcol_hist.assign(P->query_cols.size(), -1);
+  for (size_t h = 0; h < P->hist.size(); ++h) cx.qcol_hist[P->hist[h].qcol] = (int)h;
   return 0;
 }
 
@@ -832,6 +947,10 @@ bool fill_kcols(const PlanCtx& cx, size_t i, KCol* kc) {
         const KeyLut& kl = P->dc_lut[i * P->dc.size() + cx.qcol_dc[j]];
         kc[j].lut = kl.lut;
         kc[j].lut_off = kl.off;
+      } else if (cx.qcol_hist[j] >= 0) {  // histogram column: the same again
+        const KeyLut& kl = P->hist_lut[i * P->hist.size() + cx.qcol_hist[j]];
+        kc[j].lut = kl.lut;
+        kc[j].lut_off = kl.off;
       }
       if (cx.qcol_val[j]) {  // accumulator operand: value arrays, built once (ensure_values) and never replaced
         kc[j].dkey = c->key_affine ? nullptr : c->d_key;
@@ -850,7 +969,7 @@ bool fill_kcols(const PlanCtx& cx, size_t i, KCol* kc) {
         }
       }
     }
-    gathers |= ((cx.qcol_key[j] >= 0 || cx.qcol_dc[j] >= 0) && kc[j].lut != nullptr) ||
+    gathers |= ((cx.qcol_key[j] >= 0 || cx.qcol_dc[j] >= 0 || cx.qcol_hist[j] >= 0) && kc[j].lut != nullptr) ||
                (cx.qcol_val[j] && kc[j].dkey != nullptr);
   }
   return gathers;
@@ -1063,7 +1182,8 @@ void configure_scan_grid(PlanCtx& cx, int64_t tile_base) {
   const bool fast = !P->dense && !pair && P->pure_and && P->num_leaves <= kFastLeaves;
   P->fast_wide = fast && P->sel_estimate >= 1.0 / 16;
   // plans with DISTINCTCOUNT and plans with SLOT_SUM_FX slots launch their own instances whatever the filter
-  P->variant = !P->dc.empty() ? (P->dense ? kScanDcDense : kScanDcSparse)
+  P->variant = !P->pct.empty() ? (P->dense ? kScanHistDense : kScanHistSparse)
+               : !P->dc.empty() ? (P->dense ? kScanDcDense : kScanDcSparse)
                : P->fx        ? (P->dense ? kScanFxDense : kScanFxSparse)
                : dense_simple ? kScanDenseSimple
                : P->dense     ? kScanDense

@@ -54,6 +54,8 @@ __device__ __forceinline__ uint32_t leap2_entries(uint8_t* __restrict__ maps, in
 // own (filter_groupby_fx_kernel, family SCAN_FX, with KParamsFx), so the others keep their registers and arguments.
 // DC: the instances of plans with DISTINCTCOUNT aggregations (SLOT_DISTINCT slots and their side bitmaps) -- kernels of
 // their own again (filter_groupby_dc_kernel, family SCAN_DC, with KParamsDc).
+// HIST: the instances of plans with PERCENTILE aggregations (SLOT_PERCENTILE slots and their side histograms) --
+// filter_groupby_hist_kernel, family SCAN_HIST, with KParamsHist.
 // The kernels share their body as text (scan_direct_body.inc): a body function inlined into them changed the
 // scalar register allocation of the existing instances.
 #ifndef PGPU_MIN_WAVES
@@ -67,23 +69,33 @@ __device__ __forceinline__ uint32_t leap2_entries(uint8_t* __restrict__ maps, in
 #endif
 template <int MODE, bool DENSE, bool SIMPLE = false, bool PAIR = false, bool FAST = false, int LANE_BATCH = 2>
 __global__ __launch_bounds__(kBlock, DENSE ? (SIMPLE ? PGPU_SIMPLE_MIN_WAVES : PGPU_DENSE_MIN_WAVES) : PGPU_MIN_WAVES) void filter_groupby_kernel(const KParams p) {
-  constexpr bool FX = false, DC = false;
+  constexpr bool FX = false;
+  constexpr int DC = kSideNone;
 #include "scan_direct_body.inc"
 }
 
 // The sparse (general filter programs and pure-AND ones alike) and the dense instance for plans with SLOT_SUM_FX slots.
 template <int MODE, bool DENSE>
 __global__ __launch_bounds__(kBlock, DENSE ? PGPU_DENSE_MIN_WAVES : PGPU_MIN_WAVES) void filter_groupby_fx_kernel(const KParamsFx p) {
-  constexpr bool FX = true, DC = false, SIMPLE = false, PAIR = false, FAST = false;
-  constexpr int LANE_BATCH = 2;
+  constexpr bool FX = true, SIMPLE = false, PAIR = false, FAST = false;
+  constexpr int LANE_BATCH = 2, DC = kSideNone;
 #include "scan_direct_body.inc"
 }
 
 // The sparse and the dense instance for plans with SLOT_DISTINCT slots (DISTINCTCOUNT): MODE_LDS and MODE_GLOBAL.
 template <int MODE, bool DENSE>
 __global__ __launch_bounds__(kBlock, DENSE ? PGPU_DENSE_MIN_WAVES : PGPU_MIN_WAVES) void filter_groupby_dc_kernel(const KParamsDc p) {
-  constexpr bool FX = false, DC = true, SIMPLE = false, PAIR = false, FAST = false;
-  constexpr int LANE_BATCH = 2;
+  constexpr bool FX = false, SIMPLE = false, PAIR = false, FAST = false;
+  constexpr int LANE_BATCH = 2, DC = kSideBitmap;
+#include "scan_direct_body.inc"
+}
+
+// The sparse and the dense instance for plans with SLOT_PERCENTILE slots (PERCENTILE, and DISTINCTCOUNT beside it):
+// MODE_LDS and MODE_GLOBAL.
+template <int MODE, bool DENSE>
+__global__ __launch_bounds__(kBlock, DENSE ? PGPU_DENSE_MIN_WAVES : PGPU_MIN_WAVES) void filter_groupby_hist_kernel(const KParamsHist p) {
+  constexpr bool FX = false, SIMPLE = false, PAIR = false, FAST = false;
+  constexpr int LANE_BATCH = 2, DC = kSideHist;
 #include "scan_direct_body.inc"
 }
 

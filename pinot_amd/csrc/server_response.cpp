@@ -415,6 +415,10 @@ int pgpu_result_trim_pql(pgpu_result r, int32_t limit, int32_t final_results, in
 
 int pgpu_result_datatable(pgpu_result r, pgpu_table t, void* out, int64_t cap, int64_t* len) try {
   if (!r || !t || !len) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  for (int32_t fn : r->agg_fn)  // the intermediate result is the value list (an OBJECT column); a result holds one value
+    if (fn == PGPU_AGG_PERCENTILE)
+      return host_fail(PGPU_ERR_UNSUPPORTED, "DataTable of a result with PERCENTILE: Pinot ships the value list "
+                       "as an OBJECT, the result holds the selected value");
   for (int32_t fn : r->agg_fn)  // the intermediate result is the value set (an OBJECT column), which a result no longer has
     if (fn == PGPU_AGG_DISTINCTCOUNT)
       return host_fail(PGPU_ERR_UNSUPPORTED, "DataTable of a result with DISTINCTCOUNT: Pinot ships the value set "

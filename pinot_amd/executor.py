@@ -185,9 +185,13 @@ def aggregation_defaults(aggregations):
     """Results of aggregation functions over no documents: their result holders' initial values
     (SumAggregationFunction.java:33 0.0, MinAggregationFunction.java:33 +inf, MaxAggregationFunction.java:33 -inf,
     CountAggregationFunction.java:38 0, AvgAggregationFunction: AvgPair(0.0, 0),
-    DistinctCountAggregationFunction.extractFinalResult of an empty set: 0)."""
+    DistinctCountAggregationFunction.extractFinalResult of an empty set: 0,
+    PercentileAggregationFunction.DEFAULT_FINAL_RESULT: -inf)."""
     out = []
     for fn, _ in aggregations:
+        if fn.startswith("PERCENTILE"):
+            out.append(float("-inf"))
+            continue
         out.append({"COUNT": 0, "SUM": 0.0, "MIN": float("inf"), "MAX": float("-inf"), "DISTINCTCOUNT": 0}.get(fn, None)
                    if fn != "AVG" else AvgPair(0.0, 0))
     return out
@@ -642,7 +646,7 @@ class Plan:
         `tile_chunks`, `slot_weights` (a tuple, empty = equal shares), `longest_run`, `launch_grid`, `launch_tiles`,
         `alone` and `weights_declined` (refused for the LDS the plan reserved); `variant`, the scan kernel's instance
         (0 sparse, 1 dense, 2 dense without gathers, 3-5 sparse specialisations, 6 / 7 sparse / dense with fixed-point
-        sums, 8 / 9 sparse / dense with DISTINCTCOUNT)."""
+        sums, 8 / 9 sparse / dense with DISTINCTCOUNT, 10 / 11 sparse / dense with PERCENTILE)."""
         out = (ctypes.c_int64 * 16)()
         L.check(self.lib.pgpu_plan_scan_geometry(self.handle, out))
         return {"grid": out[0], "lds_bytes": out[1], "leap_tiles": out[2], "tiles": out[3],

@@ -14,6 +14,8 @@ import ctypes
 import re
 import time
 
+import decimal
+
 from . import _lib as L
 
 EQ, NOT_EQ, IN, NOT_IN, RANGE = "EQ", "NOT_EQ", "IN", "NOT_IN", "RANGE"
@@ -27,10 +29,57 @@ DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE = 5000  # InstancePlanMakerImplV2.DEFAULT_MIN
 DEFAULT_GROUP_TRIM_THRESHOLD = 1000000  # InstancePlanMakerImplV2.DEFAULT_GROUPBY_TRIM_THRESHOLD
 
 
-def function_name(fn):
+PERCENTILE_MAX_E4 = 1000000  # PGPU_AGG_PERCENTILE_MAX_E4: the percentile in ten-thousandths, at most 100
+_PERCENTILE_OTHERS = ("EST", "TDIGEST", "RAWEST", "RAWTDIGEST", "MV", "ESTMV", "TDIGESTMV", "RAWESTMV", "RAWTDIGESTMV")
+
+
+def percentile_code(percentile):
+    """A percentile (number or decimal string, 0 .. 100, a multiple of 0.0001) in ten-thousandths; ValueError
+    otherwise.  p_e4 / 10000.0 is the double of the decimal literal, which is what Pinot's arithmetic uses."""
+    try:
+        d = decimal.Decimal(percentile if isinstance(percentile, (str, int)) else repr(percentile))
+    except (decimal.InvalidOperation, TypeError, ValueError):
+        raise ValueError("PERCENTILE: %r is not a percentile" % (percentile,))
+    if not d.is_finite() or d < 0 or d > 100:
+        raise ValueError("PERCENTILE: percentile %s outside [0, 100]" % (percentile,))
+    e4 = d * 10000
+    if e4 != e4.to_integral_value():
+        raise ValueError("PERCENTILE: percentile %s is not a multiple of 0.0001" % (percentile,))
+    return int(e4)
+
+
+def percentile_name(p_e4):
+    """The canonical name of the exact percentile: PERCENTILE95, PERCENTILE99.9 (a whole one without a fraction)."""
+    whole, frac = divmod(p_e4, 10000)
+    return "PERCENTILE%d" % whole + (".%04d" % frac).rstrip("0") * (frac != 0)
+
+
+def percentile_e4(name):
+    """The percentile of a canonical function name in ten-thousandths, None for every other function."""
+    if not name.startswith("PERCENTILE"):
+        return None
+    return percentile_code(name[len("PERCENTILE"):])
+
+
+def function_name(fn, percentile=None):
     """An aggregation function's canonical name: upper case, underscores dropped (DISTINCT_COUNT = DISTINCTCOUNT), as
-    AggregationFunctionType.getAggregationFunctionType normalises it."""
-    return fn.upper().replace("_", "")
+    AggregationFunctionType.getAggregationFunctionType normalises it.  The exact percentile carries its percentile in
+    the name: PERCENTILE95(x), PERCENTILE(x, 95) and PERCENTILE(x, '95.0') are all PERCENTILE95.  The estimating and
+    multi-value percentile functions are not supported (ValueError)."""
+    name = fn.upper().replace("_", "")
+    if not name.startswith("PERCENTILE"):
+        if percentile is not None:
+            raise ValueError("%s takes one argument" % name)
+        return name
+    suffix = name[len("PERCENTILE"):]
+    for other in _PERCENTILE_OTHERS:
+        if suffix.startswith(other):
+            raise ValueError("unsupported aggregation function PERCENTILE%s: only the exact single-value PERCENTILE "
+                             "runs on the GPU path" % other)
+    if (suffix == "") == (percentile is None):
+        raise ValueError("PERCENTILE takes its percentile in the name (PERCENTILE95(x)) or as the second argument "
+                         "(PERCENTILE(x, 95)), got %s" % fn)
+    return percentile_name(percentile_code(suffix if percentile is None else percentile))
 
 
 class Predicate:
@@ -116,7 +165,8 @@ class QueryContext:
         self.sql_group_by = sql_group_by
         self.use_star_tree = use_star_tree  # debug option useStarTree (StarTreeUtils.java:51-59)
         self.group_by = list(group_by)
-        self.aggregations = [(function_name(fn), col) for fn, col in aggregations]
+        # (fn, column) or, for the exact percentile, ("PERCENTILE", column, percentile); kept as (canonical name, column)
+        self.aggregations = [(function_name(a[0], *a[2:]), a[1]) for a in aggregations]
         self.num_groups_limit = num_groups_limit
         # SQL-mode parts (QueryContext.getSelectExpressions / getOrderByExpressions / getLimit): the SELECT list as
         # ('col', name) / ('agg', FN, col), ORDER BY as [(expr, ascending)], LIMIT; the combine's trim options
@@ -234,9 +284,13 @@ class QueryContext:
         gb = (ctypes.c_int32 * max(len(self.group_by), 1))(*[column_index[c] for c in self.group_by])
         ac = (L.AggC * max(len(self.aggregations), 1))()
         for i, (fn, col) in enumerate(self.aggregations):
-            if fn not in AGG_FUNCTIONS:
+            p_e4 = percentile_e4(fn)
+            if p_e4 is not None:  # pgpu_agg.fn: the code in bits 0..7, the percentile above (PGPU_AGG_PERCENTILE_OF)
+                ac[i].fn = L.AGG_PERCENTILE | (p_e4 << 8)
+            elif fn not in AGG_FUNCTIONS:
                 raise L.UnsupportedQueryError(L.PGPU_ERR_UNSUPPORTED, "aggregation %s" % fn)
-            ac[i].fn = AGG_FUNCTIONS[fn]
+            else:
+                ac[i].fn = AGG_FUNCTIONS[fn]
             ac[i].column = -1 if col == "*" else column_index[col]
         q = L.QueryC()
         q.num_predicates = len(preds)
@@ -302,15 +356,19 @@ class _Parser:
     def select_list_item(self):
         tok = self.peek()
         if tok[0] == "id" and self.peek(1) == ("op", "("):
-            fn = function_name(self.take("id"))
+            fn = self.take("id")
             self.take("op", "(")
             col = "*" if self.peek() == ("op", "*") else None
             if col:
                 self.take("op", "*")
             else:
                 col = self.take("id")
+            arg = None
+            if self.peek() == ("op", ","):  # PERCENTILE(x, 95) / PERCENTILE(x, '95')
+                self.take("op", ",")
+                arg = self.take("lit")
             self.take("op", ")")
-            return ("agg", fn, col)
+            return ("agg", function_name(fn, arg), col)
         return ("col", self.take("id"))
 
     def select_list(self):
