@@ -265,8 +265,64 @@ enum pgpu_agg_fn { PGPU_AGG_COUNT = 0, PGPU_AGG_SUM = 1, PGPU_AGG_MIN = 2, PGPU_
 #define PGPU_AGG_PERCENTILE_E4(fn) ((int32_t)(((uint32_t)(fn)) >> 8))      /* its percentile in ten-thousandths */
 typedef struct {
   int32_t fn;
-  int32_t column;   /* -1 for COUNT(*) */
+  int32_t column;   /* -1 for COUNT(*); a virtual column (pgpu_table_add_expression) for an expression */
 } pgpu_agg;
+
+/* Arithmetic expressions inside aggregations -- SUM(price * qty), AVG(revenue - cost), MAX(a / b): the reference's
+ * TransformOperator between projection and aggregation, for its four arithmetic transform functions
+ * (core/operator/transform/function/{Addition,Subtraction,Multiplication,Division}TransformFunction.java).  An
+ * expression is a virtual column of the table: pgpu_table_add_expression registers its postfix program and returns a
+ * column index at or above the table's real columns, which a pgpu_agg.column may name from then on.  Registering an
+ * identical program again returns the same index, so a query's bytes -- the plan-cache key -- stay the same.
+ * Semantics, bit for bit per doc: every function yields a double.  A column operand is its getDoubleValuesSV value
+ * ((double) of an INT, LONG or FLOAT value), a literal a double.  Every operation is one IEEE double operation rounded
+ * on its own; nothing is fused into a multiply-add.  All ops are binary: the caller emits the reference's n-ary
+ * ADD(x1..xn) as ((0.0 + literals in argument order) + v1) + v2 ... over the non-literal arguments in argument order
+ * (the leading 0.0 + is part of the semantics: ADD(x, y) of two -0.0 is +0.0), MULT likewise from 1.0.  SUB(a, b) is
+ * a - b, DIV(a, b) is a / b (x / 0 is +-inf).  A NaN result is treated as the NaN of a DOUBLE column is (one canonical
+ * NaN key, above +inf, for MIN / MAX).
+ * Aggregations: SUM and AVG of an expression add the doubles (float64 sums; AVG divides by the COUNT), MIN and MAX
+ * compare them in double order (-0.0 below +0.0), COUNT(expr) is COUNT(*) -- pass column -1.  The virtual column is a
+ * DOUBLE to everything downstream of the scan: finalize, ORDER BY and the trims, the cross-GPU combine (ranks must
+ * have registered the same programs in the same order), the DataTable, which names the aggregation by the expression's
+ * name, e.g. sum(mult(price,qty)).  numEntriesScannedPostFilter counts every distinct real column the query projects
+ * once: the group-by columns and every column named by an aggregation or inside its expression.  A segment carrying a
+ * star-tree is scanned for such a query.  The values are computed per matched doc inside the fused scan, by a
+ * pair of instances of its own (pgpu_plan_scan_geometry word 15 = 12: sparse, in every accumulator mode -- LDS, global
+ * and hash tables; 13: dense, the whole-group decode of plans of estimated selectivity >= dense_selectivity).
+ * Limits (PGPU_ERR_INVALID_ARGUMENT otherwise): 1..PGPU_EXPR_MAX_OPS ops; an evaluation stack of at most
+ * PGPU_EXPR_MAX_DEPTH values; at most PGPU_EXPR_MAX_COLUMNS distinct columns; a well-formed postfix program (no
+ * underflow, an op code of the enum, column indexes of the table) that leaves exactly one value; at least one column
+ * operand; at most PGPU_EXPR_MAX_PER_TABLE expressions per table.
+ * Declined with PGPU_ERR_UNSUPPORTED (the message names "expression"): an operand that is a STRING column or itself a
+ * virtual column (at registration); an operand that is a raw (no-dictionary) column in a planned segment (multi-value
+ * columns cannot be pinned at all); DISTINCTCOUNT or PERCENTILE of an expression; an expression aggregation in one
+ * query with a DISTINCTCOUNT or PERCENTILE (those plans take another scan instance); the combination with
+ * PGPU_OPT_EXACT_FP_SUM (pgpu_query_fp_sum_ranges and pgpu_plan_create_agreed included); more than 8 distinct
+ * expressions in one query; an external d_table (execute, finalize, pgpu_plan_combine); numGroupsLimit plans that
+ * split per segment; a virtual column in GROUP BY or in a predicate (PGPU_ERR_INVALID_ARGUMENT: bad column).  Such
+ * plans never take the radix- or hash-partitioned pipelines: they are planned as with
+ * pgpu_config.partitioned_group_by = 0, hash_partitions = 0 and stream_chunks = 1. */
+enum pgpu_expr_opcode { PGPU_EXPR_COLUMN = 0, PGPU_EXPR_LITERAL = 1, PGPU_EXPR_ADD = 2, PGPU_EXPR_SUB = 3,
+                        PGPU_EXPR_MULT = 4, PGPU_EXPR_DIV = 5 };
+#define PGPU_EXPR_MAX_OPS 16
+#define PGPU_EXPR_MAX_DEPTH 4
+#define PGPU_EXPR_MAX_COLUMNS 4
+#define PGPU_EXPR_MAX_PER_TABLE 256
+typedef struct {
+  int32_t op;       /* pgpu_expr_opcode; ADD / SUB / MULT / DIV pop b then a and push a op b */
+  int32_t column;   /* PGPU_EXPR_COLUMN: a real column of the table */
+  double literal;   /* PGPU_EXPR_LITERAL */
+} pgpu_expr_op;
+/* Registers ops[0, n) as a virtual column named `name` -- the expression in the reference's function form, e.g.
+ * "mult(price,qty)" or "add(div(a,b),2.5)"; NULL = built from the program -- and returns its index in *column.  An
+ * identical program (same ops, literals compared by their bits) registered before returns that index and keeps its
+ * name. */
+int pgpu_table_add_expression(pgpu_table table, const pgpu_expr_op* ops, int32_t n, const char* name, int32_t* column);
+/* A virtual column's program and name: *n = its ops (ops receives min(cap, *n) of them; ops may be NULL when cap is 0),
+ * name receives at most name_cap bytes, NUL-terminated.  PGPU_ERR_NOT_FOUND for a column that is no virtual one. */
+int pgpu_table_expression(pgpu_table table, int32_t column, pgpu_expr_op* ops, int32_t cap, int32_t* n, char* name,
+                          int32_t name_cap);
 
 typedef struct {
   int32_t num_predicates;
@@ -550,7 +606,8 @@ int pgpu_plan_star_work(pgpu_plan plan, int64_t* out3);
  * run could pass [2]; [15] the scan kernel's instance: 0 sparse, 1 dense, 2 dense without gathers, 3 - 5 the sparse
  * specialisations (index + scan pair, pure AND, pure AND with 4-doc batches), 6 / 7 the sparse / dense instance of
  * plans with fixed-point sums (PGPU_OPT_EXACT_FP_SUM), 8 / 9: sparse / dense of plans with PGPU_AGG_DISTINCTCOUNT,
- * 10 / 11: sparse / dense of plans with PGPU_AGG_PERCENTILE (side histograms). */
+ * 10 / 11: sparse / dense of plans with PGPU_AGG_PERCENTILE (side histograms), 12 / 13: sparse / dense of plans with
+ * expression aggregations (pgpu_table_add_expression). */
 int pgpu_plan_scan_geometry(pgpu_plan plan, int64_t* out16);
 /* Bytes of the star-tree metric arrays the last execution's document scan read (after finalize): the 64-byte
  * sectors holding at least one matched document, summed over the arrays read; -1 where finalize did not read the

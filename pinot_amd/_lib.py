@@ -93,6 +93,15 @@ class AggC(ctypes.Structure):
     _fields_ = [("fn", c_i32), ("column", c_i32)]
 
 
+# pgpu_expr_opcode / pgpu_expr_op: the postfix program of an expression inside an aggregation (a virtual column)
+EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MULT, EXPR_DIV = 0, 1, 2, 3, 4, 5
+EXPR_MAX_OPS, EXPR_MAX_DEPTH, EXPR_MAX_COLUMNS, EXPR_MAX_PER_TABLE = 16, 4, 4, 256
+
+
+class ExprOpC(ctypes.Structure):
+    _fields_ = [("op", c_i32), ("column", c_i32), ("literal", ctypes.c_double)]
+
+
 class QueryC(ctypes.Structure):
     _fields_ = [("num_predicates", c_i32), ("num_filter_ops", c_i32), ("predicates", ctypes.POINTER(PredicateC)),
                 ("filter", ctypes.POINTER(FilterOpC)), ("num_group_by", c_i32), ("num_aggs", c_i32),
@@ -197,6 +206,8 @@ _PROTOS = {
     "pgpu_table_set_config": (c_int, [c_voidp, ctypes.POINTER(ConfigC)]),
     "pgpu_table_get_config": (c_int, [c_voidp, ctypes.POINTER(ConfigC)]),
     "pgpu_table_destroy": (c_int, [c_voidp]),
+    "pgpu_table_add_expression": (c_int, [c_voidp, ctypes.POINTER(ExprOpC), c_i32, ctypes.c_char_p, c_i32p]),
+    "pgpu_table_expression": (c_int, [c_voidp, c_i32, ctypes.POINTER(ExprOpC), c_i32, c_i32p, ctypes.c_char_p, c_i32]),
     "pgpu_pin_segment": (c_int, [c_voidp, ctypes.POINTER(SegmentDesc), c_i64p]),
     "pgpu_unpin_segment": (c_int, [c_voidp, c_i64]),
     "pgpu_table_num_segments": (c_int, [c_voidp, c_i32p]),

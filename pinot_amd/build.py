@@ -19,13 +19,13 @@ SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTI
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
            ("k_partition.hip", [], "k_partition"), ("k_partition_fx.hip", [], "k_partition_fx"),
            ("k_hashfinal.hip", [], "k_hashfinal")] + \
-    [("k_%s.hip" % k, ["-DPGPU_FAMILY=%d" % f, "-DPGPU_MODE=%d" % m], "k_%s%s_%d" % (k, ("", "_fx", "_dc", "_hist")[f], m))
+    [("k_%s.hip" % k, ["-DPGPU_FAMILY=%d" % f, "-DPGPU_MODE=%d" % m], "k_%s%s_%d" % (k, ("", "_fx", "_dc", "_hist", "_expr")[f], m))
      for k, f, modes in (("direct", 0, 3), ("startree", 0, 3), ("direct", 1, 3), ("startree", 1, 3), ("direct", 2, 2),
-                         ("direct", 3, 2))
+                         ("direct", 3, 2), ("direct", 4, 3))
      for m in range(modes)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "scan_direct_body.inc", "part_aggregate_body.inc",
            "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
@@ -158,7 +158,7 @@ def build_host_fuzz(force=False):
     return FUZZ_PATH
 
 
-def _build_header_check(name, src, hdr, force=False):
+def _build_header_check(name, src, hdr, force=False, extra=()):
     """build/<name>: tools/<src>, which includes csrc/<hdr> and nothing else of the library, under AddressSanitizer +
     UndefinedBehaviorSanitizer.  One compile, no library linked; rebuilt when the source or the header is newer."""
     out = os.path.join(ROOT, "build", name)
@@ -171,7 +171,7 @@ def _build_header_check(name, src, hdr, force=False):
     obj = out + ".o"
     # (the sanitizers are host-only flags: compiled as the library's sources are, then linked with their runtimes)
     for cmd in ([hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS +
-                ["-c", src, "-o", obj],
+                list(extra) + ["-c", src, "-o", obj],
                 [hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined", obj,
                  "-o", out + ".tmp"]):
         res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -204,6 +204,12 @@ def build_fx_agree_check(force=False):
 def build_key_range_check(force=False):
     """The key range a rank owns in the dense cross-GPU combine (key_range.h)."""
     return _build_header_check("key_range_check", "key_range_check.cpp", "key_range.h", force)
+
+
+def build_expr_check(force=False):
+    """The expression programs of aggregations (expr_eval.h): validation, evaluation and keys on the host, compiled
+    with floating-point contraction off -- no fused multiply-add, as on the device."""
+    return _build_header_check("expr_check", "expr_check.cpp", "expr_eval.h", force, extra=("-ffp-contract=off",))
 
 
 if __name__ == "__main__":

@@ -717,6 +717,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   if (plan_has_percentile(P)) return percentile_decline("a cross-GPU combine");  // (... and the function)
   // DISTINCTCOUNT: the side bitmaps belong to the plan's own table (a caller table is declined at execute already)
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");  // (every rank passes one or none)
+  if (d_table && plan_has_expr(P)) return expr_decline("external table");
   P->k8d_counts = false;
   if (mode == PGPU_COMBINE_LOCAL) {
     if (key_begin) *key_begin = 0;

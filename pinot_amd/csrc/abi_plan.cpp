@@ -531,6 +531,7 @@ int pgpu_plan_execute(pgpu_plan P, void* stream, void* d_table) try {
   if (P->hash && d_table) return fail(PGPU_ERR_UNSUPPORTED, "external table with a hash-mode plan");
   if (d_table && plan_fx_local(P)) return fx_decline("external table");
   if (d_table && plan_has_percentile(P)) return percentile_decline("external table");
+  if (d_table && plan_has_expr(P)) return expr_decline("external table");
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;
@@ -542,6 +543,7 @@ int pgpu_plan_finalize(pgpu_plan P, void* stream, const void* d_table, pgpu_resu
   if (!P || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (d_table && plan_fx_local(P)) return fx_decline("external table");
   if (d_table && plan_has_percentile(P)) return percentile_decline("external table");
+  if (d_table && plan_has_expr(P)) return expr_decline("external table");
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");
   DeviceGuard g(P->table->device);
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : P->table->stream;

@@ -129,6 +129,94 @@ int pgpu_table_get_config(pgpu_table t, pgpu_config* out) try {
   return 0;
 } PGPU_ABI_CATCH
 
+// ---- virtual columns: arithmetic expressions inside aggregations (expr_eval.h)
+static_assert(sizeof(pgpu_expr_op) == sizeof(pgpu::ExprOpIn) && offsetof(pgpu_expr_op, literal) == offsetof(pgpu::ExprOpIn, literal) &&
+              offsetof(pgpu_expr_op, column) == offsetof(pgpu::ExprOpIn, column), "pgpu_expr_op is ExprOpIn");
+static_assert(PGPU_EXPR_COLUMN == pgpu::EXPR_COLUMN && PGPU_EXPR_LITERAL == pgpu::EXPR_LITERAL &&
+              PGPU_EXPR_ADD == pgpu::EXPR_ADD && PGPU_EXPR_SUB == pgpu::EXPR_SUB && PGPU_EXPR_MULT == pgpu::EXPR_MULT &&
+              PGPU_EXPR_DIV == pgpu::EXPR_DIV && PGPU_EXPR_MAX_OPS == pgpu::kExprMaxOps &&
+              PGPU_EXPR_MAX_DEPTH == pgpu::kExprMaxDepth && PGPU_EXPR_MAX_COLUMNS == pgpu::kExprMaxCols &&
+              PGPU_EXPR_MAX_PER_TABLE == pgpu::kMaxTableExprs, "the header's limits are expr_eval.h's");
+
+// The function form of a program: add(div(a,b),2.5).
+static std::string expr_default_name(const pgpu_table_s* t, const pgpu::ExprProg& g) {
+  std::vector<std::string> st;
+  for (int k = 0; k < g.nops; ++k) {
+    const int op = g.code[k] & 0xFF, arg = g.code[k] >> 8;
+    if (op == pgpu::EXPR_COLUMN) {
+      st.push_back(t->names[g.col[arg]]);
+    } else if (op == pgpu::EXPR_LITERAL) {
+      char buf[40];
+      snprintf(buf, sizeof buf, "%.17g", g.lit[arg]);
+      st.push_back(buf);
+    } else {
+      const std::string b = st.back();
+      st.pop_back();
+      const char* fn = op == pgpu::EXPR_ADD ? "add" : op == pgpu::EXPR_SUB ? "sub" : op == pgpu::EXPR_MULT ? "mult" : "div";
+      st.back() = std::string(fn) + "(" + st.back() + "," + b + ")";
+    }
+  }
+  return st.back();
+}
+
+int pgpu_table_add_expression(pgpu_table t, const pgpu_expr_op* ops, int32_t n, const char* name, int32_t* column) try {
+  PGPU_ABI_GUARD;
+  if (!t || !column) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  const int ncols = (int)t->names.size();
+  pgpu_table_s::Expr e;
+  const pgpu::ExprOpIn* in = reinterpret_cast<const pgpu::ExprOpIn*>(ops);
+  if (const int rc = pgpu::expr_compile(in, n, &e.prog))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "expression: %s", pgpu::expr_error_text(rc));
+  // (a virtual operand before a bad index: at or above the real columns it is either, and the caller meant the former)
+  std::lock_guard<std::mutex> g(t->mu);
+  for (int c = 0; c < e.prog.ncols; ++c) {
+    const int col = e.prog.col[c];
+    if (col >= ncols && col < ncols + (int)t->exprs.size())
+      return fail(PGPU_ERR_UNSUPPORTED, "expression over virtual column %d: an operand is a real column", col);
+    if (col >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "expression: bad column %d", col);
+    if (t->types[col] == PGPU_STRING)
+      return fail(PGPU_ERR_UNSUPPORTED, "expression over STRING column %d (%s)", col, t->names[col].c_str());
+  }
+  e.ops.assign(in, in + n);
+  for (pgpu::ExprOpIn& o : e.ops) {  // only the fields the op reads count
+    if (o.op != pgpu::EXPR_COLUMN) o.column = 0;
+    if (o.op != pgpu::EXPR_LITERAL) o.literal = 0.0;
+  }
+  auto same = [](const pgpu::ExprOpIn& a, const pgpu::ExprOpIn& b) {
+    return a.op == b.op && a.column == b.column && pgpu::bits_of_double(a.literal) == pgpu::bits_of_double(b.literal);
+  };
+  for (size_t i = 0; i < t->exprs.size(); ++i)
+    if (t->exprs[i].ops.size() == e.ops.size() && std::equal(e.ops.begin(), e.ops.end(), t->exprs[i].ops.begin(), same)) {
+      *column = ncols + (int32_t)i;
+      return 0;
+    }
+  if ((int)t->exprs.size() >= pgpu::kMaxTableExprs)
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "expression: the table already has %d expressions", pgpu::kMaxTableExprs);
+  e.name = name && *name ? std::string(name) : expr_default_name(t, e.prog);
+  t->exprs.push_back(std::move(e));
+  *column = ncols + (int32_t)t->exprs.size() - 1;
+  return 0;
+} PGPU_ABI_CATCH
+
+int pgpu_table_expression(pgpu_table t, int32_t column, pgpu_expr_op* ops, int32_t cap, int32_t* n, char* name,
+                          int32_t name_cap) try {
+  PGPU_ABI_GUARD;
+  if (!t || !n || cap < 0 || (cap > 0 && !ops) || name_cap < 0 || (name_cap > 0 && !name))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  std::lock_guard<std::mutex> g(t->mu);
+  const int e = column - (int)t->names.size();
+  if (e < 0 || e >= (int)t->exprs.size()) return fail(PGPU_ERR_NOT_FOUND, "column %d is no expression", column);
+  const pgpu_table_s::Expr& x = t->exprs[e];
+  *n = (int32_t)x.ops.size();
+  for (int k = 0; k < cap && k < *n; ++k) {
+    ops[k].op = x.ops[k].op;
+    ops[k].column = x.ops[k].column;
+    ops[k].literal = x.ops[k].literal;
+  }
+  if (name_cap > 0) snprintf(name, (size_t)name_cap, "%s", x.name.c_str());
+  return 0;
+} PGPU_ABI_CATCH
+
 int pgpu_table_destroy(pgpu_table t) try {
   PGPU_ABI_GUARD;
   if (!t) return 0;

@@ -494,9 +494,50 @@ __device__ __forceinline__ void hist_add(uint32_t* __restrict__ row, uint32_t gi
 // DC (the template argument of the aggregate functions below): kSideNone, kSideBitmap (the DC instances: SLOT_DISTINCT
 // rows and side bitmaps) or kSideHist (the histogram instances: SLOT_PERCENTILE rows and side histograms).
 constexpr int kSideNone = 0, kSideBitmap = 1, kSideHist = 2;
+// ... or kSideExpr (the expression instance): no side structure and no row skipped -- the slots of a program
+// (KExpr.slot_prog) take the program's value instead of a column's.
+constexpr int kSideExpr = 3;
 // The slot kind the instance's slot loop skips: its side structure's rows.
 template <int DC>
 __device__ __forceinline__ constexpr int side_slot_kind() { return DC == kSideHist ? SLOT_PERCENTILE : SLOT_DISTINCT; }
+
+// The programs of the expression aggregations: p is the KParamsExpr of the expression instance (the only callers).
+__device__ __forceinline__ const KExpr& expr_programs(const KParams& p) { return static_cast<const KParamsExpr&>(p).ex; }
+
+// Program P's value for NB docs per lane (doc b of segment S[b]): each distinct operand column is gathered once --
+// dictId -> vidx -> dval, the gathers of a level issued for every column and doc before any is consumed -- then the
+// wave-uniform program is interpreted over the register stack (expr_eval).  Docs with ok[b] == false read doc 0.
+template <int NB>
+__device__ __forceinline__ void expr_batch(const ExprProg& P, const SegView (&S)[NB], const int64_t (&doc)[NB],
+                                           const bool (&ok)[NB], double (&out)[NB]) {
+  const int nc = P.ncols;
+  uint32_t id[kExprMaxCols][NB];
+  double v[kExprMaxCols][NB];
+#pragma unroll
+  for (int c = 0; c < kExprMaxCols; ++c) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      id[c][b] = 0;
+      v[c][b] = 0.0;
+    }
+    if (c < nc) {  // wave-uniform
+      const int col = P.col[c];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        KColC& kc = S[b].cols[col];
+        id[c][b] = gather_id(kc.fwd, kc.bits, ok[b] ? doc[b] : 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kExprMaxCols; ++c)
+    if (c < nc) {
+      const int col = P.col[c];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) v[c][b] = gp(S[b].cols[col].dval)[vidx(S[b].cols[col], id[c][b])];
+    }
+  expr_eval<NB>(P, v, out);
+}
 
 template <int MODE>
 __device__ __forceinline__ void accumulate(uint64_t* __restrict__ base, int64_t idx, int kind, int64_t ikey,
@@ -658,15 +699,35 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
   }
   uint32_t id[NB], vi[NB];  // dictIds, and their indexes in the value arrays (vidx)
   int prev_col = -1;
+  // kSideExpr: the value of the program evaluated last (the adjacent slots of one program share the evaluation)
+  [[maybe_unused]] double ev[DC == kSideExpr ? NB : 1];
+  [[maybe_unused]] int prev_prog = -1;
   for (int s = 0; s < p.num_slots; ++s) {
     const int kind = p.slot_kind[s];
-    if constexpr (DC != kSideNone) {
+    if constexpr (DC == kSideBitmap || DC == kSideHist) {
       if (kind == side_slot_kind<DC>()) continue;  // the row is distinct_popcount_kernel's / percentile_select_kernel's
     }
     int64_t ikey[NB];
     double dval[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) { ikey[b] = 0; dval[b] = 0.0; }
+    if constexpr (DC == kSideExpr) {
+      const KExpr& E = expr_programs(p);
+      const int pi = kind != SLOT_COUNT ? E.slot_prog[s] : -1;  // wave-uniform
+      if (pi >= 0) {  // a slot of a program: its value, evaluated once for the program's slots
+        if (pi != prev_prog) {
+          expr_batch<NB>(E.prog[pi], S, doc, ok, ev);
+          prev_prog = pi;
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          if (kind == SLOT_SUM_F64) dval[b] = ev[b];
+          else ikey[b] = expr_value_key(ev[b]);
+        }
+        // (a jump, not a flag in the condition below: the other instances keep their text and with it their code)
+        goto operands_ready;
+      }
+    }
     if (kind != SLOT_COUNT) {
       const int col = p.slot_col[s];
       if (col != prev_col) {  // SUM/MIN/MAX of one column share the dictId gather
@@ -697,6 +758,7 @@ __device__ __forceinline__ void aggregate_batch(const KParams& p, const SegView 
         }
       }
     }
+  operands_ready:
     // an FX digit accumulates as an integer SUM from here on
     const int akind = FX && kind == SLOT_SUM_FX ? (int)SLOT_SUM_I64 : kind;
     if (G == 1) {  // single row: fold the lane's docs, then the wave
@@ -1091,6 +1153,201 @@ __device__ __forceinline__ void aggregate_half(const KParams& p, const SegView& 
   }
 }
 
+// ---- the whole-group path of the expression instance (kSideExpr): kExprStep docs of the lane's group per step, so
+// that the evaluation stack -- four rows, whatever the program's depth, which is a run-time value -- is 4 x kExprStep
+// doubles beside one gathered operand and the step's keys.  Measured with tools/vgpr_report.py at the dense instances'
+// 128 registers: 16 docs per step cannot fit by count (128 VGPRs of stack alone), 8 spill 57 - 61 VGPRs
+// (profiles/vgpr_report_expr_agg_dense8.txt).
+constexpr int kExprStep = 4;
+// dictIds of docs Q .. Q + kExprStep - 1 of a lane's group of B-bit ids at `words`.  Only the words those docs' bits
+// span are loaded -- bits [Q * B, (Q + kExprStep) * B), compile-time bounds -- so the steps of a group read each word
+// of a column once (twice where two steps share a word), not the whole group per step.
+template <int B, int Q, int... I>
+__device__ __forceinline__ void decode_step_b(const uint32_t* __restrict__ words, uint32_t (&ids)[kExprStep],
+                                              std::integer_sequence<int, I...>) {
+  constexpr int first = (Q * B) >> 5, last = ((Q + kExprStep) * B - 1) >> 5;  // last < B: the group is B words
+  gmem<uint32_t>* g = gp(words);
+  uint32_t w[B + 1];
+#pragma unroll
+  for (int k = 0; k <= B; ++k) w[k] = (k >= first && k <= last) ? bswap32(g[k]) : 0u;
+  ((ids[I] = extract<B, Q + I>(w)), ...);
+}
+// dictIds of docs [32*group + Q, 32*group + Q + kExprStep).
+template <int Q>
+__device__ __forceinline__ void decode_step(const uint32_t* __restrict__ fwd, int bits, int64_t group,
+                                              uint32_t (&ids)[kExprStep]) {
+  const uint32_t* words = fwd + group * (int64_t)bits;
+  switch (bits) {
+#define PGPU_CASE(B)                                                          \
+  case B: {                                                                   \
+    decode_step_b<B, Q>(words, ids, std::make_integer_sequence<int, kExprStep>{}); \
+    break;                                                                    \
+  }
+    PGPU_CASE(1) PGPU_CASE(2) PGPU_CASE(3) PGPU_CASE(4) PGPU_CASE(5) PGPU_CASE(6) PGPU_CASE(7) PGPU_CASE(8)
+    PGPU_CASE(9) PGPU_CASE(10) PGPU_CASE(11) PGPU_CASE(12) PGPU_CASE(13) PGPU_CASE(14) PGPU_CASE(15)
+    PGPU_CASE(16) PGPU_CASE(17) PGPU_CASE(18) PGPU_CASE(19) PGPU_CASE(20) PGPU_CASE(21) PGPU_CASE(22)
+    PGPU_CASE(23) PGPU_CASE(24) PGPU_CASE(25) PGPU_CASE(26) PGPU_CASE(27) PGPU_CASE(28) PGPU_CASE(29)
+    PGPU_CASE(30) PGPU_CASE(31)
+#undef PGPU_CASE
+    default:
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i) ids[i] = 0;
+      break;
+  }
+}
+
+// Program P over docs Q..Q+kExprStep-1 of the lane's group, operand by operand: a COLUMN op decodes the step's dictIds
+// of its column (the lane's own words of the forward index, those the step's docs span), issues their dictionary lookups
+// together and pushes them; at most the four stack rows and one operand are live.  Every doc is evaluated, matched or
+// not (docs past numDocs decode the zero padding to dictId 0: in bounds); the caller adds the matched ones.
+template <int Q>
+__device__ __forceinline__ void expr_eval_group(const ExprProg& P, const SegView& S, int64_t group, double (&out)[kExprStep]) {
+  double s0[kExprStep], s1[kExprStep], s2[kExprStep], s3[kExprStep];
+#pragma unroll
+  for (int i = 0; i < kExprStep; ++i) s0[i] = s1[i] = s2[i] = s3[i] = 0.0;
+  const int n = P.nops;
+  for (int k = 0; k < n; ++k) {
+    const int code = P.code[k], op = code & 0xFF, arg = code >> 8;
+    if (op == EXPR_COLUMN || op == EXPR_LITERAL) {
+      double x[kExprStep];
+      if (op == EXPR_COLUMN) {
+        KColC& c = S.cols[P.col[arg]];
+        uint32_t ids[kExprStep];
+        decode_step<Q>(c.fwd, c.bits, group, ids);
+        vidx_n(c, ids);
+        gmem<double>* __restrict__ dv = gp(c.dval);
+#pragma unroll
+        for (int i = 0; i < kExprStep; ++i) x[i] = dv[ids[i]];
+      } else {
+        const double lit = P.lit[arg];
+#pragma unroll
+        for (int i = 0; i < kExprStep; ++i) x[i] = lit;
+      }
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i) {
+        s3[i] = s2[i];
+        s2[i] = s1[i];
+        s1[i] = s0[i];
+        s0[i] = x[i];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i) {
+        s0[i] = expr_apply(op, s1[i], s0[i]);
+        s1[i] = s2[i];
+        s2[i] = s3[i];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kExprStep; ++i) out[i] = s0[i];
+}
+
+// Docs Q..Q+kExprStep-1 of the lane's group into every slot: the keys from whole-group decodes (as aggregate_half), a real
+// column's slots from its decoded dictIds, a program's slots from expr_eval_group (one evaluation for the slots of one
+// program).  Dense key spaces only (MODE_LDS / MODE_GLOBAL).
+template <int MODE, int Q>
+__device__ __forceinline__ void aggregate_step_expr(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
+                                                       uint64_t* __restrict__ tbl, int64_t G) {
+  const uint32_t m = (mask >> Q) & ((1u << kExprStep) - 1u);
+  const KExpr& E = expr_programs(p);
+  uint32_t ids[kExprStep];
+  int32_t key[kExprStep];
+#pragma unroll
+  for (int i = 0; i < kExprStep; ++i) key[i] = -(int32_t)p.key_bias;
+  for (int j = 0; j < p.num_keys; ++j) {
+    KColC& c = S.cols[p.key_col[j]];
+    decode_step<Q>(c.fwd, c.bits, group, ids);
+    const int32_t stride = (int32_t)p.key_stride[j];
+    if (c.lut) {  // segment-uniform
+      gmem<int32_t>* __restrict__ lut = gp(c.lut);
+      int32_t g[kExprStep];
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i) g[i] = lut[ids[i]];
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i) key[i] += g[i] * stride;
+    } else {
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i) key[i] += ((int32_t)ids[i] + c.lut_off) * stride;
+    }
+  }
+  double ev[kExprStep];
+  int prev_prog = -1, prev_col = -1;
+  for (int s = 0; s < p.num_slots; ++s) {
+    const int kind = p.slot_kind[s];
+    int64_t ikey[kExprStep];
+    double dval[kExprStep];
+#pragma unroll
+    for (int i = 0; i < kExprStep; ++i) { ikey[i] = 0; dval[i] = 0.0; }
+    const int pi = kind != SLOT_COUNT ? E.slot_prog[s] : -1;  // wave-uniform
+    if (pi >= 0) {
+      if (pi != prev_prog) {
+        expr_eval_group<Q>(E.prog[pi], S, group, ev);
+        prev_prog = pi;
+      }
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i) {
+        if (kind == SLOT_SUM_F64) dval[i] = ev[i];
+        else ikey[i] = expr_value_key(ev[i]);
+      }
+    } else if (kind != SLOT_COUNT) {
+      const int col = p.slot_col[s];
+      KColC& c = S.cols[col];
+      if (col != prev_col) {
+        decode_step<Q>(c.fwd, c.bits, group, ids);
+        vidx_n(c, ids);
+        prev_col = col;
+      }
+      if (kind == SLOT_SUM_F64) {
+        gmem<double>* __restrict__ dv = gp(c.dval);
+#pragma unroll
+        for (int i = 0; i < kExprStep; ++i) dval[i] = dv[ids[i]];
+      } else if (c.dkey) {
+        gmem<int64_t>* __restrict__ dk = gp(c.dkey);
+#pragma unroll
+        for (int i = 0; i < kExprStep; ++i) ikey[i] = dk[ids[i]];
+      } else {
+#pragma unroll
+        for (int i = 0; i < kExprStep; ++i) ikey[i] = c.key_base + (int64_t)ids[i];
+      }
+    }
+    if (G == 1) {  // single row: fold the lane's docs, then the wave
+      int64_t iacc = slot_identity(kind);
+      double facc = 0.0;
+#pragma unroll
+      for (int i = 0; i < kExprStep; ++i)
+        if ((m >> i) & 1u) { iacc = slot_fold(kind, iacc, ikey[i]); facc += dval[i]; }
+      accumulate_wave(tbl + s, kind, __popc(m), iacc, facc);
+      continue;
+    }
+    if (MODE == MODE_LDS && p.pack_slot >= 0) {  // KParams.pack_slot: the pack slot adds the COUNT too
+      if (kind == SLOT_COUNT) continue;
+      if (s == p.pack_slot) {
+#pragma unroll
+        for (int i = 0; i < kExprStep; ++i)
+          if ((m >> i) & 1u)
+            atomicAdd(reinterpret_cast<unsigned long long*>(tbl + (int64_t)s * G + key[i]),
+                      (1ull << p.pack_shift) | (unsigned long long)ikey[i]);
+        continue;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kExprStep; ++i)
+      if ((m >> i) & 1u) accumulate<MODE>(tbl, (int64_t)s * G + key[i], kind, ikey[i], dval[i]);
+  }
+}
+
+template <int MODE, int... K>
+__device__ __forceinline__ void aggregate_steps_expr(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
+                                                     uint64_t* __restrict__ tbl, int64_t G,
+                                                     std::integer_sequence<int, K...>) {
+  // (wave-uniform conditions: the single-row fold inside uses cross-lane shuffles)
+  ((__any(((mask >> (K * kExprStep)) & ((1u << kExprStep) - 1u)) != 0u)
+        ? aggregate_step_expr<MODE, K * kExprStep>(p, S, group, mask, tbl, G)
+        : (void)0),
+   ...);
+}
+
 // Aggregates the matched docs (bits of `mask`) of this lane's 32-doc group `group` of segment S, 16 docs at a
 // time.  Dense key spaces only (MODE_LDS / MODE_GLOBAL: composite keys < 2^31).  Docs beyond numDocs decode from
 // the zero padding to dictId 0 (in bounds) and are never in `mask`.
@@ -1098,6 +1355,10 @@ template <int MODE, bool SIMPLE = false, bool FX = false, int DC = kSideNone>
 __device__ __forceinline__ void aggregate_group(const KParams& p, const SegView& S, int64_t group, uint32_t mask,
                                                 uint64_t* __restrict__ tbl, int64_t G) {
   // wave-uniform conditions: the single-row (G == 1) fold inside uses cross-lane shuffles
+  if constexpr (DC == kSideExpr) {  // the expression instance: kExprStep docs at a time (aggregate_step_expr)
+    aggregate_steps_expr<MODE>(p, S, group, mask, tbl, G, std::make_integer_sequence<int, 32 / kExprStep>{});
+    return;
+  }
   if (__any((mask & 0xFFFFu) != 0u)) aggregate_half<MODE, 0, SIMPLE, FX, DC>(p, S, group, mask, tbl, G);
   if (__any((mask >> 16) != 0u)) aggregate_half<MODE, 16, SIMPLE, FX, DC>(p, S, group, mask, tbl, G);
 }

@@ -163,6 +163,8 @@ struct DictView {
   std::string name;
 };
 int table_dict_view(pgpu_table t, int col, DictView* out);
+// The name of a table column: a real column's, or a virtual column's (an expression in function form: mult(price,qty)).
+int table_column_name(pgpu_table t, int col, std::string* out);
 // The dictionary snapshot group-by key `key` of result r indexes (the table's current one for results without).
 int result_key_dict_view(const pgpu_result_s* r, pgpu_table t, int key, DictView* out);
 

@@ -14,6 +14,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "expr_eval.h"   // ExprProg: the programs of expression aggregations
 #include "tile_split.h"  // kBlock, kMaxStack, kWaveQ: the scan's LDS layout and tile split
 
 namespace pgpu {
@@ -263,6 +264,26 @@ struct KHist {
 struct KParamsHist : KParams {
   KHist hs;
 };
+// Expression aggregations of a plan (SUM(price * qty): the aggregation's column is a virtual column of the table, a
+// postfix program over real columns, expr_eval.h).  prog[e]: the plan's distinct programs, their col[] holding the
+// record indexes (KCol) of their operand columns; slot_prog[s]: the program whose value slot s aggregates, -1 for a
+// slot of a real column or the COUNT.  A slot of a program is SLOT_SUM_F64 (SUM / AVG: the doubles are added),
+// SLOT_MIN_KEY or SLOT_MAX_KEY (on expr_value_key of the double).  Slots are made in aggregation order; the slots of
+// one program share its evaluation per matched doc as long as no slot of another program lies between them (a slot of
+// a real column between them does not break the sharing): SUM(a*b), SUM(a), MAX(a*b) evaluate a*b once, SUM(a*b),
+// SUM(c-d), MAX(a*b) twice.
+struct KExpr {
+  int32_t n;
+  int32_t pad;
+  int32_t slot_prog[kMaxSlots];
+  ExprProg prog[kMaxPlanExprs];
+};
+// The parameters of the scan's expression instance (filter_groupby_expr_kernel): KParams and the programs.  A type of
+// its own, as KParamsFx, KParamsDc and KParamsHist are.
+struct KParamsExpr : KParams {
+  KExpr ex;
+};
+static_assert(sizeof(KParamsExpr) <= 4096, "kernel arguments of the expression instance");
 // What percentile_select_kernel resolves from the histograms: per histogram the column's global values as doubles
 // (null where only a DISTINCTCOUNT reads it) and the row of its DISTINCTCOUNT (-1: none); per PERCENTILE aggregation
 // its row, its histogram and its percentile in ten-thousandths (pgpu_agg.fn bits 8..31).
@@ -289,12 +310,17 @@ struct KPctSelect {
 //                   plans have dense key spaces, so there is none in MODE_HASH
 //   10, 11 HIST     the sparse / dense instance of plans with PERCENTILE aggregations (SLOT_PERCENTILE rows and side
 //                   histograms, filter_groupby_hist_kernel); dense key spaces again
+//   12, 13 EXPR     the sparse / dense instance of plans with expression aggregations (filter_groupby_expr_kernel,
+//                   KParamsExpr).  Sparse: every accumulator mode.  Dense: the whole-group decode, 4 docs of a lane's
+//                   group per step (aggregate_step_expr, kExprStep); dense key spaces, so none in MODE_HASH
 enum ScanVariant : int32_t { kScanSparse = 0, kScanDense, kScanDenseSimple, kScanPair, kScanFast, kScanFastWide,
-                             kScanFxSparse, kScanFxDense, kScanDcSparse, kScanDcDense, kScanHistSparse, kScanHistDense };
-constexpr int kScanVariants = 12;
-// The kernel template of an instance, i.e. the parameter block it takes: KParams, KParamsFx, KParamsDc, KParamsHist.
-enum ScanFamily : int32_t { SCAN_BASE = 0, SCAN_FX = 1, SCAN_DC = 2, SCAN_HIST = 3 };
-constexpr int kScanFamilies = 4;
+                             kScanFxSparse, kScanFxDense, kScanDcSparse, kScanDcDense, kScanHistSparse, kScanHistDense,
+                             kScanExprSparse, kScanExprDense };
+constexpr int kScanVariants = 14;
+// The kernel template of an instance, i.e. the parameter block it takes: KParams, KParamsFx, KParamsDc, KParamsHist,
+// KParamsExpr.
+enum ScanFamily : int32_t { SCAN_BASE = 0, SCAN_FX = 1, SCAN_DC = 2, SCAN_HIST = 3, SCAN_EXPR = 4 };
+constexpr int kScanFamilies = 5;
 struct ScanInstance {
   ScanFamily family;
   uint32_t modes;                  // bit m: the instance exists in accumulator mode m
@@ -315,6 +341,8 @@ constexpr ScanInstance kScanInstances[kScanVariants] = {
     {SCAN_DC, 1u << MODE_LDS | 1u << MODE_GLOBAL, true, false, false, false, 2},   // kScanDcDense
     {SCAN_HIST, 1u << MODE_LDS | 1u << MODE_GLOBAL, false, false, false, false, 2},  // kScanHistSparse
     {SCAN_HIST, 1u << MODE_LDS | 1u << MODE_GLOBAL, true, false, false, false, 2},   // kScanHistDense
+    {SCAN_EXPR, kScanAllModes, false, false, false, false, 2},              // kScanExprSparse
+    {SCAN_EXPR, 1u << MODE_LDS | 1u << MODE_GLOBAL, true, false, false, false, 2},  // kScanExprDense
 };
 
 // A kernel as its object hands it out: the host pointer hipLaunchKernel / the occupancy query take, and its block size.
@@ -536,9 +564,9 @@ int launch_expand_tiles(const uint8_t* segs, int32_t seg_stride, int32_t num_seg
 // out of range, a mode the instance does not exist in).  Launch and occupancy both resolve through it.
 KernelEntry scan_entry(int mode, int variant);
 // Launches it with its family's parameter block: p (SCAN_BASE), p then fx (SCAN_FX), p then dc (SCAN_DC), p then hs
-// (SCAN_HIST).  -1 where scan_entry has nothing.
-int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, const KHist& hs, int mode, int variant,
-                int grid, size_t lds_bytes, void* stream);
+// (SCAN_HIST), p then ex (SCAN_EXPR).  -1 where scan_entry has nothing.
+int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, const KHist& hs, const KExpr& ex, int mode,
+                int variant, int grid, size_t lds_bytes, void* stream);
 // PERCENTILE's final step over table [num_slots][num_keys]: per key with docs (COUNT, row 0, not 0) row
 // sel.pct_slot[a] <- the double of the value at the aggregation's target index of the key's sorted values, read off
 // the key's histogram row; row sel.dc_slot[h] <- the row's non-zero cells.  A key without docs keeps its zeros.

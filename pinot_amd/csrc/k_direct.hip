@@ -1,12 +1,12 @@
 // k_direct.hip — the direct-load scan kernel's instances of one family in one accumulator mode: compiled with
-// -DPGPU_FAMILY=0|1|2|3 (ScanFamily: base, FX, DC, HIST) and -DPGPU_MODE=0|1|2 (LDS, GLOBAL, HASH).  Which instances those
+// -DPGPU_FAMILY=0|1|2|3|4 (ScanFamily: base, FX, DC, HIST, EXPR) and -DPGPU_MODE=0|1|2 (LDS, GLOBAL, HASH).  Which instances those
 // are, and their template arguments, is kScanInstances' to say (internal.h).
 #include <utility>
 
 #include "scan_direct.h"
 
 #if !defined(PGPU_MODE) || !defined(PGPU_FAMILY)
-#error "compile with -DPGPU_FAMILY=0 (base), 1 (FX), 2 (DC) or 3 (HIST) and -DPGPU_MODE=0 (LDS), 1 (GLOBAL) or 2 (HASH)"
+#error "compile with -DPGPU_FAMILY=0 (base), 1 (FX), 2 (DC), 3 (HIST) or 4 (EXPR) and -DPGPU_MODE=0 (LDS), 1 (GLOBAL) or 2 (HASH)"
 #endif
 #if (PGPU_FAMILY == 2 || PGPU_FAMILY == 3) && PGPU_MODE == 2
 #error "the DC and HIST instances exist for MODE_LDS and MODE_GLOBAL only"
@@ -26,6 +26,8 @@ static const void* instance() {
     return reinterpret_cast<const void*>(filter_groupby_dc_kernel<PGPU_MODE, I.dense>);
   else if constexpr (I.family == SCAN_HIST)
     return reinterpret_cast<const void*>(filter_groupby_hist_kernel<PGPU_MODE, I.dense>);
+  else if constexpr (I.family == SCAN_EXPR)
+    return reinterpret_cast<const void*>(filter_groupby_expr_kernel<PGPU_MODE, I.dense>);
   else
     return reinterpret_cast<const void*>(
         filter_groupby_kernel<PGPU_MODE, I.dense, I.simple, I.pair, I.fast, I.lane_batch>);

@@ -828,13 +828,15 @@ PGPU_FAMILY_DECLS(0)
 PGPU_FAMILY_DECLS(1)
 PGPU_FAMILY_DECLS(2)
 PGPU_FAMILY_DECLS(3)
+PGPU_FAMILY_DECLS(4)
 #undef PGPU_FAMILY_DECLS
 #undef PGPU_MODE_DECLS
 static KernelEntry (*const kScanObjects[kScanFamilies][3])(ScanVariant) = {  // [ScanFamily][Mode]
     {scan_entry_f0_m0, scan_entry_f0_m1, scan_entry_f0_m2},
     {scan_entry_f1_m0, scan_entry_f1_m1, scan_entry_f1_m2},
     {scan_entry_f2_m0, scan_entry_f2_m1, nullptr},
-    {scan_entry_f3_m0, scan_entry_f3_m1, nullptr}};
+    {scan_entry_f3_m0, scan_entry_f3_m1, nullptr},
+    {scan_entry_f4_m0, scan_entry_f4_m1, scan_entry_f4_m2}};
 static KernelEntry (*const kStarObjects[2][3])() = {  // [fx][Mode]
     {star_entry_f0_m0, star_entry_f0_m1, star_entry_f0_m2}, {star_entry_f1_m0, star_entry_f1_m1, star_entry_f1_m2}};
 
@@ -857,13 +859,14 @@ KernelEntry scan_entry(int mode, int variant) {
   return kScanObjects[I.family][mode]((ScanVariant)variant);
 }
 
-int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, const KHist& hs, int mode, int variant,
-                int grid, size_t lds_bytes, void* stream) {
+int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, const KHist& hs, const KExpr& ex, int mode,
+                int variant, int grid, size_t lds_bytes, void* stream) {
   const KernelEntry e = scan_entry(mode, variant);
   if (!e.fn) return -1;
   KParamsFx kf;
   KParamsDc kd;
   KParamsHist kh;
+  KParamsExpr ke;
   switch (kScanInstances[variant].family) {
     case SCAN_FX:
       static_cast<KParams&>(kf) = p;
@@ -879,6 +882,20 @@ int launch_scan(const KParams& p, const KFxSplit& fx, const KDistinct& dc, const
       static_cast<KParams&>(kh) = p;
       kh.hs = hs;
       return launch_entry(e, grid, lds_bytes, stream, &kh);
+    case SCAN_EXPR:
+      // (the programs index the records' KCol and their own operands: checked here, where the launch still can refuse)
+      if (ex.n <= 0 || ex.n > kMaxPlanExprs) return -1;
+      for (int i = 0; i < ex.n; ++i) {
+        const ExprProg& g = ex.prog[i];
+        if (g.nops < 1 || g.nops > kExprMaxOps || g.ncols < 1 || g.ncols > kExprMaxCols) return -1;
+        for (int c = 0; c < g.ncols; ++c)
+          if (g.col[c] < 0 || g.col[c] >= p.num_cols) return -1;
+      }
+      for (int s = 0; s < kMaxSlots; ++s)
+        if (ex.slot_prog[s] >= ex.n) return -1;
+      static_cast<KParams&>(ke) = p;
+      ke.ex = ex;
+      return launch_entry(e, grid, lds_bytes, stream, &ke);
     default:
       return launch_entry(e, grid, lds_bytes, stream, &p);
   }

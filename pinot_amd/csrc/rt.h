@@ -237,12 +237,9 @@ inline const double kCanonicalNaN = [] {
 // lane's whole group).
 inline int64_t raw_padded_docs(int64_t n) { return std::max<int64_t>((n + 31) & ~int64_t(31), 32); }
 
-// Order-preserving int64 key of a double (MIN/MAX operand on the device).
-inline int64_t double_key(double d) {
-  int64_t b;
-  memcpy(&b, &d, 8);
-  return b >= 0 ? b : (b ^ INT64_MAX);
-}
+// Order-preserving int64 key of a double (MIN/MAX operand on the device): the function the scan's expression
+// instance computes from a program's value (expr_eval.h).
+inline int64_t double_key(double d) { return pgpu::double_key_bits(d); }
 inline double key_double(int64_t k) {
   int64_t b = k >= 0 ? k : (k ^ INT64_MAX);
   double d;
@@ -264,6 +261,11 @@ constexpr int64_t kMaxParts = 16384;                 // K8a/K8c LDS histogram en
 constexpr int64_t kHashPartLdsMax = 64 * 1024;       // K8h LDS hash table per partition, at most
 constexpr int64_t kPartMaxRecordBytes = 32ll << 30;  // scratch for the partitioned records
 constexpr int kDocIdColumn = -2;                     // query column of the virtual $docId (hidden first-doc slot)
+// slot_tcol of a slot that aggregates the plan's expression e (pgpu_plan_s::exprs): negative, as every slot_tcol that is
+// no real column
+constexpr int kExprColumnBase = -16;
+inline int expr_tcol(int e) { return kExprColumnBase - e; }
+inline bool is_expr_tcol(int c) { return c <= kExprColumnBase; }
 
 inline bool is_int_type(int t) { return t == PGPU_INT || t == PGPU_LONG; }
 inline bool is_fp_type(int t) { return t == PGPU_FLOAT || t == PGPU_DOUBLE; }
@@ -562,6 +564,15 @@ struct pgpu_table_s {
   std::vector<std::string> names;
   std::vector<int32_t> types;
   std::mutex mu;
+  // Virtual columns (pgpu_table_add_expression): expression e is column names.size() + e of the table, a DOUBLE to
+  // everything downstream of the scan.  prog.col[] holds table columns; ops is the program as registered (the getter
+  // returns it; an identical one registered again gets the same column).  Under mu; entries are never removed.
+  struct Expr {
+    pgpu::ExprProg prog;
+    std::vector<pgpu::ExprOpIn> ops;
+    std::string name;
+  };
+  std::vector<Expr> exprs;
   std::unordered_map<int64_t, std::shared_ptr<Segment>> segments;
   std::vector<std::shared_ptr<Segment>> by_handle;  // handle -> segment (handles are dense), null once unpinned
   int64_t next_handle = 1;
@@ -720,6 +731,27 @@ struct pgpu_plan_s {
   std::vector<KeyLut> hist_lut;
   // a row the scan leaves to a post-scan kernel (distinct_popcount_kernel / percentile_select_kernel): reads no values
   bool side_slot(size_t s) const { return slot_dc[s] >= 0 || slot_pct[s] >= 0; }
+  // Expression aggregations (SUM(price * qty)): the plan's distinct programs, copied from the table's virtual columns
+  // when the slots are assigned (prog.col[]: table columns; the scan's copy holds record indexes, fill_kexpr).  A slot
+  // of expression e has slot_tcol = expr_tcol(e) (below every real column and kDocIdColumn), slot_expr = e and a kind
+  // of SLOT_SUM_F64 / SLOT_MIN_KEY / SLOT_MAX_KEY; slot_expr is -1 for every other slot.  Such a plan launches the
+  // scan's expression instance (kScanExprSparse).
+  struct PlanExpr {
+    int32_t vcol = 0;  // the table's virtual column
+    pgpu::ExprProg prog;
+  };
+  std::vector<PlanExpr> exprs;
+  std::vector<int32_t> slot_expr;
+  // the table columns slot s reads values of: its column, or the operands of its program
+  void slot_value_cols(size_t s, std::vector<int32_t>* out) const {
+    out->clear();
+    if (slot_expr[s] >= 0) {
+      const pgpu::ExprProg& g = exprs[slot_expr[s]].prog;
+      out->assign(g.col, g.col + g.ncols);
+    } else if (slot_tcol[s] >= 0) {
+      out->push_back(slot_tcol[s]);
+    }
+  }
   std::vector<int32_t> agg_fn, agg_slot, agg_col;   // per aggregation: fn, value slot (or -1), table column
   int num_projected = 0;
   // per-segment compiled data
@@ -917,6 +949,23 @@ inline int percentile_decline(const char* what) {
   return fail(PGPU_ERR_UNSUPPORTED, "%s with PERCENTILE: per-rank percentiles do not merge (the value histograms would "
                          "have to be added)", what);
 }
+// Plans with expression aggregations: their rows are ordinary rows of a DOUBLE column, so the cross-GPU entry points
+// take them as they are; a caller's table (d_table) is declined, as for the other families with a parameter block of
+// their own.
+inline bool plan_has_expr(const pgpu_plan_s* P) {
+  if (!P->exprs.empty()) return true;
+  for (const auto& part : P->parts)
+    if (part.plan && !part.plan->exprs.empty()) return true;
+  return false;
+}
+inline bool query_has_expr(const pgpu_table_s* t, const pgpu_query* q) {
+  for (int i = 0; q && q->aggs && i < q->num_aggs; ++i)
+    if (PGPU_AGG_FN(q->aggs[i].fn) != PGPU_AGG_COUNT && q->aggs[i].column >= (int)t->names.size()) return true;
+  return false;
+}
+inline int expr_decline(const char* what) {
+  return fail(PGPU_ERR_UNSUPPORTED, "%s with an expression aggregation: such plans run on their own tables", what);
+}
 inline int fx_decline(const char* what) {
   return fail(PGPU_ERR_UNSUPPORTED, "%s with PGPU_OPT_EXACT_FP_SUM: the ranks would have to agree on the "
                          "fixed-point format (E, K, W) first", what);
@@ -994,6 +1043,7 @@ struct ExecCtx {
   KDistinct dc{};  // the side bitmaps of the plan's DISTINCTCOUNT aggregations (n = 0: none)
   KHist hs{};      // the side histograms of a plan with PERCENTILE aggregations (n = 0: none; then dc.n = 0)
   KPctSelect sel{};  // ... and what percentile_select_kernel resolves from them
+  KExpr ex{};      // the programs of a plan with expression aggregations (n = 0: none)
   // PGPU_TRACE=1: host time marks of the execution, printed when it took over a millisecond
   std::vector<std::pair<const char*, double>> marks;
   void mark(const char* what) { if (trace_on()) marks.emplace_back(what, now_us()); }

@@ -133,6 +133,15 @@ int pgpu::table_dict_view(pgpu_table t, int col, DictView* out) {
   return 0;
 }
 
+int pgpu::table_column_name(pgpu_table t, int col, std::string* out) {
+  if (!t || col < 0) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
+  std::lock_guard<std::mutex> g(t->mu);
+  const int e = col - (int)t->names.size();
+  if (e >= (int)t->exprs.size()) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
+  *out = e < 0 ? t->names[col] : t->exprs[e].name;
+  return 0;
+}
+
 int pgpu::result_key_dict_view(const pgpu_result_s* r, pgpu_table t, int key, DictView* out) {
   if (!r || key < 0 || key >= r->num_keys) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad group-by key %d", key);
   if ((int)r->key_dicts.size() <= key || !r->key_dicts[key]) return table_dict_view(t, r->key_cols[key], out);

@@ -369,6 +369,16 @@ static void fill_kparams(const pgpu_plan_s* P, uint64_t deadline, ExecCtx& X) {
     for (const pgpu_plan_s::Distinct& d : P->dc) kp.slot_kind[d.slot] = SLOT_PERCENTILE;
     for (const pgpu_plan_s::Percentile& e : P->pct) kp.slot_kind[e.slot] = SLOT_PERCENTILE;
   }
+  // expression aggregations (X.ex): the programs with their operands as record indexes, and each slot's program
+  memset(&X.ex, 0, sizeof X.ex);
+  for (int sl = 0; sl < kMaxSlots; ++sl) X.ex.slot_prog[sl] = sl < nslots ? P->slot_expr[sl] : -1;
+  X.ex.n = (int32_t)P->exprs.size();
+  for (size_t e = 0; e < P->exprs.size(); ++e) {
+    ExprProg& g = X.ex.prog[e];
+    g = P->exprs[e].prog;
+    for (int c = 0; c < g.ncols; ++c)  // (bound by plan_expr; launch_scan refuses an index outside the records)
+      g.col[c] = (int32_t)(std::find(P->query_cols.begin(), P->query_cols.end(), g.col[c]) - P->query_cols.begin());
+  }
   kp.pair_leaves = 1;
   dense_lds_forms(P, &kp.pack_slot, &kp.narrow);
   kp.pack_shift = P->pack_shift;
@@ -846,7 +856,7 @@ static int launch_scan_chunk(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X, KPa
   P->last_scan.alone = P->alone;
   P->last_scan.declined = !fits;
   // (the instance's family takes what it needs: the split of the fixed-point slots, the side bitmaps, or neither)
-  if (launch_scan(kp, fx_split(P), X.dc, X.hs, P->mode, P->variant, grid, P->lds_bytes, stream))
+  if (launch_scan(kp, fx_split(P), X.dc, X.hs, X.ex, P->mode, P->variant, grid, P->lds_bytes, stream))
     return fail(PGPU_ERR_DEVICE, "scan launch failed: %s", hipGetErrorString(hipGetLastError()));
   X.mark("scan launched");
   if (wg_times) TRY(diag_wg_times_report(P->table, kp, grid, stream));

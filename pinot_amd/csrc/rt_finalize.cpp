@@ -429,7 +429,9 @@ void describe_result(const pgpu_plan_s* P, pgpu_result_s* R) {
     if (fn == PGPU_AGG_SUM || fn == PGPU_AGG_AVG)
       R->agg_conv[a] = P->slot_kind[P->agg_slot[a]] == SLOT_SUM_I64 ? RCONV_I64 : RCONV_F64;
     else
-      R->agg_conv[a] = is_int_type(P->table->types[P->agg_col[a]]) ? RCONV_I64 : RCONV_KEY_F64;
+      // (MIN / MAX of an expression, a virtual column past the table's real ones: the key of its double)
+      R->agg_conv[a] = P->agg_col[a] < (int)P->table->types.size() && is_int_type(P->table->types[P->agg_col[a]])
+                           ? RCONV_I64 : RCONV_KEY_F64;
   }
   // fixed-point FLOAT / DOUBLE sums (PGPU_OPT_EXACT_FP_SUM): W digit sums from the aggregation's slot on, converted to
   // the one double on the result's first read -- after the merge for the parts of a composite plan

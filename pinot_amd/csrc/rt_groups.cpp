@@ -53,6 +53,8 @@ int split_for_groups_limit(pgpu_table_s* t, const int64_t* handles, int32_t nseg
   if (!any_sensitive && !cap_may_bind) return 0;
   if (query_has_percentile(q))  // (first: the message names the function the plan would be built around)
     return fail(PGPU_ERR_UNSUPPORTED, "PERCENTILE in a numGroupsLimit (composite) plan");
+  if (query_has_expr(t, q))  // (the parts would each need the expression instance and its declines: not built)
+    return fail(PGPU_ERR_UNSUPPORTED, "an expression aggregation in a numGroupsLimit (composite) plan");
   if (query_has_distinct(q))  // the parts' rows are merged on the host: distinct counts do not add
     return fail(PGPU_ERR_UNSUPPORTED, "DISTINCTCOUNT in a numGroupsLimit (composite) plan");
   std::vector<int32_t> rest;

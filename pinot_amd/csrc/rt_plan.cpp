@@ -602,6 +602,8 @@ int query_fp_sum_ranges(pgpu_table_s* t, const std::vector<Segment*>& segs, cons
   for (int i = 0; i < q->num_aggs; ++i) {
     const pgpu_agg& a = q->aggs[i];
     out[i] = FxAgree{};
+    if (a.column >= ncols && query_has_expr(t, q))
+      return fail(PGPU_ERR_UNSUPPORTED, "an expression aggregation with PGPU_OPT_EXACT_FP_SUM");
     if (a.fn != PGPU_AGG_SUM && a.fn != PGPU_AGG_AVG) continue;
     if (a.column < 0 || a.column >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: bad column", i);
     if (t->types[a.column] == PGPU_STRING) return fail(PGPU_ERR_UNSUPPORTED, "numeric aggregation over a STRING column");

@@ -153,7 +153,9 @@ int compile_filter(const pgpu_query* q, std::vector<int32_t>* ops, bool* pure_an
 void push_slot(pgpu_plan_s* P, int kind, int tcol, int fx_digit, const FxFormat& fmt) {
   P->slot_kind.push_back(kind);
   P->slot_tcol.push_back(tcol);
-  P->slot_col.push_back(tcol == -1 ? 0 : query_col(P, tcol));
+  // (a slot of an expression reads its program's operand columns, bound by add_expr_slot: no query column of its own)
+  P->slot_col.push_back(tcol == -1 || is_expr_tcol(tcol) ? 0 : query_col(P, tcol));
+  P->slot_expr.push_back(-1);
   P->slot_fx.push_back(fx_digit);
   P->slot_fmt.push_back(fmt);
   P->slot_dc.push_back(-1);
@@ -206,6 +208,40 @@ int add_percentile_slot(pgpu_plan_s* P, int tcol, int32_t p_e4) {
   P->slot_pct[e.slot] = (int32_t)P->pct.size();
   P->pct.push_back(e);
   return e.slot;
+}
+
+// The plan's entry of the table's virtual column vcol (an expression), added on first use with its operand columns as
+// query columns (*out).  The program is copied under the table mutex (registrations append to the table's list).
+int plan_expr(PlanCtx& cx, int vcol, int* out) {
+  pgpu_plan_s* P = cx.P;
+  for (size_t e = 0; e < P->exprs.size(); ++e)
+    if (P->exprs[e].vcol == vcol) { *out = (int)e; return 0; }
+  pgpu_plan_s::PlanExpr pe;
+  pe.vcol = vcol;
+  {
+    std::lock_guard<std::mutex> g(cx.t->mu);
+    const int e = vcol - (int)cx.t->names.size();
+    if (e < 0 || e >= (int)cx.t->exprs.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation: bad column %d", vcol);
+    pe.prog = cx.t->exprs[e].prog;
+  }
+  if ((int)P->exprs.size() >= kMaxPlanExprs)
+    return fail(PGPU_ERR_UNSUPPORTED, "more than %d distinct expression aggregations in one query", kMaxPlanExprs);
+  for (int c = 0; c < pe.prog.ncols; ++c) {
+    for (const Segment* s : P->segs)
+      if (s->cols[pe.prog.col[c]].raw)
+        return fail(PGPU_ERR_UNSUPPORTED, "expression over raw (no-dictionary) column %d", pe.prog.col[c]);
+    query_col(P, pe.prog.col[c]);
+  }
+  P->exprs.push_back(pe);
+  *out = (int)P->exprs.size() - 1;
+  return 0;
+}
+
+// The slot of (kind, expression e): SUM and AVG share the float64 sum, MIN and MAX have a key row each.
+int add_expr_slot(pgpu_plan_s* P, int kind, int e) {
+  const int s = add_slot(P, kind, expr_tcol(e));
+  P->slot_expr[s] = e;
+  return s;
 }
 
 // The W digit slots of a fixed-point sum: adjacent, of the one column, shared by SUM and AVG of the column.
@@ -298,7 +334,30 @@ int assign_slots(PlanCtx& cx) {
     if (fn != PGPU_AGG_PERCENTILE && a.fn != fn) return fail(PGPU_ERR_UNSUPPORTED, "aggregation function %d", a.fn);
     P->agg_fn.push_back(fn);
     P->agg_col.push_back(a.column);
-    if (fn == PGPU_AGG_COUNT) { P->agg_slot.push_back(0); continue; }
+    if (fn == PGPU_AGG_COUNT) {  // (COUNT never reads its argument, but the column must be one: the results name it)
+      if (a.column >= ncols) {
+        std::lock_guard<std::mutex> g(cx.t->mu);
+        if (a.column - ncols >= (int)cx.t->exprs.size())
+          return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: bad column", i);
+      }
+      P->agg_slot.push_back(0);
+      continue;
+    }
+    if (a.column >= ncols) {  // a virtual column: an expression over real columns (pgpu_table_add_expression)
+      if (fn == PGPU_AGG_DISTINCTCOUNT || fn == PGPU_AGG_PERCENTILE)
+        return fail(PGPU_ERR_UNSUPPORTED, "%s of an expression (virtual column %d)",
+                    fn == PGPU_AGG_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT", a.column);
+      if (fn != PGPU_AGG_SUM && fn != PGPU_AGG_AVG && fn != PGPU_AGG_MIN && fn != PGPU_AGG_MAX)
+        return fail(PGPU_ERR_UNSUPPORTED, "aggregation function %d", a.fn);
+      if (q->options & PGPU_OPT_EXACT_FP_SUM)
+        return fail(PGPU_ERR_UNSUPPORTED, "an expression aggregation with PGPU_OPT_EXACT_FP_SUM");
+      int e = 0;
+      TRY(plan_expr(cx, a.column, &e));
+      P->agg_slot.push_back(add_expr_slot(P, fn == PGPU_AGG_MIN   ? SLOT_MIN_KEY
+                                             : fn == PGPU_AGG_MAX ? SLOT_MAX_KEY
+                                                                  : SLOT_SUM_F64, e));
+      continue;
+    }
     if (a.column < 0 || a.column >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation %d: bad column", i);
     if (fn == PGPU_AGG_PERCENTILE) {
       const int32_t p_e4 = PGPU_AGG_PERCENTILE_E4(a.fn);
@@ -364,11 +423,31 @@ int assign_slots(PlanCtx& cx) {
     P->cfg.hash_partitions = 0;
     P->cfg.stream_chunks = 1;
   }
+  if (!P->exprs.empty()) {
+    // the scan's expression instance: its own family, so not beside the side structures of another; one launch on the
+    // scan kernel's own tables (LDS, global, hash), never the partitioned pipelines
+    if (!P->dc.empty() || !P->pct.empty())
+      return fail(PGPU_ERR_UNSUPPORTED, "an expression aggregation in one query with %s",
+                  !P->pct.empty() ? "PERCENTILE" : "DISTINCTCOUNT");
+    if (P->first_doc_slot) return fail(PGPU_ERR_UNSUPPORTED, "an expression aggregation in a numGroupsLimit (composite) plan");
+    if (cx.se && cx.se->d_table) return fail(PGPU_ERR_UNSUPPORTED, "an expression aggregation with an external table");
+    P->cfg.partitioned_group_by = 0;
+    P->cfg.hash_partitions = 0;
+    P->cfg.stream_chunks = 1;
+  }
   if ((int)P->slot_kind.size() > kMaxSlots) return fail(PGPU_ERR_UNSUPPORTED, "too many accumulators");
   if ((int)P->query_cols.size() > kMaxQueryCols) return fail(PGPU_ERR_UNSUPPORTED, "too many columns");
-  // TransformOperator.getNumColumnsProjected: distinct group-by and aggregation columns
+  // TransformOperator.getNumColumnsProjected: distinct group-by and aggregation columns -- for an expression the
+  // columns it names (AggregationOperator.java:90 counts the projection's columns, each once)
   std::vector<int> proj(P->key_cols.begin(), P->key_cols.end());
-  for (int i = 0; i < q->num_aggs; ++i) if (q->aggs[i].column >= 0) proj.push_back(q->aggs[i].column);
+  for (int i = 0; i < q->num_aggs; ++i) {
+    if (q->aggs[i].column >= ncols) {  // (a COUNT never reads its argument: of an expression it projects nothing)
+      for (const pgpu_plan_s::PlanExpr& pe : P->exprs)
+        if (pe.vcol == q->aggs[i].column) proj.insert(proj.end(), pe.prog.col, pe.prog.col + pe.prog.ncols);
+      continue;
+    }
+    if (q->aggs[i].column >= 0) proj.push_back(q->aggs[i].column);
+  }
   std::sort(proj.begin(), proj.end());
   P->num_projected = (int)(std::unique(proj.begin(), proj.end()) - proj.begin());
   return 0;
@@ -418,8 +497,12 @@ int plan_segment_arrays(PlanCtx& cx) {
       kl.lut = col.lut_off >= 0 ? nullptr : reinterpret_cast<const int32_t*>(col.lut->p);
       kl.off = col.lut_off;
     }
-    for (size_t k = 1; k < P->slot_kind.size(); ++k)
-      if (P->slot_tcol[k] != kDocIdColumn && !P->side_slot(k)) TRY(ensure_values(t, *s, P->slot_tcol[k], stream));
+    std::vector<int32_t> vcols;
+    for (size_t k = 1; k < P->slot_kind.size(); ++k) {
+      if (P->side_slot(k)) continue;
+      P->slot_value_cols(k, &vcols);  // the slot's column, or the operands of its expression
+      for (int32_t c : vcols) TRY(ensure_values(t, *s, c, stream));
+    }
     if (P->first_doc_slot) TRY(ensure_docid(t, s->num_docs, stream));
   }
   // the distinct columns' local -> global mapping, as a key column's (after the key LUTs: plan_star_segment indexes
@@ -479,10 +562,14 @@ int plan_global_values(PlanCtx& cx) {
   pgpu_table_s* t = cx.t;
   pgpu_plan_s* P = cx.P;
   P->val_cols.clear();
+  std::vector<int32_t> slot_cols, cols;
   for (size_t k = 1; k < P->slot_kind.size(); ++k) {
-    const int c = P->slot_tcol[k];
     if (P->side_slot(k)) continue;  // a DISTINCTCOUNT / PERCENTILE row reads no values in the scan
-    if (c == kDocIdColumn || std::find(P->val_cols.begin(), P->val_cols.end(), c) != P->val_cols.end()) continue;
+    P->slot_value_cols(k, &slot_cols);  // (the hidden docId slot: none)
+    cols.insert(cols.end(), slot_cols.begin(), slot_cols.end());
+  }
+  for (const int c : cols) {
+    if (std::find(P->val_cols.begin(), P->val_cols.end(), c) != P->val_cols.end()) continue;
     bool any = false;
     for (Segment* s : P->segs) {
       const Column& col = s->cols[c];
@@ -765,7 +852,7 @@ int prepare_translation(PlanCtx& cx) {
     TRY(parse_predicate(t->types[q->predicates[l].column], q->predicates[l], &cx.parsed[l]));
   // (DISTINCTCOUNT: StarTreeUtils finds no function-column pair for it -- such a plan scans)
   cx.star_allowed = q->num_group_by > 0 && !(q->options & PGPU_OPT_NO_STAR_TREE) && P->stage_end.empty() &&
-                    P->dc.empty() && P->pct.empty() && star_composites(P->ops, q, &cx.star_comps);
+                    P->dc.empty() && P->pct.empty() && P->exprs.empty() && star_composites(P->ops, q, &cx.star_comps);
   // Aggregation-only over a match-all segment: COUNT-only is answered from metadata, MIN / MAX / DISTINCTCOUNT-only
   // from the dictionaries (AggregationPlanNode.java:165-183, isFitForDictionaryBasedPlan :233-246; every dictionary
   // value occurs in its segment, so the scan gives the same set) -- same values, numEntriesScannedPostFilter 0
@@ -778,6 +865,8 @@ int prepare_translation(PlanCtx& cx) {
       all_minmax &= q->aggs[i].fn == PGPU_AGG_MIN || q->aggs[i].fn == PGPU_AGG_MAX ||
                     q->aggs[i].fn == PGPU_AGG_DISTINCTCOUNT;
     }
+    // (MIN / MAX of an expression: isFitForDictionaryBasedPlan wants an identifier as the argument -- it scans)
+    if (!P->exprs.empty()) all_minmax = false;
     cx.exempt_kind = all_count || all_minmax;
     cx.minmax_kind = all_minmax && !all_count;
   }
@@ -793,7 +882,9 @@ int prepare_translation(PlanCtx& cx) {
     for (size_t i = 0; i < P->query_cols.size(); ++i)
       if (P->query_cols[i] == P->key_cols[j]) cx.qcol_key[i] = (int)j;
   for (size_t k = 1; k < P->slot_col.size(); ++k)
-    if (!P->side_slot(k)) cx.qcol_val[P->slot_col[k]] = 1;
+    if (!P->side_slot(k) && P->slot_expr[k] < 0) cx.qcol_val[P->slot_col[k]] = 1;
+  for (const pgpu_plan_s::PlanExpr& pe : P->exprs)  // the operands of the expressions: their doubles are gathered
+    for (int c = 0; c < pe.prog.ncols; ++c) cx.qcol_val[query_col(P, pe.prog.col[c])] = 1;
   cx.qcol_dc.assign(P->query_cols.size(), -1);
   for (size_t d = 0; d < P->dc.size(); ++d) cx.qcol_dc[P->dc[d].qcol] = (int)d;
   cx.qcol_hist.assign(P->query_cols.size(), -1);
@@ -972,7 +1063,7 @@ bool fill_kcols(const PlanCtx& cx, size_t i, KCol* kc) {
     gathers |= ((cx.qcol_key[j] >= 0 || cx.qcol_dc[j] >= 0 || cx.qcol_hist[j] >= 0) && kc[j].lut != nullptr) ||
                (cx.qcol_val[j] && kc[j].dkey != nullptr);
   }
-  return gathers;
+  return gathers || !P->exprs.empty();  // (an expression's operands are gathered per matched doc)
 }
 
 // LEAF_SET: the bitset words, every leaf's 8-byte aligned; `field`: the chunk offset of the record's KLeaf::set.
@@ -1182,7 +1273,8 @@ void configure_scan_grid(PlanCtx& cx, int64_t tile_base) {
   const bool fast = !P->dense && !pair && P->pure_and && P->num_leaves <= kFastLeaves;
   P->fast_wide = fast && P->sel_estimate >= 1.0 / 16;
   // plans with DISTINCTCOUNT and plans with SLOT_SUM_FX slots launch their own instances whatever the filter
-  P->variant = !P->pct.empty() ? (P->dense ? kScanHistDense : kScanHistSparse)
+  P->variant = !P->exprs.empty() ? (P->dense ? kScanExprDense : kScanExprSparse)
+               : !P->pct.empty() ? (P->dense ? kScanHistDense : kScanHistSparse)
                : !P->dc.empty() ? (P->dense ? kScanDcDense : kScanDcSparse)
                : P->fx        ? (P->dense ? kScanFxDense : kScanFxSparse)
                : dense_simple ? kScanDenseSimple

@@ -56,6 +56,8 @@ __device__ __forceinline__ uint32_t leap2_entries(uint8_t* __restrict__ maps, in
 // their own again (filter_groupby_dc_kernel, family SCAN_DC, with KParamsDc).
 // HIST: the instances of plans with PERCENTILE aggregations (SLOT_PERCENTILE slots and their side histograms) --
 // filter_groupby_hist_kernel, family SCAN_HIST, with KParamsHist.
+// EXPR: the instances of plans with expression aggregations (slots that take a program's value, KExpr) --
+// filter_groupby_expr_kernel, family SCAN_EXPR, with KParamsExpr.
 // The kernels share their body as text (scan_direct_body.inc): a body function inlined into them changed the
 // scalar register allocation of the existing instances.
 #ifndef PGPU_MIN_WAVES
@@ -96,6 +98,18 @@ template <int MODE, bool DENSE>
 __global__ __launch_bounds__(kBlock, DENSE ? PGPU_DENSE_MIN_WAVES : PGPU_MIN_WAVES) void filter_groupby_hist_kernel(const KParamsHist p) {
   constexpr bool FX = false, SIMPLE = false, PAIR = false, FAST = false;
   constexpr int LANE_BATCH = 2, DC = kSideHist;
+#include "scan_direct_body.inc"
+}
+
+// The sparse and the dense instance for plans with expression aggregations (SUM(price * qty): KExpr, expr_eval.h).
+// Sparse, in every accumulator mode: any filter program, matched docs aggregated in per-lane batches (aggregate_batch),
+// where the operand columns of a program are gathered once per batch and the program is interpreted over a register
+// stack.  Dense (MODE_LDS and MODE_GLOBAL): dense tiles decode whole groups, kExprStep = 4 docs of a lane's group per
+// step (aggregate_step_expr).
+template <int MODE, bool DENSE>
+__global__ __launch_bounds__(kBlock, DENSE ? PGPU_DENSE_MIN_WAVES : PGPU_MIN_WAVES) void filter_groupby_expr_kernel(const KParamsExpr p) {
+  constexpr bool FX = false, SIMPLE = false, PAIR = false, FAST = false;
+  constexpr int LANE_BATCH = 2, DC = kSideExpr;
 #include "scan_direct_body.inc"
 }
 

@@ -31,6 +31,7 @@ namespace {
 
 enum { RC_I64 = 0, RC_F64 = 1, RC_KEY_F64 = 2 };
 
+// (the inverse of double_key_bits, expr_eval.h: key -1 is -0.0, key 0 is +0.0)
 double key_to_double(uint64_t w) {
   int64_t k = (int64_t)w;
   int64_t b = k >= 0 ? k : (k ^ INT64_MAX);
@@ -437,9 +438,8 @@ int pgpu_result_datatable(pgpu_result r, pgpu_table t, void* out, int64_t cap, i
   for (int a = 0; a < na; ++a) {  // AggregationFunction.getResultColumnName / getIntermediateResultColumnType
     std::string arg = "*";
     if (r->agg_col[a] >= 0) {
-      DictView v;
-      if (table_dict_view(t, r->agg_col[a], &v)) return PGPU_ERR_INVALID_ARGUMENT;
-      arg = v.name;
+      // (an expression's function form for a virtual column: sum(mult(price,qty)), as ExpressionContext.toString)
+      if (table_column_name(t, r->agg_col[a], &arg)) return PGPU_ERR_INVALID_ARGUMENT;
     }
     names.push_back(std::string(fn_name(r->agg_fn[a])) + "(" + arg + ")");
     types.push_back(r->agg_fn[a] == PGPU_AGG_COUNT ? "LONG" : r->agg_fn[a] == PGPU_AGG_AVG ? "OBJECT" : "DOUBLE");

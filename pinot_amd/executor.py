@@ -277,6 +277,42 @@ class GpuTable:
     def __exit__(self, *a):
         self.close()
 
+    # ------------------------------------------------------------------ expressions inside aggregations
+    def add_expression(self, ops, name=None):
+        """pgpu_table_add_expression: registers a postfix program -- (op, column index, literal) triples, _lib.EXPR_* --
+        as a virtual column and returns its index (at or above the real columns).  An identical program registered
+        before returns the same index."""
+        arr = (L.ExprOpC * max(len(ops), 1))()
+        for i, (op, col, lit) in enumerate(ops):
+            arr[i].op, arr[i].column, arr[i].literal = int(op), int(col), float(lit)
+        out = ctypes.c_int32()
+        L.check(self.lib.pgpu_table_add_expression(self.handle, arr, len(ops), name.encode() if name else None,
+                                                   ctypes.byref(out)))
+        return out.value
+
+    def expression(self, column):
+        """pgpu_table_expression: a virtual column's (ops, name), ops as (op, column index, literal) triples."""
+        n = ctypes.c_int32()
+        arr = (L.ExprOpC * L.EXPR_MAX_OPS)()
+        name = ctypes.create_string_buffer(1024)
+        L.check(self.lib.pgpu_table_expression(self.handle, column, arr, L.EXPR_MAX_OPS, ctypes.byref(n), name, len(name)))
+        return [(arr[i].op, arr[i].column, arr[i].literal) for i in range(n.value)], name.value.decode()
+
+    def query_c(self, query):
+        """query.to_c over this table's columns, the query's expressions (SUM(price * qty)) registered as virtual
+        columns on first use: from then on the expression's function-form name is a column of the table's index."""
+        exprs = query.expressions
+        for fn, col in query.aggregations:
+            if col in exprs and col not in self.index and fn != "COUNT":
+                from .query import expr_program
+                ops = []
+                for op, c, lit in expr_program(exprs[col]):
+                    if c is not None and c not in self.index:
+                        raise KeyError("unknown column %r" % c)
+                    ops.append((op, self.index[c] if c is not None else 0, lit))
+                self.index[col] = self.add_expression(ops, col)
+        return query.to_c(self.index)
+
     # ------------------------------------------------------------------ segments
     def pin_segment(self, seg):
         """Pins SegmentBuffers (ImmutableSegmentLoader.load time); returns the segment handle."""
@@ -474,7 +510,7 @@ class GpuTable:
         return out[:len(docs)]
 
     def filter_bitmap(self, handle, query, num_docs):
-        q, keep = query.to_c(self.index)
+        q, keep = self.query_c(query)
         out = np.zeros(max((num_docs + 63) // 64, 1), dtype=np.uint64)
         L.check(self.lib.pgpu_filter_bitmap(self.handle, handle, ctypes.byref(q), L.ptr(out, ctypes.c_uint64)))
         return out
@@ -496,7 +532,7 @@ class GpuTable:
             from .query import parse_query
             query = parse_query(query)
         hs = np.ascontiguousarray(list(handles), dtype=np.int64)
-        q, keep = query.to_c(self.index)
+        q, keep = self.query_c(query)
         na = len(query.aggregations)
         out = (L.FpSumRangeC * max(na, 1))()
         L.check(self.lib.pgpu_query_fp_sum_ranges(self.handle, L.ptr(hs, ctypes.c_int64), len(hs), ctypes.byref(q), out))
@@ -538,7 +574,7 @@ class Plan:
         self.lib = table.lib
         hs = handles if isinstance(handles, np.ndarray) and handles.dtype == np.int64 else \
             np.ascontiguousarray(list(handles), dtype=np.int64)
-        q, keep = query.to_c(table.index)
+        q, keep = table.query_c(query)
         h = ctypes.c_void_p()
         if fp_sum_ranges is not None:
             assert execute is None, "an agreed plan is created, then executed"
@@ -646,7 +682,8 @@ class Plan:
         `tile_chunks`, `slot_weights` (a tuple, empty = equal shares), `longest_run`, `launch_grid`, `launch_tiles`,
         `alone` and `weights_declined` (refused for the LDS the plan reserved); `variant`, the scan kernel's instance
         (0 sparse, 1 dense, 2 dense without gathers, 3-5 sparse specialisations, 6 / 7 sparse / dense with fixed-point
-        sums, 8 / 9 sparse / dense with DISTINCTCOUNT, 10 / 11 sparse / dense with PERCENTILE)."""
+        sums, 8 / 9 sparse / dense with DISTINCTCOUNT, 10 / 11 sparse / dense with PERCENTILE, 12 / 13 sparse / dense with expression
+        aggregations)."""
         out = (ctypes.c_int64 * 16)()
         L.check(self.lib.pgpu_plan_scan_geometry(self.handle, out))
         return {"grid": out[0], "lds_bytes": out[1], "leap_tiles": out[2], "tiles": out[3],

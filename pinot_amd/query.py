@@ -82,6 +82,137 @@ def function_name(fn, percentile=None):
     return percentile_name(percentile_code(suffix if percentile is None else percentile))
 
 
+# ================================================================================ expressions inside aggregations
+# SUM(price * qty): the reference's arithmetic transform functions (AdditionTransformFunction & co).  A tree is
+# ("col", name), ("lit", text) or (fn, [args]) with fn in add / sub / mult / div; infix operators are binary nodes.
+_EXPR_FUNCTIONS = {"ADD": "add", "PLUS": "add", "SUB": "sub", "MINUS": "sub", "MULT": "mult", "TIMES": "mult",
+                   "DIV": "div", "DIVIDE": "div"}
+_EXPR_OPCODE = {"add": L.EXPR_ADD, "sub": L.EXPR_SUB, "mult": L.EXPR_MULT, "div": L.EXPR_DIV}
+_EXPR_CHARS = re.compile(r"[()+\-*/]")
+
+
+def is_expression(column):
+    """An aggregation's argument that is no plain column name (and not COUNT's *)."""
+    return isinstance(column, str) and column != "*" and _EXPR_CHARS.search(column) is not None
+
+
+def expr_node(fn, args):
+    """The node of function `fn` (a name or SQL alias, any case) over `args`, its argument count checked."""
+    name = _EXPR_FUNCTIONS.get(fn.upper())
+    if name is None:
+        raise ValueError("unknown function %s in an aggregation's argument (ADD, SUB, MULT, DIV and their aliases "
+                         "PLUS, MINUS, TIMES, DIVIDE are supported)" % fn)
+    if name in ("sub", "div") and len(args) != 2:
+        raise ValueError("%s takes exactly 2 arguments, got %d" % (name.upper(), len(args)))
+    if len(args) < 2:
+        raise ValueError("%s takes at least 2 arguments, got %d" % (name.upper(), len(args)))
+    return (name, list(args))
+
+
+def expr_literal(text):
+    """A numeric literal node: Double.parseDouble of its text, named by the double's shortest form."""
+    try:
+        return ("lit", repr(float(text)))
+    except ValueError:
+        raise ValueError("%r is not a numeric literal" % (text,))
+
+
+def expr_columns(tree):
+    """The distinct columns of a tree, in first-use order."""
+    out = []
+
+    def walk(t):
+        if t[0] == "col":
+            if t[1] not in out:
+                out.append(t[1])
+        elif t[0] != "lit":
+            for a in t[1]:
+                walk(a)
+    walk(tree)
+    return out
+
+
+def expr_name(tree):
+    """The expression in the reference's function form: mult(price,qty), add(div(a,b),2.5)."""
+    if tree[0] in ("col", "lit"):
+        return tree[1]
+    return "%s(%s)" % (tree[0], ",".join(expr_name(a) for a in tree[1]))
+
+
+def expr_program(tree):
+    """The postfix program of a tree as (op, column name or None, literal) triples, all ops binary: ADD(x1..xn) is
+    ((0.0 + the literal arguments in order) + v1) + v2 ... over the non-literal arguments in order, MULT likewise from
+    1.0 (AdditionTransformFunction.java:44-82, MultiplicationTransformFunction.java:34-82); SUB and DIV are a op b."""
+    ops = []
+
+    def emit(t):
+        if t[0] == "col":
+            ops.append((L.EXPR_COLUMN, t[1], 0.0))
+        elif t[0] == "lit":
+            ops.append((L.EXPR_LITERAL, None, float(t[1])))
+        elif t[0] in ("sub", "div"):
+            emit(t[1][0])
+            emit(t[1][1])
+            ops.append((_EXPR_OPCODE[t[0]], None, 0.0))
+        else:
+            acc = 0.0 if t[0] == "add" else 1.0
+            for a in t[1]:
+                if a[0] == "lit":
+                    acc = acc + float(a[1]) if t[0] == "add" else acc * float(a[1])
+            ops.append((L.EXPR_LITERAL, None, acc))
+            for a in t[1]:
+                if a[0] != "lit":
+                    emit(a)
+                    ops.append((_EXPR_OPCODE[t[0]], None, 0.0))
+    emit(tree)
+    return ops
+
+
+def check_expr_limits(tree):
+    """ValueError where the tree's program is beyond what a virtual column holds (pgpu_table_add_expression: 16 ops, an
+    evaluation stack of 4, 4 distinct columns).  Every ADD / MULT node spends one op and one stack level on its folded
+    literal, so a long infix chain -- a + b + c + d + e nests four binary nodes -- is deeper than it looks: the n-ary
+    form ADD(a, b, c, d, e) is one node."""
+    ops = expr_program(tree)
+    depth = most = 0
+    for op, _, _ in ops:
+        depth += 1 if op in (L.EXPR_COLUMN, L.EXPR_LITERAL) else -1
+        most = max(most, depth)
+    name = expr_name(tree)
+    hint = "; the n-ary forms ADD(x1, .., xn) / MULT(x1, .., xn) take one op per argument more and no nesting"
+    if len(ops) > L.EXPR_MAX_OPS:
+        raise ValueError("expression %s compiles to %d ops, more than %d%s" % (name, len(ops), L.EXPR_MAX_OPS, hint))
+    if most > L.EXPR_MAX_DEPTH:
+        raise ValueError("expression %s needs an evaluation stack of %d, more than %d%s" % (name, most, L.EXPR_MAX_DEPTH, hint))
+    if len(expr_columns(tree)) > L.EXPR_MAX_COLUMNS:
+        raise ValueError("expression %s names %d columns, more than %d" % (name, len(expr_columns(tree)), L.EXPR_MAX_COLUMNS))
+
+
+def _check_expr(tree):
+    """Every function node needs a column somewhere below it: a literal-only (sub)expression is not evaluated here."""
+    if tree[0] in ("col", "lit"):
+        return
+    if not expr_columns(tree):
+        raise ValueError("literal-only expression %s: an expression needs a column operand" % expr_name(tree))
+    for a in tree[1]:
+        _check_expr(a)
+
+
+def parse_expression(text):
+    """The canonical tree of an aggregation's argument: a column, or an arithmetic expression in function form
+    (ADD / SUB / MULT / DIV, aliases PLUS / MINUS / TIMES / DIVIDE), infix (+ - * / with the usual precedence and
+    parentheses), nested, with numeric literals.  ValueError for anything else."""
+    p = _Parser(text)
+    tree = p.arith()
+    if p.peek()[0] is not None:
+        raise ValueError("cannot parse expression %r near %r" % (text, p.peek()[1]))
+    if tree[0] == "lit":
+        raise ValueError("literal-only expression %s: an expression needs a column operand" % text)
+    _check_expr(tree)
+    check_expr_limits(tree)
+    return tree
+
+
 class Predicate:
     def __init__(self, ptype, column, values, lower_inclusive=True, upper_inclusive=True):
         self.type = ptype
@@ -156,7 +287,8 @@ class QueryContext:
     def __init__(self, group_by, aggregations, filter=None, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT,
                  use_star_tree=True, select=None, order_by=None, limit=DEFAULT_LIMIT,
                  min_server_group_trim_size=DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE,
-                 group_trim_threshold=DEFAULT_GROUP_TRIM_THRESHOLD, sql_group_by=False, exact_fp_sum=False):
+                 group_trim_threshold=DEFAULT_GROUP_TRIM_THRESHOLD, sql_group_by=False, exact_fp_sum=False,
+                 expressions=None):
         self.filter = filter
         # bit-reproducible FLOAT / DOUBLE SUM / AVG (PGPU_OPT_EXACT_FP_SUM): fixed-point digits summed as integers,
         # rounded once -- the same bits in every run, segment layout and accumulator mode (GpuPlan.fp_sum_format)
@@ -165,8 +297,26 @@ class QueryContext:
         self.sql_group_by = sql_group_by
         self.use_star_tree = use_star_tree  # debug option useStarTree (StarTreeUtils.java:51-59)
         self.group_by = list(group_by)
-        # (fn, column) or, for the exact percentile, ("PERCENTILE", column, percentile); kept as (canonical name, column)
-        self.aggregations = [(function_name(a[0], *a[2:]), a[1]) for a in aggregations]
+        # expressions: {function-form name: canonical tree} of the aggregation arguments that are expressions, as the
+        # parser found them -- every other name is a column, whatever characters it has (a quoted identifier).  None
+        # (a query built by hand): an argument with one of ( ) + - * / is read as an expression's text.
+        sniff = expressions is None
+        for c in self.group_by:
+            if sniff and is_expression(c):
+                raise ValueError("expression %r in GROUP BY: expressions are supported inside aggregations only" % (c,))
+        # (fn, column) or, for the exact percentile, ("PERCENTILE", column, percentile); kept as (canonical name, column).
+        # An argument that is an arithmetic expression (SUM(price * qty)) is kept as its canonical function-form name
+        # (mult(price,qty)); expressions: name -> canonical tree.  Equal expressions share one name, so one virtual column.
+        self.expressions = dict(expressions or {})
+        self.aggregations = []
+        for a in aggregations:
+            col = a[1]
+            if sniff and is_expression(col):
+                tree = parse_expression(col)
+                col = expr_name(tree)
+                if tree[0] != "col":
+                    self.expressions[col] = tree
+            self.aggregations.append((function_name(a[0], *a[2:]), col))
         self.num_groups_limit = num_groups_limit
         # SQL-mode parts (QueryContext.getSelectExpressions / getOrderByExpressions / getLimit): the SELECT list as
         # ('col', name) / ('agg', FN, col), ORDER BY as [(expr, ascending)], LIMIT; the combine's trim options
@@ -215,7 +365,8 @@ class QueryContext:
             self.filter.postfix(preds, [])
             cols += [p.column for p in preds]
         cols += self.group_by
-        cols += [c for _, c in self.aggregations if c != "*"]
+        for _, c in self.aggregations:
+            cols += expr_columns(self.expressions[c]) if c in self.expressions else [c] * (c != "*")
         out = []
         for c in cols:
             if c not in out:
@@ -291,7 +442,14 @@ class QueryContext:
                 raise L.UnsupportedQueryError(L.PGPU_ERR_UNSUPPORTED, "aggregation %s" % fn)
             else:
                 ac[i].fn = AGG_FUNCTIONS[fn]
-            ac[i].column = -1 if col == "*" else column_index[col]
+            if col in self.expressions and ac[i].fn == L.AGG_COUNT:
+                ac[i].column = -1  # COUNT(expr) is COUNT
+            elif col == "*":
+                ac[i].column = -1
+            elif col not in column_index:  # (an expression: GpuTable registers it, then the name is a column)
+                raise KeyError("unknown column %r" % col)
+            else:
+                ac[i].column = column_index[col]
         q = L.QueryC()
         q.num_predicates = len(preds)
         q.num_filter_ops = len(ops)
@@ -309,8 +467,9 @@ class QueryContext:
 
 
 # ================================================================================ SQL / PQL subset parser
-_TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][+-]?\d+)?)|(?P<str>'(?:[^']|'')*')|"
-                    r"(?P<id>[A-Za-z_][A-Za-z0-9_.$]*|\"[^\"]+\")|(?P<op><=|>=|<>|!=|=|<|>|\(|\)|,|\*))")
+# (a number's sign is a token of its own, so that a-1 is a subtraction: _Parser.literal / arith put it back)
+_TOKEN = re.compile(r"\s*(?:(?P<num>\d+(?:\.\d+)?(?:[eE][+-]?\d+)?)|(?P<str>'(?:[^']|'')*')|"
+                    r"(?P<id>[A-Za-z_][A-Za-z0-9_.$]*|\"[^\"]+\")|(?P<op><=|>=|<>|!=|=|<|>|\(|\)|,|\*|\+|-|/))")
 
 
 def _tokenize(s):
@@ -338,6 +497,7 @@ class _Parser:
     def __init__(self, sql):
         self.t = _tokenize(sql)
         self.i = 0
+        self.exprs = {}  # function-form name -> tree of the aggregation arguments that are expressions
 
     def peek(self, k=0):
         return self.t[self.i + k] if self.i + k < len(self.t) else (None, None)
@@ -361,12 +521,15 @@ class _Parser:
             col = "*" if self.peek() == ("op", "*") else None
             if col:
                 self.take("op", "*")
-            else:
-                col = self.take("id")
+            else:  # a column, or an arithmetic expression kept as its canonical function-form name
+                tree = self.arith_checked()
+                col = expr_name(tree)
+                if tree[0] != "col":
+                    self.exprs[col] = tree
             arg = None
             if self.peek() == ("op", ","):  # PERCENTILE(x, 95) / PERCENTILE(x, '95')
                 self.take("op", ",")
-                arg = self.take("lit")
+                arg = self.literal()
             self.take("op", ")")
             return ("agg", function_name(fn, arg), col)
         return ("col", self.take("id"))
@@ -382,10 +545,62 @@ class _Parser:
 
     def literal(self):
         tok = self.peek()
+        if tok == ("op", "-") and self.peek(1)[0] == "lit":  # a negative number
+            self.i += 2
+            return "-" + self.peek(-1)[1]
         if tok[0] not in ("lit", "id"):
             raise ValueError("literal expected, got %r" % (tok,))
         self.i += 1
         return tok[1]
+
+    # ---- an aggregation's argument: arith := term (+|- term)*, term := factor (*|/ factor)*,
+    # factor := [-] number | FN ( arith , ... ) | column | ( arith )
+    def arith_checked(self):
+        tree = self.arith()
+        if tree[0] == "lit":
+            raise ValueError("literal-only expression %s: an expression needs a column operand" % tree[1])
+        _check_expr(tree)
+        check_expr_limits(tree)
+        return tree
+
+    def arith(self):
+        left = self.term()
+        while self.peek() in (("op", "+"), ("op", "-")):
+            op = self.take("op")
+            left = expr_node("ADD" if op == "+" else "SUB", [left, self.term()])
+        return left
+
+    def term(self):
+        left = self.factor()
+        while self.peek() in (("op", "*"), ("op", "/")):
+            op = self.take("op")
+            left = expr_node("MULT" if op == "*" else "DIV", [left, self.factor()])
+        return left
+
+    def factor(self):
+        tok = self.peek()
+        if tok == ("op", "("):
+            self.take("op", "(")
+            e = self.arith()
+            self.take("op", ")")
+            return e
+        if tok == ("op", "-"):  # unary minus on a literal
+            self.take("op", "-")
+            if self.peek()[0] != "lit":
+                raise ValueError("unary minus is supported on a numeric literal only, got %r" % (self.peek(),))
+            return expr_literal("-" + self.take("lit"))
+        if tok[0] == "lit":
+            return expr_literal(self.take("lit"))
+        if tok[0] == "id" and self.peek(1) == ("op", "("):
+            fn = self.take("id")
+            self.take("op", "(")
+            args = [self.arith()]
+            while self.peek() == ("op", ","):
+                self.take("op", ",")
+                args.append(self.arith())
+            self.take("op", ")")
+            return expr_node(fn, args)
+        return ("col", self.take("id"))
 
     def expr_or(self):
         kids = [self.expr_and()]
@@ -411,6 +626,8 @@ class _Parser:
             self.take("op", ")")
             return e
         col = self.take("id")
+        if self.peek() in (("op", "("), ("op", "+"), ("op", "-"), ("op", "*"), ("op", "/")):
+            raise ValueError("expression in WHERE near %r: expressions are supported inside aggregations only" % col)
         if self.kw("BETWEEN"):
             self.take("id")
             lo = self.literal()
@@ -464,10 +681,15 @@ def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=Fal
     if p.kw("GROUP"):
         p.take("id")
         p.take("id", "BY")
-        group_by.append(p.take("id"))
+        def group_by_column():
+            col = p.take("id")
+            if p.peek() in (("op", "("), ("op", "+"), ("op", "-"), ("op", "*"), ("op", "/")):
+                raise ValueError("expression in GROUP BY near %r: expressions are supported inside aggregations only" % col)
+            return col
+        group_by.append(group_by_column())
         while p.peek() == ("op", ","):
             p.take("op", ",")
-            group_by.append(p.take("id"))
+            group_by.append(group_by_column())
     order_by, limit = [], DEFAULT_LIMIT
     if p.kw("ORDER"):
         p.take("id")
@@ -483,11 +705,11 @@ def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=Fal
             p.take("op", ",")
     if p.kw("TOP", "LIMIT"):
         p.take("id")
-        limit = int(p.take("lit"))
+        limit = int(p.literal())
     select = [("col", it[1]) if it[0] == "col" else ("agg", it[1], it[2]) for it in items]
     aggs = []
     for e in [x for x in select if x[0] == "agg"] + [e for e, _ in order_by if e[0] == "agg"]:
         if (e[1], e[2]) not in aggs:
             aggs.append((e[1], e[2]))
     return QueryContext(group_by, aggs, flt, num_groups_limit, select=select, order_by=order_by, limit=limit,
-                        exact_fp_sum=exact_fp_sum)
+                        exact_fp_sum=exact_fp_sum, expressions=p.exprs)

@@ -35,24 +35,26 @@ namespace {
 
 // The scan kernel's dispatch (scan_entry, kernels.hip) over every (mode, variant) cell and one variant past each end:
 // an entry exactly where kScanInstances has one -- all but DC x HASH and HIST x HASH.  Counted per block of rows: the
-// cells of rows [0, kFirstHistVariant) in `resolved` (28), those of the histogram rows in *hist (4).  Resolves only;
-// nothing is launched.
+// cells of rows [0, kFirstHistVariant) in `resolved` (28), those of the histogram rows in *hist (4), those of the
+// expression rows (sparse: every mode; dense: LDS and global) in *expr (5).  Resolves only; nothing is launched.
 constexpr int kFirstHistVariant = pgpu::kScanHistSparse;
-int scan_cells_resolved(int* hist) {
+constexpr int kFirstExprVariant = pgpu::kScanExprSparse;
+int scan_cells_resolved(int* hist, int* expr) {
   std::vector<const void*> seen;
   int resolved = 0;
   *hist = 0;
+  *expr = 0;
   for (int mode = pgpu::MODE_LDS; mode <= pgpu::MODE_HASH; ++mode)
     for (int v = -1; v <= pgpu::kScanVariants; ++v) {
       const bool want = v >= 0 && v < pgpu::kScanVariants &&
-                        !(mode == pgpu::MODE_HASH && pgpu::kScanInstances[v].family >= pgpu::SCAN_DC);
+                        (pgpu::kScanInstances[v].modes >> mode & 1u);
       const pgpu::KernelEntry e = pgpu::scan_entry(mode, v);
       if ((e.fn != nullptr) != want || (want && e.block != pgpu::kBlock)) {
         fprintf(stderr, "scan_entry(mode %d, variant %d): %s\n", mode, v, want ? "no entry" : "an entry");
         exit(5);
       }
       if (want) seen.push_back(e.fn);
-      (v >= kFirstHistVariant ? *hist : resolved) += want;
+      (v >= kFirstExprVariant ? *expr : v >= kFirstHistVariant ? *hist : resolved) += want;
     }
   std::sort(seen.begin(), seen.end());
   if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) {
@@ -440,12 +442,13 @@ int main(int argc, char** argv) {
   const long inv = timed("inv", [&] { return fuzz_inv(iters, r); });
   const long stb = timed("stb", [&] { return fuzz_startree_build(iters / 4 + 1, r); });
   const long flt = timed("flt", [&] { return fuzz_filter(iters, r); });
-  int hist_cells = 0;
-  const int cells = scan_cells_resolved(&hist_cells);
+  int hist_cells = 0, expr_cells = 0;
+  const int cells = scan_cells_resolved(&hist_cells, &expr_cells);
   printf("scan instances resolved: %d of 3 x %d cells\n", cells, kFirstHistVariant);
-  printf("histogram scan instances resolved: %d of 3 x %d cells\n", hist_cells, pgpu::kScanVariants - kFirstHistVariant);
+  printf("histogram scan instances resolved: %d of 3 x %d cells\n", hist_cells, kFirstExprVariant - kFirstHistVariant);
+  printf("expression scan instances resolved: %d of 3 x %d cells\n", expr_cells, pgpu::kScanVariants - kFirstExprVariant);
   printf("host_fuzz calls: raw %ld dt %ld st %ld invf %ld inv %ld stb %ld flt %ld\n", raw, dt, st, invf, inv, stb,
          flt);
-  if (cells != 28 || hist_cells != 4) return 5;
+  if (cells != 28 || hist_cells != 4 || expr_cells != 5) return 5;
   return (raw > 0 && dt > 0 && st > 0 && invf > 0) ? 0 : 3;  // 3: a seed family is missing from the corpus
 }
