@@ -183,12 +183,24 @@ int pgpu_unpack_fixed_bit_device(const void* d_fwd, int64_t fwd_len, int32_t bit
 
 /* Predicate types (segspi Predicate.Type subset on dictionary columns). RANGE literal pair uses "*" for
  * unbounded (RangePredicate.UNBOUNDED). Literals are strings, converted per column type exactly as
- * PredicateUtils.getStoredValue + Dictionary.insertionIndexOf do. */
+ * PredicateUtils.getStoredValue + Dictionary.insertionIndexOf do.
+ * A predicate on an arithmetic expression -- WHERE price * qty > 1000, the reference's ExpressionFilterOperator
+ * (FilterPlanNode.java:179-186) -- names the expression's virtual column (pgpu_table_add_expression) in `column`.  The
+ * expression's value is a DOUBLE without a dictionary, so its evaluator is the raw DOUBLE one: the literals are read by
+ * Double.parseDouble; RANGE and EQ / NOT_EQ compare as Java doubles (0.0 equals -0.0, a NaN value matches no RANGE and
+ * no EQ, hence every NOT_EQ), IN / NOT_IN by Double.doubleToLongBits (0.0 and -0.0 differ).  One kernel in front of the
+ * scan evaluates the leaf for every doc of every planned segment into a per-query docId bitmap, which the scan reads
+ * as it reads an inverted-index leaf's; the leaf is never folded to match-all or empty, a filter with such a leaf never
+ * takes a star-tree, and the leaf runs wherever a raw-value leaf does (every accumulator mode, the partitioned
+ * pipelines, pgpu_filter_bitmap; one launch, never streamed).  Its operands are filter columns: they do not count in
+ * numEntriesScannedPostFilter.  numEntriesScannedInFilter counts it as ExpressionScanDocIdIterator does
+ * (PGPU_LEAF_EXPRESSION below).  Declined as for expression aggregations (STRING, raw or virtual operands:
+ * PGPU_ERR_UNSUPPORTED, the message names "expression"). */
 enum pgpu_predicate_type { PGPU_PRED_EQ = 0, PGPU_PRED_NOT_EQ = 1, PGPU_PRED_IN = 2, PGPU_PRED_NOT_IN = 3,
                            PGPU_PRED_RANGE = 4 };
 typedef struct {
   int32_t type;
-  int32_t column;
+  int32_t column;             /* a table column, or a virtual column (an expression: see above) */
   int32_t num_values;         /* EQ/NOT_EQ 1, IN/NOT_IN k, RANGE 2 (lower, upper) */
   int32_t lower_inclusive;
   const char* const* values;
@@ -268,7 +280,7 @@ typedef struct {
   int32_t column;   /* -1 for COUNT(*); a virtual column (pgpu_table_add_expression) for an expression */
 } pgpu_agg;
 
-/* Arithmetic expressions inside aggregations -- SUM(price * qty), AVG(revenue - cost), MAX(a / b): the reference's
+/* Arithmetic expressions inside aggregations (and in predicates: pgpu_predicate) -- SUM(price * qty), AVG(revenue - cost), MAX(a / b): the reference's
  * TransformOperator between projection and aggregation, for its four arithmetic transform functions
  * (core/operator/transform/function/{Addition,Subtraction,Multiplication,Division}TransformFunction.java).  An
  * expression is a virtual column of the table: pgpu_table_add_expression registers its postfix program and returns a
@@ -300,8 +312,9 @@ typedef struct {
  * query with a DISTINCTCOUNT or PERCENTILE (those plans take another scan instance); the combination with
  * PGPU_OPT_EXACT_FP_SUM (pgpu_query_fp_sum_ranges and pgpu_plan_create_agreed included); more than 8 distinct
  * expressions in one query; an external d_table (execute, finalize, pgpu_plan_combine); numGroupsLimit plans that
- * split per segment; a virtual column in GROUP BY or in a predicate (PGPU_ERR_INVALID_ARGUMENT: bad column).  Such
- * plans never take the radix- or hash-partitioned pipelines: they are planned as with
+ * split per segment; a virtual column in GROUP BY (PGPU_ERR_INVALID_ARGUMENT: bad column).  None of this list but the
+ * operand rules applies to a virtual column named by a predicate, which changes nothing after the filter.  Plans with
+ * an expression aggregation never take the radix- or hash-partitioned pipelines: they are planned as with
  * pgpu_config.partitioned_group_by = 0, hash_partitions = 0 and stream_chunks = 1. */
 enum pgpu_expr_opcode { PGPU_EXPR_COLUMN = 0, PGPU_EXPR_LITERAL = 1, PGPU_EXPR_ADD = 2, PGPU_EXPR_SUB = 3,
                         PGPU_EXPR_MULT = 4, PGPU_EXPR_DIV = 5 };
@@ -627,9 +640,15 @@ int pgpu_plan_scanned_segments(pgpu_plan plan, uint8_t* out);
  * OrDocIdIterator) are replayed over the sets.  The plans compute the same statistic on the device; this entry is
  * the host form (a caller holding the doc sets, tests).  PGPU_LEAF_RANGE_INDEX (RangeIndexBasedFilterOperator) is an
  * index-based leaf ranked after the bitmap leaves; the entries of its own partial-match scan are not included (the
- * caller adds them: pgpu_range_index_partial_entries). */
+ * caller adds them: pgpu_range_index_partial_entries).  PGPU_LEAF_EXPRESSION (ExpressionFilterOperator, a predicate
+ * on an expression) is a scan-based leaf ranked after every other AND child (priority 10, stable;
+ * FilterOperatorUtils.java:171-172) whose iterator is ExpressionScanDocIdIterator: applyAnd counts the docs it is
+ * handed; next() evaluates blocks of up to 10000 docs (DocIdSetPlanNode.MAX_DOC_PER_CALL), counting every doc of a
+ * block, until one holds a match; advance(target) looks inside the current block, uncounted, when the target lies in
+ * it and otherwise starts the next block at the target.  So a lone leaf or an OR child counts numDocs, and in a
+ * leap-frog AND the blocks start wherever the other children's docs land. */
 enum pgpu_leaf_type { PGPU_LEAF_EMPTY = 0, PGPU_LEAF_MATCH_ALL = 1, PGPU_LEAF_SCAN = 2, PGPU_LEAF_SORTED = 3,
-                      PGPU_LEAF_BITMAP = 4, PGPU_LEAF_RANGE_INDEX = 5 };
+                      PGPU_LEAF_BITMAP = 4, PGPU_LEAF_RANGE_INDEX = 5, PGPU_LEAF_EXPRESSION = 6 };
 int pgpu_filter_entries_scanned(const pgpu_filter_op* filter, int32_t num_filter_ops, const int32_t* leaf_types,
                                 const uint32_t* const* leaf_masks, int32_t num_leaves, int32_t num_docs,
                                 int64_t* out);

@@ -70,6 +70,7 @@ OPT_TIMING = 8
 OPT_EXACT_FP_SUM = 16
 FP_SUM_MODE_NAMES = ("none", "exact", "quantised")  # pgpu_plan_fp_sum_format mode
 LEAF_EMPTY, LEAF_MATCH_ALL, LEAF_SCAN, LEAF_SORTED, LEAF_BITMAP, LEAF_RANGE_INDEX = 0, 1, 2, 3, 4, 5
+LEAF_EXPRESSION = 6  # ExpressionFilterOperator: a predicate on an arithmetic expression (a virtual column)
 
 
 ORDER_GROUP_BY, ORDER_AGGREGATION = 0, 1

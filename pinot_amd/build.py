@@ -25,7 +25,7 @@ SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTI
      for m in range(modes)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "scan_direct_body.inc", "part_aggregate_body.inc",
            "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
@@ -210,6 +210,31 @@ def build_expr_check(force=False):
     """The expression programs of aggregations (expr_eval.h): validation, evaluation and keys on the host, compiled
     with floating-point contraction off -- no fused multiply-add, as on the device."""
     return _build_header_check("expr_check", "expr_check.cpp", "expr_eval.h", force, extra=("-ffp-contract=off",))
+
+
+def build_expr_filter_check(force=False):
+    """build/expr_filter_check: tools/expr_filter_check.cpp with csrc/filter_stats.cpp -- the host code of the
+    expression filter leaves (expr_leaf.h's task builder and job list, the ExpressionScanDocIdIterator replay) --
+    under AddressSanitizer + UndefinedBehaviorSanitizer.  A stand-alone program: no device code runs, no library is
+    linked."""
+    out = os.path.join(ROOT, "build", "expr_filter_check")
+    srcs = [os.path.join(ROOT, "tools", "expr_filter_check.cpp"), os.path.join(CSRC, "filter_stats.cpp")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("expr_leaf.h", "expr_eval.h", "internal.h", "filter_stats.h",
+                                                    "host_common.h", "tile_split.h")]
+    if not force and os.path.exists(out) and all(os.path.getmtime(f) <= os.path.getmtime(out) for f in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    hipcc = _hipcc()
+    objs = [out + "_%d.o" % i for i in range(len(srcs))]
+    cmds = [[hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"),
+             "-ffp-contract=off"] + SAN_FLAGS + ["-c", s, "-o", o] for s, o in zip(srcs, objs)]
+    cmds.append([hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined"] + objs + ["-o", out + ".tmp"])
+    for cmd in cmds:
+        res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if res.returncode != 0:
+            raise RuntimeError("hipcc (expr_filter_check) failed:\n%s" % res.stdout[-6000:])
+    os.replace(out + ".tmp", out)
+    return out
 
 
 if __name__ == "__main__":

@@ -234,7 +234,7 @@ int pgpu_filter_bitmap(pgpu_table t, int64_t h, const pgpu_query* q, uint64_t* o
   fq.num_aggs = 0;
   fq.aggs = nullptr;
   auto P = std::make_unique<pgpu_plan_s>();
-  P->no_inverted = true;  // the standalone filter kernel reads scan / sorted / raw-value leaves only
+  P->no_inverted = true;  // the standalone filter kernel reads scan / sorted / raw-value / expression leaves only
   TRY(plan_create_impl(t, &h, 1, &fq, P.get()));
   Segment* s = P->segs[0];
   const int64_t ngroups = ((int64_t)s->num_docs + 31) / 32;
@@ -252,13 +252,15 @@ int pgpu_filter_bitmap(pgpu_table t, int64_t h, const pgpu_query* q, uint64_t* o
       const uint32_t* p = sc->sets.as<uint32_t>() + f.second;
       memcpy(P->segrec.data() + f.first, &p, sizeof p);
     }
-    if (!P->raw_tasks.empty()) {  // raw-value leaves: their docbits regions first (inverted leaves are off here)
+    // raw-value and expression leaves: their docbits regions first (inverted leaves are off here)
+    if (!P->raw_tasks.empty() || !P->expr_tasks.empty()) {
       if ((rc = sc->docbits.ensure((size_t)P->docbit_words * 4))) break;
       for (auto& f : P->bit_fix) {
         const uint32_t* p = sc->docbits.as<uint32_t>() + f.second;
         memcpy(P->segrec.data() + f.first, &p, sizeof p);
       }
       if ((rc = launch_raw_leaves(P.get(), sc, t->stream))) break;
+      if ((rc = launch_expr_leaves(P.get(), sc, t->stream))) break;
     }
     if ((rc = sc->bitmap.ensure((size_t)nwords * 8))) break;
     hipMemsetAsync(sc->bitmap.p, 0, (size_t)nwords * 8, t->stream);

@@ -14,12 +14,14 @@ namespace pgpu {
 namespace {
 
 bool is_primitive(int type) {
-  return type == SN_SCAN || type == SN_SORTED || type == SN_BITMAP || type == SN_RANGEIDX || type == SN_NOT;
+  return type == SN_SCAN || type == SN_SORTED || type == SN_BITMAP || type == SN_RANGEIDX || type == SN_NOT ||
+         type == SN_EXPR;
 }
 // Index-based leaves: their docIdSet is a sorted range or a bitmap, no iterator scans for them.
 bool is_index(int type) { return type == SN_SORTED || type == SN_BITMAP || type == SN_RANGEIDX; }
 
-// reorderAndFilterChildOperators priorities (FilterOperatorUtils.java:143-178); NOT ranks with the scans.
+// reorderAndFilterChildOperators priorities (FilterOperatorUtils.java:143-178); NOT ranks with the scans, an
+// ExpressionFilterOperator after everything (:171-172).
 int and_priority(int type) {
   switch (type) {
     case SN_SORTED: return 0;
@@ -27,6 +29,7 @@ int and_priority(int type) {
     case SN_RANGEIDX: return 2;
     case SN_AND: return 3;
     case SN_OR: return 4;
+    case SN_EXPR: return 10;
     default: return 5;
   }
 }
@@ -50,7 +53,7 @@ StatTree build_stat_tree(const std::vector<int32_t>& ops, const std::vector<int3
   for (int32_t e : ops) {
     const int op = e >> 16, arg = e & 0xFFFF;
     if (op == OP_LEAF) {
-      static const int kType[] = {SN_EMPTY, SN_ALL, SN_SCAN, SN_SORTED, SN_BITMAP, SN_RANGEIDX};
+      static const int kType[] = {SN_EMPTY, SN_ALL, SN_SCAN, SN_SORTED, SN_BITMAP, SN_RANGEIDX, SN_EXPR};
       st.push_back(add(kType[leaf[arg]], arg));
     } else if (op == OP_NOT) {
       const int32_t c = st.back();
@@ -98,7 +101,7 @@ StatsPlan classify_stat_tree(const StatTree& t, int64_t num_docs) {
   const StatNode& r = t.nodes[t.root];
   switch (r.type) {
     case SN_EMPTY: case SN_ALL: case SN_SORTED: case SN_BITMAP: case SN_RANGEIDX: return p;  // no scan-based iterator
-    case SN_SCAN: case SN_NOT: p.constant = num_docs; return p;          // iterated over every doc
+    case SN_SCAN: case SN_NOT: case SN_EXPR: p.constant = num_docs; return p;  // iterated over every doc
     default: break;
   }
   for (int32_t c : r.kids)
@@ -106,14 +109,14 @@ StatsPlan classify_stat_tree(const StatTree& t, int64_t num_docs) {
   if (r.type == SN_OR) {
     // OrDocIdIterator.next: every scan child runs through the whole segment (index children merged or not)
     for (int32_t c : r.kids)
-      if (t.nodes[c].type == SN_SCAN || t.nodes[c].type == SN_NOT) p.constant += num_docs;
+      if (t.nodes[c].type == SN_SCAN || t.nodes[c].type == SN_NOT || t.nodes[c].type == SN_EXPR) p.constant += num_docs;
     return p;
   }
-  int nidx = 0, nscan = 0, nnot = 0;
+  int nidx = 0, nscan = 0, nnot = 0, nexpr = 0;  // (nscan: the scan-based children, expression leaves included)
   for (int32_t c : r.kids) {
     const int ty = t.nodes[c].type;
     if (is_index(ty)) { ++nidx; p.index_leaves.push_back(t.nodes[c].leaf); }
-    else if (ty == SN_SCAN) { ++nscan; p.scan_leaves.push_back(t.nodes[c].leaf); }
+    else if (ty == SN_SCAN || ty == SN_EXPR) { ++nscan; nexpr += ty == SN_EXPR; p.scan_leaves.push_back(t.nodes[c].leaf); }
     else ++nnot;
   }
   if (nnot > 0) { p.kind = STATS_GENERIC; return p; }
@@ -121,7 +124,9 @@ StatsPlan classify_stat_tree(const StatTree& t, int64_t num_docs) {
     p.kind = nscan > 0 ? STATS_CHAIN : STATS_CONST;
     return p;
   }
-  p.kind = nscan == 2 ? STATS_LEAP2 : STATS_GENERIC;  // AndDocIdIterator over the children
+  // AndDocIdIterator over the children; the leap-frog count in the kernel is SVScanDocIdIterator's, not the blocks
+  // of an ExpressionScanDocIdIterator
+  p.kind = nscan == 2 && nexpr == 0 ? STATS_LEAP2 : STATS_GENERIC;
   return p;
 }
 
@@ -167,7 +172,8 @@ struct Bits {
   }
 };
 
-enum ItType { IT_EMPTY, IT_ALL, IT_SCAN, IT_IDX, IT_AND, IT_OR };
+enum ItType { IT_EMPTY, IT_ALL, IT_SCAN, IT_IDX, IT_AND, IT_OR, IT_EXPR };
+constexpr int kMaxDocPerCall = 10000;  // DocIdSetPlanNode.MAX_DOC_PER_CALL
 struct It {
   int type = IT_EMPTY;
   int next_doc = 0;
@@ -177,6 +183,10 @@ struct It {
   std::vector<It*> kids;
   std::vector<int> next_ids;   // IT_OR
   int num_not_exhausted = 0, prev_doc = -1;
+  // IT_EXPR (ExpressionScanDocIdIterator): _blockEndDocId, and whether _docIdIterator is set -- it then walks the
+  // matches of bits in [next_doc, block_end)
+  int block_end = 0;
+  bool in_block = false;
 };
 
 int it_next(It* it);
@@ -203,6 +213,21 @@ int it_next(It* it) {
       it->scanned += d - it->next_doc + 1;
       it->next_doc = d + 1;
       return d;
+    }
+    case IT_EXPR: {  // ExpressionScanDocIdIterator.next
+      if (it->in_block) {  // the current block's remaining matches first
+        const int d = it->bits.next(it->next_doc);
+        if (d >= 0 && d < it->block_end) { it->next_doc = d + 1; return d; }
+      }
+      while (it->block_end < it->bits.n) {  // then whole blocks, every doc of each an entry, until one has a match
+        const int start = it->block_end;
+        it->block_end = std::min(start + kMaxDocPerCall, it->bits.n);
+        it->scanned += it->block_end - start;
+        const int d = it->bits.next(start);
+        if (d >= 0 && d < it->block_end) { it->in_block = true; it->next_doc = d + 1; return d; }
+      }
+      it->in_block = false;
+      return kEof;
     }
     case IT_AND: {  // AndDocIdIterator.next
       int max_doc = it->next_doc, max_idx = -1, index = 0;
@@ -244,6 +269,18 @@ int it_next(It* it) {
 int it_advance(It* it, int target) {
   if (it->type != IT_OR) {
     if (it->type == IT_EMPTY) return kEof;
+    if (it->type == IT_EXPR) {  // ExpressionScanDocIdIterator.advance
+      if (target < it->block_end) {  // inside the current block: forward only, nothing evaluated again
+        if (it->in_block) {
+          const int d = it->bits.next(std::max(it->next_doc, target));
+          if (d >= 0 && d < it->block_end) { it->next_doc = d + 1; return d; }
+        }
+      } else {
+        it->block_end = target;  // the next block starts at the target
+      }
+      it->in_block = false;
+      return it_next(it);
+    }
     it->next_doc = target;
     return it_next(it);
   }
@@ -289,7 +326,7 @@ struct Replay {
     switch (s.type) {
       case SN_EMPTY: b.w.assign(nw, 0u); break;
       case SN_ALL: b.w.assign(nw, ~0u); break;
-      case SN_SCAN: case SN_SORTED: case SN_BITMAP: case SN_RANGEIDX: b = leaf_bits(s.leaf); break;
+      case SN_SCAN: case SN_SORTED: case SN_BITMAP: case SN_RANGEIDX: case SN_EXPR: b = leaf_bits(s.leaf); break;
       case SN_NOT: b = match(s.kids[0]); for (auto& x : b.w) x = ~x; break;
       case SN_AND:
         b.w.assign(nw, ~0u);
@@ -326,6 +363,7 @@ struct Replay {
       case SN_EMPTY: return make(IT_EMPTY);
       case SN_ALL: return make(IT_ALL);
       case SN_SCAN: case SN_NOT: { It* it = make(IT_SCAN); it->bits = match(node); return it; }
+      case SN_EXPR: { It* it = make(IT_EXPR); it->bits = match(node); return it; }
       case SN_SORTED: case SN_BITMAP: case SN_RANGEIDX: {
         It* it = make(IT_IDX);
         it->bits = match(node);
@@ -337,7 +375,9 @@ struct Replay {
     std::vector<It*> kids;
     for (int32_t c : s.kids) kids.push_back(build(c));
     int nidx = 0, nscan = 0;
-    for (It* k : kids) { nidx += k->type == IT_IDX; nscan += k->type == IT_SCAN; }
+    // (ScanBasedDocIdIterator: SVScanDocIdIterator and ExpressionScanDocIdIterator alike)
+    auto scan_based = [](const It* k) { return k->type == IT_SCAN || k->type == IT_EXPR; };
+    for (It* k : kids) { nidx += k->type == IT_IDX; nscan += scan_based(k); }
     const int nrem = (int)kids.size() - nidx - nscan;
     if (s.type == SN_AND) {
       if (!((nidx > 0 && nscan > 0) || nidx > 1)) return make_multi(IT_AND, kids);
@@ -346,14 +386,14 @@ struct Replay {
       if (nw && (n & 31)) rangeless->bits.w[nw - 1] &= (1u << (n & 31)) - 1u;
       for (It* k : kids)
         if (k->type == IT_IDX) for (size_t i = 0; i < nw; ++i) rangeless->bits.w[i] &= k->bits.w[i];
-      for (It* k : kids) {  // ScanBasedDocIdIterator.applyAnd (SVScanDocIdIterator.java:75-94)
-        if (k->type != IT_SCAN) continue;
+      for (It* k : kids) {  // ScanBasedDocIdIterator.applyAnd (SVScanDocIdIterator.java:75-94; Expression...:113-123)
+        if (!scan_based(k)) continue;
         k->scanned += rangeless->bits.count();
         for (size_t i = 0; i < nw; ++i) rangeless->bits.w[i] &= k->bits.w[i];
       }
       if (nrem == 0) return rangeless;
       std::vector<It*> ks{rangeless};
-      for (It* k : kids) if (k->type != IT_IDX && k->type != IT_SCAN) ks.push_back(k);
+      for (It* k : kids) if (k->type != IT_IDX && !scan_based(k)) ks.push_back(k);
       return make_multi(IT_AND, ks);
     }
     if (nidx <= 1) return make_multi(IT_OR, kids);
@@ -377,7 +417,7 @@ int64_t simulate_entries_scanned(const StatTree& t, const std::vector<const uint
   if (root->type != IT_IDX && root->type != IT_ALL && root->type != IT_EMPTY)
     while (it_next(root) != kEof) {}  // DocIdSetOperator pulls every matching doc
   int64_t s = 0;
-  for (auto& it : r.pool) if (it->type == IT_SCAN) s += it->scanned;
+  for (auto& it : r.pool) if (it->type == IT_SCAN || it->type == IT_EXPR) s += it->scanned;
   return s;
 }
 
@@ -413,7 +453,7 @@ extern "C" int pgpu_filter_entries_scanned(const pgpu_filter_op* filter, int32_t
   if (num_filter_ops && depth != 1) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "malformed filter program");
   std::vector<const uint32_t*> masks(num_leaves, nullptr);
   for (int i = 0; i < num_leaves; ++i) {
-    if (types[i] < SL_EMPTY || types[i] > SL_RANGEIDX) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad leaf type");
+    if (types[i] < SL_EMPTY || types[i] > SL_EXPR) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad leaf type");
     if (types[i] >= SL_SCAN) {
       if (!leaf_masks || !leaf_masks[i]) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "leaf %d has no doc set", i);
       masks[i] = leaf_masks[i];

@@ -3,7 +3,7 @@
 // The statistic depends on the physical operator tree Pinot builds for the segment (FilterPlanNode.java:146-247,
 // FilterOperatorUtils.java:42-178: leaf operator choice, constant folding, AND child order) and on how its
 // docId iterators run (AndDocIdSet.java:60-146, OrDocIdSet.java:57-110, AndDocIdIterator.java:40-67,
-// OrDocIdIterator.java:25-130, SVScanDocIdIterator.java:56-94).  The GPU computes the document sets; this module
+// OrDocIdIterator.java:25-130, SVScanDocIdIterator.java:56-94, ExpressionScanDocIdIterator.java:70-123).  The GPU computes the document sets; this module
 // turns them into the count:
 //   - shapes whose count needs no document data (a single leaf, an OR of leaves) are counted on the host;
 //   - an AND of index leaves and scans without other children (applyAnd chain) and an AND of exactly two scans
@@ -21,14 +21,19 @@ namespace pgpu {
 // RangeIndexBasedFilterOperator (a RANGE predicate on an unsorted column with a range index, :57-62) -- its docIdSet
 // is a BitmapDocIdSet like an inverted leaf's; the entries of its own partial-match scan
 // (RangeIndexBasedFilterOperator.java:110-126) do not depend on the rest of the tree and are added by the caller.
-enum StatLeaf : int32_t { SL_EMPTY = 0, SL_ALL = 1, SL_SCAN = 2, SL_SORTED = 3, SL_BITMAP = 4, SL_RANGEIDX = 5 };
-constexpr int kStatLeafKinds = 6;
+// SL_EXPR: ExpressionFilterOperator (a predicate on an arithmetic expression, FilterPlanNode.java:179-186) -- scan-based,
+// ranked after every other AND child (priority 10, FilterOperatorUtils.java:171-172), never folded; its iterator
+// (ExpressionScanDocIdIterator) evaluates blocks of up to 10000 docs (DocIdSetPlanNode.MAX_DOC_PER_CALL) that start
+// wherever an advance() target lands, and counts every doc of a block it evaluates; its applyAnd counts its input.
+enum StatLeaf : int32_t { SL_EMPTY = 0, SL_ALL = 1, SL_SCAN = 2, SL_SORTED = 3, SL_BITMAP = 4, SL_RANGEIDX = 5,
+                          SL_EXPR = 6 };
+constexpr int kStatLeafKinds = 7;
 
 // Physical filter tree of one segment after folding (EmptyFilterOperator / MatchAllFilterOperator removed as
 // FilterPlanNode and getAnd/OrFilterOperator do), AND children in reorderAndFilterChildOperators order.  NOT is not
 // part of the reference's 0.10 FilterContext; it is a scan-based iterator over its child (the oracle's model).
 enum StatNodeType : int32_t { SN_EMPTY = 0, SN_ALL = 1, SN_SCAN = 2, SN_SORTED = 3, SN_BITMAP = 4, SN_NOT = 5,
-                              SN_AND = 6, SN_OR = 7, SN_RANGEIDX = 8 };
+                              SN_AND = 6, SN_OR = 7, SN_RANGEIDX = 8, SN_EXPR = 9 };
 struct StatNode {
   int32_t type = SN_ALL;
   int32_t leaf = -1;           // leaves: predicate index
@@ -48,7 +53,8 @@ struct StatsPlan {
   int32_t kind = STATS_CONST;
   int64_t constant = 0;              // STATS_CONST: the count
   std::vector<int32_t> index_leaves; // STATS_CHAIN: index leaves (ANDed first), then
-  std::vector<int32_t> scan_leaves;  //   scan leaves in Pinot's order; STATS_LEAP2: the two scans (A, B)
+  std::vector<int32_t> scan_leaves;  //   scan leaves in Pinot's order (expression leaves last: applyAnd counts the
+                                     //   same way for both); STATS_LEAP2: the two scans (A, B)
 };
 StatsPlan classify_stat_tree(const StatTree& t, int64_t num_docs);
 // Predicate indexes of the range-index leaves whose operator runs (SN_RANGEIDX nodes not under a NOT, which

@@ -40,13 +40,16 @@ constexpr int kFastLeaves = 4;              // pure-AND programs up to this many
 // LEAF_RAW_RANGE / LEAF_RAW_IN: host-side kinds of a raw-value predicate on a no-dictionary column
 // (RangePredicateEvaluatorFactory / InPredicateEvaluatorFactory raw evaluators).  raw_leaf_bitmap_kernel evaluates
 // them per query into a docId bitmap (KRawTask), which the scans read as a LEAF_BITMAP leaf.
+// LEAF_EXPR_RANGE / LEAF_EXPR_IN: host-side kinds of a predicate on a virtual column (an arithmetic expression,
+// ExpressionFilterOperator): the raw DOUBLE evaluator's bounds / key set over keys that expr_leaf_bitmap_kernel
+// computes per doc (KExprLeafTask) instead of loading; the scans read the result as a LEAF_BITMAP leaf too.
 // LEAF_BITDIR: a LEAF_BITMAP of one dictId -- its Roaring containers read in place, as BitmapBasedFilterOperator
 // uses a single bitmap without an OR (BitmapBasedFilterOperator.java:77-79): `set` is a directory of one 64-bit entry
 // per 65536-doc block: 0 = no docs in the block; a BITMAP container's address (its 2048 words); an ARRAY container's
 // address | 1 with its entry count in bits 48..63 (array_group_mask, device.h).
 enum LeafKind : int32_t { LEAF_NONE = 0, LEAF_ALL = 1, LEAF_RANGE = 2, LEAF_SET = 3, LEAF_DOCRANGE = 4, LEAF_BITMAP = 5,
-                          LEAF_RAW_RANGE = 6, LEAF_RAW_IN = 7, LEAF_BITDIR = 8 };
-constexpr int kLeafKinds = 9;
+                          LEAF_RAW_RANGE = 6, LEAF_RAW_IN = 7, LEAF_BITDIR = 8, LEAF_EXPR_RANGE = 9, LEAF_EXPR_IN = 10 };
+constexpr int kLeafKinds = 9;  // the kinds a kernel sees (pgpu_plan_leaf_kinds); the LEAF_EXPR_* kinds stay on the host
 enum OpCode : int32_t { OP_LEAF = 0, OP_AND = 1, OP_OR = 2, OP_NOT = 3 };
 // SLOT_SUM_FX (plans with PGPU_OPT_EXACT_FP_SUM): one fixed-point digit of a FLOAT / DOUBLE sum (fx_sum.h).  Only the
 // FX instances of the accumulating kernels see the kind (KParams / KStarParams.slot_kind: the scans, and K8d / K8h of
@@ -548,6 +551,30 @@ struct KRawJob {
   int32_t group0;
 };
 
+// One expression leaf of one segment (ExpressionFilterOperator: a predicate on a virtual column): per doc the
+// program's double over its operand columns -- dictId from the MSB-first fixed-bit forward index fwd[c] (bits[c] wide),
+// double from the segment's dictId -> double table dval[c] -- as its order-preserving key (expr_value_key), tested
+// against [lo, hi] (kind LEAF_RAW_RANGE) or the hi sorted keys expr_vals[lo, lo + hi) (LEAF_RAW_IN), negated for
+// NOT_EQ / NOT_IN, into the docbits words from `dst` in KRawTask's layout (the region's even word count written whole).
+struct KExprLeafTask {
+  const uint32_t* fwd[kExprMaxCols];
+  const double* dval[kExprMaxCols];
+  int32_t bits[kExprMaxCols];
+  ExprProg prog;  // (col[] is not read on the device)
+  int64_t dst;
+  int64_t lo, hi;
+  int32_t num_docs;
+  int32_t kind;
+  int32_t negate;
+  int32_t pad;
+};
+// expr_leaf_bitmap_kernel work item: docs [doc0, doc0 + kExprLeafJobDocs) of task `task`, a quarter per wave.
+constexpr int kExprLeafJobDocs = 8192;
+struct KExprLeafJob {
+  int32_t task;
+  int32_t doc0;
+};
+
 // Host-callable launchers (kernels.hip).
 int launch_unpack(const uint32_t* fwd, int32_t bits, int64_t start, int64_t n, int32_t* out, void* stream);
 int launch_gather_ids(const uint32_t* fwd, int32_t bits, const int32_t* docs, int32_t n, int32_t* out, void* stream);
@@ -656,6 +683,8 @@ int launch_inv_materialize(const KBitBlock* blocks, int64_t num_blocks, const KB
                            void* stream);
 int launch_raw_leaf_bitmaps(const KRawJob* jobs, int64_t num_jobs, const KRawTask* tasks, const int64_t* raw_vals,
                             uint32_t* docbits, void* stream);
+int launch_expr_leaf_bitmaps(const KExprLeafJob* jobs, int64_t num_jobs, const KExprLeafTask* tasks,
+                             const int64_t* expr_vals, uint32_t* docbits, void* stream);
 constexpr int kStarMaxSegs = 4096;  // star-tree segments per K6 launch (their group prefix lives in LDS)
 int launch_deadline_gate(uint64_t deadline, unsigned long long* stats, void* stream);
 int launch_startree_traverse(const KStarSeg* segs, int32_t num_segs, int64_t* seg_total, uint64_t deadline,

@@ -732,6 +732,93 @@ int launch_raw_leaf_bitmaps(const KRawJob* jobs, int64_t num_jobs, const KRawTas
   return PGPU_HIP_OK(hipGetLastError());
 }
 
+// Expression filter leaves (WHERE price * qty > 1000): one lane per doc.  A wave's 64 docs read adjacent forward-index
+// words of each operand column; the dictId -> double gathers of all operands are issued before the program is
+// interpreted (expr_eval over a register stack), four 64-doc steps at a time; the result's key is tested as a raw
+// DOUBLE leaf's and the wave's ballot is its two docbits words.  Lanes past numDocs load nothing and vote 0.  The task
+// is read through the constant address space: program, pointers and bounds are scalar operands.
+__global__ __launch_bounds__(256) void expr_leaf_bitmap_kernel(const KExprLeafJob* __restrict__ jobs,
+                                                               const KExprLeafTask* __restrict__ tasks,
+                                                               const int64_t* __restrict__ expr_vals,
+                                                               uint32_t* __restrict__ docbits) {
+  const KExprLeafJob J = jobs[blockIdx.x];
+  cmem<KExprLeafTask>* T = cp(tasks + J.task);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t num_docs = T->num_docs;
+  const int nc = T->prog.ncols;
+  const int kind = T->kind, negate = T->negate;
+  const int64_t lo = T->lo, hi = T->hi;
+  gmem<int64_t>* __restrict__ set = gp(expr_vals) + (kind == LEAF_RAW_IN ? lo : 0);
+  constexpr int kWaveDocs = kExprLeafJobDocs / 4;
+  constexpr int kU = 4;  // 64-doc steps in flight per wave: their loads are issued together (the chain dictId ->
+                         // double is two dependent loads per operand, and a step on its own waits for both)
+  for (int it = 0; it < kWaveDocs / (64 * kU); ++it) {
+    const int64_t base = (int64_t)J.doc0 + wave * kWaveDocs + it * (64 * kU);  // wave-uniform
+    if (base >= num_docs) break;
+    bool live[kU];
+    uint32_t id[kExprMaxCols][kU];
+    double v[kExprMaxCols][kU], out[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) live[u] = base + u * 64 + lane < num_docs;
+#pragma unroll
+    for (int c = 0; c < kExprMaxCols; ++c) {
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        id[c][u] = 0;
+        v[c][u] = 0.0;
+      }
+      if (c < nc) {  // wave-uniform
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+          if (live[u]) id[c][u] = gather_id(T->fwd[c], T->bits[c], base + u * 64 + lane);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kExprMaxCols; ++c)
+      if (c < nc) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+          if (live[u]) v[c][u] = gp(T->dval[c])[id[c][u]];
+      }
+    expr_eval<kU>(T->prog, v, out);
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int64_t d0 = base + u * 64;
+      if (d0 >= num_docs) break;  // wave-uniform
+      const int64_t key = expr_value_key(out[u]);
+      bool hit;
+      if (kind == LEAF_RAW_RANGE) {
+        hit = lo <= key && key <= hi;
+      } else {
+        const int n = (int)hi;
+        int a = 0, b = n;  // first set key >= key
+        while (a < b) {
+          const int mid = (a + b) >> 1;
+          if (set[mid] < key) a = mid + 1;
+          else b = mid;
+        }
+        hit = a < n && set[a] == key;
+      }
+      if (negate) hit = !hit;
+      const unsigned long long m = __ballot(hit && live[u]);
+      if (lane == 0) {
+        uint32_t* w = docbits + T->dst + (d0 >> 5);
+        w[0] = (uint32_t)m;
+        w[1] = (uint32_t)(m >> 32);
+      }
+    }
+  }
+}
+
+int launch_expr_leaf_bitmaps(const KExprLeafJob* jobs, int64_t num_jobs, const KExprLeafTask* tasks,
+                             const int64_t* expr_vals, uint32_t* docbits, void* stream) {
+  if (num_jobs <= 0) return 0;
+  if (num_jobs > INT32_MAX) return -1;
+  hipLaunchKernelGGL(expr_leaf_bitmap_kernel, dim3((unsigned)num_jobs), dim3(256), 0, S(stream), jobs, tasks, expr_vals,
+                     docbits);
+  return PGPU_HIP_OK(hipGetLastError());
+}
+
 int launch_inv_materialize(const KBitBlock* blocks, int64_t num_blocks, const KBitTask* tasks, uint32_t* docbits,
                            void* stream) {
   if (num_blocks <= 0) return 0;

@@ -469,6 +469,8 @@ struct Scratch {
   DevBuf docbits, bittasks, bitblocks;  // inverted-index leaves: materialised docId bitmaps and their container tasks
   DevBuf rawtasks;                      // raw-value leaves: tasks, jobs, IN keys (one buffer)
   HostPinned rawstage;
+  DevBuf exprtasks;                     // expression leaves: tasks, jobs, IN keys (one buffer)
+  HostPinned exprstage;
   DevBuf segrec, sets, slab, table, hash_keys, stats, ckeys, cslots, counter, bitmap, tile_seg, starrec, starwork;
   DevBuf part_start, block_off, rec_key, rec_val;  // partitioned group-by (large dense key spaces)
   DevBuf rec_key32;                                // hashed partitions: whole record keys
@@ -497,7 +499,7 @@ struct Scratch {
   // device bytes held (acquire_scratch prefers the scratch that has grown the most)
   size_t footprint() const {
     size_t n = 0;
-    for (const DevBuf* b : {&docbits, &bittasks, &bitblocks, &rawtasks, &segrec, &sets, &slab, &table, &hash_keys,
+    for (const DevBuf* b : {&docbits, &bittasks, &bitblocks, &rawtasks, &exprtasks, &segrec, &sets, &slab, &table, &hash_keys,
                             &stats, &ckeys, &cslots, &counter, &bitmap, &tile_seg, &starrec, &starwork, &part_start,
                             &block_off, &rec_key, &rec_val, &rec_key32, &stage_keys, &coarse_fill, &fine_fill,
                             &mid_key, &mid_val, &leap_maps, &mask_jobs, &leaf_masks, &hsort, &part_mm, &dc_bits, &dc_recv})
@@ -510,6 +512,7 @@ struct Scratch {
     for (auto& e : cev) if (e) hipEventDestroy(e);
     cev.clear();
     docbits.release(); bittasks.release(); bitblocks.release(); rawtasks.release(); rawstage.release();
+    exprtasks.release(); exprstage.release();
     segrec.release(); tile_seg.release(); sets.release(); slab.release(); table.release(); hash_keys.release(); stats.release();
     ckeys.release(); cslots.release(); counter.release(); bitmap.release(); stage.release(); readback.release();
     starrec.release();
@@ -632,6 +635,7 @@ struct LeafHost {
   std::vector<uint32_t> set;  // bitset words for LEAF_SET
   std::vector<int32_t> inv_ids;  // LEAF_BITMAP: matching dictIds whose inverted-index bitmaps are ORed
   std::vector<int64_t> raw;      // LEAF_RAW_RANGE: inclusive key bounds {lo, hi}; LEAF_RAW_IN: sorted distinct keys
+                                 // (LEAF_EXPR_RANGE / LEAF_EXPR_IN: the same, over the expression's keys)
   double inv_frac = 0;           // LEAF_BITMAP: fraction of the segment's docs in those bitmaps
 };
 
@@ -766,6 +770,14 @@ struct pgpu_plan_s {
   std::vector<KBitBlock> bit_blocks;      // every 65536-doc block of the docbits, with its tasks
   std::vector<KRawTask> raw_tasks;        // raw-value leaves evaluated into docbits regions (raw_leaf_bitmap_kernel)
   std::vector<int64_t> raw_vals;          // their IN / NOT_IN keys
+  // Expression leaves (WHERE price * qty > 1000): leaf_exprs[l] is the program of predicate l, copied from the table's
+  // virtual column when the query's columns are bound (ncols 0: a predicate on a real column; empty in a plan without
+  // such a leaf, so that a plan-cache hit copies nothing more than before).  Their tasks are
+  // evaluated into docbits regions by expr_leaf_bitmap_kernel, beside the raw-value leaves'.
+  std::vector<pgpu::ExprProg> leaf_exprs;
+  std::vector<KExprLeafTask> expr_tasks;
+  std::vector<int64_t> expr_vals;         // their IN / NOT_IN keys
+  bool expr_leaf(int l) const { return (size_t)l < leaf_exprs.size() && leaf_exprs[l].ncols > 0; }
   std::vector<std::shared_ptr<InvIndex>> inv_refs;  // inverted indexes the bit tasks point into (kept alive)
   std::shared_ptr<DeviceImage> image;     // cached plans: device-resident records / tile map (one-launch plans)
   int64_t num_tiles = 0;

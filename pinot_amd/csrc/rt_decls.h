@@ -87,6 +87,7 @@ int abandon_scratch(Scratch* sc, hipStream_t stream);
 bool cancelled(const pgpu_plan_s* P);
 int wait_plan(pgpu_plan_s* P, hipStream_t stream);
 int launch_raw_leaves(const pgpu_plan_s* P, Scratch* sc, hipStream_t stream);
+int launch_expr_leaves(const pgpu_plan_s* P, Scratch* sc, hipStream_t stream);
 int exec_prologue(pgpu_plan_s* P, hipStream_t stream, void* d_table, int max_chunks, ExecCtx& X);
 int exec_upload_chunk(pgpu_plan_s* P, hipStream_t stream, const ExecCtx& X, const LaunchChunk& C);
 bool check_launch_on();

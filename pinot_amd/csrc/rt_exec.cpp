@@ -1,4 +1,5 @@
 // rt_exec.cpp -- query execution: the wait, and the launches in phases (rt.h).  Finalize is rt_finalize.cpp.
+#include "expr_leaf.h"
 #include "rt_decls.h"
 
 namespace pgpu {
@@ -162,6 +163,30 @@ int launch_raw_leaves(const pgpu_plan_s* P, Scratch* sc, hipStream_t stream) {
   return 0;
 }
 
+// Expression leaves of a plan, staged and launched as the raw-value leaves are: expr_leaf_bitmap_kernel evaluates each
+// leaf's program per doc into its docbits region.
+int launch_expr_leaves(const pgpu_plan_s* P, Scratch* sc, hipStream_t stream) {
+  if (P->expr_tasks.empty()) return 0;
+  std::vector<KExprLeafJob> jobs;
+  expr_leaf_jobs(P->expr_tasks, &jobs);
+  const size_t tb = (P->expr_tasks.size() * sizeof(KExprLeafTask) + 15) & ~size_t(15);
+  const size_t jb = (jobs.size() * sizeof(KExprLeafJob) + 15) & ~size_t(15);
+  const size_t vb = std::max<size_t>(P->expr_vals.size(), 1) * 8;
+  TRY(sc->exprtasks.ensure(tb + jb + vb));
+  TRY(sc->exprstage.ensure(tb + jb + vb));
+  uint8_t* hs = reinterpret_cast<uint8_t*>(sc->exprstage.p);
+  memcpy(hs, P->expr_tasks.data(), P->expr_tasks.size() * sizeof(KExprLeafTask));
+  if (!jobs.empty()) memcpy(hs + tb, jobs.data(), jobs.size() * sizeof(KExprLeafJob));
+  if (!P->expr_vals.empty()) memcpy(hs + tb + jb, P->expr_vals.data(), P->expr_vals.size() * 8);
+  HIP_TRY(hipMemcpyAsync(sc->exprtasks.p, hs, tb + jb + vb, hipMemcpyHostToDevice, stream));
+  uint8_t* d = sc->exprtasks.as<uint8_t>();
+  if (launch_expr_leaf_bitmaps(reinterpret_cast<const KExprLeafJob*>(d + tb), (int64_t)jobs.size(),
+                               reinterpret_cast<const KExprLeafTask*>(d), reinterpret_cast<const int64_t*>(d + tb + jb),
+                               sc->docbits.as<uint32_t>(), stream))
+    return fail(PGPU_ERR_DEVICE, "expression filter launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
 // ---- execution, in three phases so that plan_create can launch segment chunks while it still plans the rest
 // (streamed plans): prologue (buffers, table init, stats), one launch per chunk of segment records, epilogue
 // (star-tree kernels, slab reduce).  A plan that is not streamed is one chunk.
@@ -303,7 +328,7 @@ static int exec_image(pgpu_plan_s* P, hipStream_t stream, ExecCtx& X) {
   return 0;
 }
 
-// The filter's per-query docId bitmaps: inverted-index leaves and raw-value leaves.
+// The filter's per-query docId bitmaps: inverted-index leaves, raw-value leaves and expression leaves.
 static int exec_filter_bitmaps(pgpu_plan_s* P, hipStream_t stream) {
   Scratch* sc = P->scratch;
   if (P->docbit_words > 0) TRY(sc->docbits.ensure((size_t)P->docbit_words * 4));
@@ -323,7 +348,8 @@ static int exec_filter_bitmaps(pgpu_plan_s* P, hipStream_t stream) {
       return fail(PGPU_ERR_DEVICE, "inverted-index materialise launch failed: %s",
                   hipGetErrorString(hipGetLastError()));
   }
-  return launch_raw_leaves(P, sc, stream);  // raw-value leaves' docbits regions
+  TRY(launch_raw_leaves(P, sc, stream));  // raw-value leaves' docbits regions
+  return launch_expr_leaves(P, sc, stream);  // expression leaves' likewise
 }
 
 // X.kp: what every launch of the execution shares (no buffer but the statistics block; exec_tables adds the rest).

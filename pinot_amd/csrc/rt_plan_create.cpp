@@ -1,5 +1,6 @@
 // rt_plan_create.cpp -- plan_create_impl: a query over a segment list becomes a plan, in named phases that share one
 // PlanCtx (rt.h; the predicate translation and the sizing helpers the phases call are rt_plan.cpp's).
+#include "expr_leaf.h"
 #include "rt_decls.h"
 
 namespace pgpu {
@@ -40,6 +41,8 @@ struct Chunk {
   std::vector<KBitBlock> bit_blocks;
   std::vector<KRawTask> raw_tasks;
   std::vector<int64_t> raw_vals;
+  std::vector<KExprLeafTask> expr_tasks;
+  std::vector<int64_t> expr_vals;
   std::vector<std::shared_ptr<InvIndex>> inv_refs;
   std::vector<pgpu_plan_s::GenericStat> generic;  // rec: chunk-relative record index
   bool any_leap2 = false;
@@ -58,6 +61,13 @@ int query_col(pgpu_plan_s* P, int col) {
     if (P->query_cols[i] == col) return (int)i;
   P->query_cols.push_back(col);
   return (int)P->query_cols.size() - 1;
+}
+
+// The column of predicate l in segment s.  An expression leaf (a predicate on a virtual column) has none: a plain
+// dictionary column without any index stands in, so the leaf is nobody's sorted, inverted or range-index leaf.
+const Column& pred_column(const pgpu_plan_s* P, const Segment* s, const pgpu_query* q, int l) {
+  static const Column kNoColumn;
+  return P->expr_leaf(l) ? kNoColumn : s->cols[q->predicates[l].column];
 }
 
 // Segment references (SegmentDataManager acquire): the table mutex is held only to take them here and, in
@@ -80,15 +90,42 @@ int acquire_segments(PlanCtx& cx, const int64_t* handles, int32_t nsegs) {
   return 0;
 }
 
+// The program of predicate i's virtual column vcol (ExpressionFilterOperator), copied under the table mutex as
+// plan_expr copies an aggregation's.  Operands are those of expression aggregations: dictionary columns (STRING and
+// virtual operands were refused when the expression was registered).
+int bind_expr_leaf(PlanCtx& cx, int i, int vcol) {
+  pgpu_plan_s* P = cx.P;
+  ExprProg& prog = P->leaf_exprs[i];
+  {
+    std::lock_guard<std::mutex> g(cx.t->mu);
+    const int e = vcol - (int)cx.t->names.size();
+    if (e < 0 || e >= (int)cx.t->exprs.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "predicate %d: bad column %d", i, vcol);
+    prog = cx.t->exprs[e].prog;
+  }
+  for (int c = 0; c < prog.ncols; ++c)
+    for (const Segment* s : P->segs)
+      if (s->cols[prog.col[c]].raw)
+        return fail(PGPU_ERR_UNSUPPORTED, "predicate %d: expression over raw (no-dictionary) column %d", i, prog.col[c]);
+  cx.any_raw_leaf = true;  // planned and launched as a raw-value leaf is: a docbits region per query
+  return 0;
+}
+
 // Predicate and group-by columns become query columns.  Raw (no-dictionary) columns: aggregation operands and
 // raw-value predicate leaves; a group-by on one runs on Pinot's NoDictionary*GroupKeyGenerator, not here.
 int bind_query_columns(PlanCtx& cx) {
   const pgpu_query* q = cx.q;
   pgpu_plan_s* P = cx.P;
   const int ncols = (int)cx.t->names.size();
+  for (int i = 0; i < q->num_predicates; ++i)
+    if (q->predicates[i].column >= ncols) { P->leaf_exprs.assign(q->num_predicates, ExprProg{}); break; }
   for (int i = 0; i < q->num_predicates; ++i) {
     const int c = q->predicates[i].column;
-    if (c < 0 || c >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "predicate %d: bad column %d", i, c);
+    if (c >= ncols) {  // a virtual column: the operands are read by the leaf's own kernel, not by the scan -- the
+      TRY(bind_expr_leaf(cx, i, c));  // leaf's record column (never read: a LEAF_BITMAP) is its first operand
+      P->leaf_slot.push_back(query_col(P, P->leaf_exprs[i].col[0]));
+      continue;
+    }
+    if (c < 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "predicate %d: bad column %d", i, c);
     P->leaf_slot.push_back(query_col(P, c));
   }
   P->num_leaves = q->num_predicates;
@@ -100,6 +137,7 @@ int bind_query_columns(PlanCtx& cx) {
   }
   for (Segment* s : P->segs) {
     for (int i = 0; i < q->num_predicates; ++i) {
+      if (P->expr_leaf(i)) continue;
       const Column& c = s->cols[q->predicates[i].column];
       cx.any_raw_leaf |= c.raw;
       if (c.raw && cx.t->types[q->predicates[i].column] == PGPU_STRING)
@@ -503,6 +541,8 @@ int plan_segment_arrays(PlanCtx& cx) {
       P->slot_value_cols(k, &vcols);  // the slot's column, or the operands of its expression
       for (int32_t c : vcols) TRY(ensure_values(t, *s, c, stream));
     }
+    for (const ExprProg& g : P->leaf_exprs)  // expression leaves: their operands' dictId -> double tables
+      for (int c = 0; c < g.ncols; ++c) TRY(ensure_values(t, *s, g.col[c], stream));
     if (P->first_doc_slot) TRY(ensure_docid(t, s->num_docs, stream));
   }
   // the distinct columns' local -> global mapping, as a key column's (after the key LUTs: plan_star_segment indexes
@@ -849,10 +889,13 @@ int prepare_translation(PlanCtx& cx) {
   P->segrec.reserve(P->segs.size() * (size_t)P->seg_stride);
   cx.parsed.resize(P->num_leaves);
   for (int l = 0; l < P->num_leaves; ++l)
-    TRY(parse_predicate(t->types[q->predicates[l].column], q->predicates[l], &cx.parsed[l]));
+    // (an expression's value is a DOUBLE: its literals are read by Double.parseDouble)
+    TRY(parse_predicate(P->expr_leaf(l) ? PGPU_DOUBLE : t->types[q->predicates[l].column], q->predicates[l], &cx.parsed[l]));
   // (DISTINCTCOUNT: StarTreeUtils finds no function-column pair for it -- such a plan scans)
   cx.star_allowed = q->num_group_by > 0 && !(q->options & PGPU_OPT_NO_STAR_TREE) && P->stage_end.empty() &&
                     P->dc.empty() && P->pct.empty() && P->exprs.empty() && star_composites(P->ops, q, &cx.star_comps);
+  // (a filter with an expression leaf never takes the star-tree: StarTreeUtils.java:255-258)
+  for (int l = 0; l < P->num_leaves; ++l) cx.star_allowed &= !P->expr_leaf(l);
   // Aggregation-only over a match-all segment: COUNT-only is answered from metadata, MIN / MAX / DISTINCTCOUNT-only
   // from the dictionaries (AggregationPlanNode.java:165-183, isFitForDictionaryBasedPlan :233-246; every dictionary
   // value occurs in its segment, so the scan gives the same set) -- same values, numEntriesScannedPostFilter 0
@@ -874,7 +917,7 @@ int prepare_translation(PlanCtx& cx) {
   for (Segment* s : P->segs) {
     cx.any_star |= cx.star_allowed && s->star != nullptr;
     for (int l = 0; l < q->num_predicates; ++l)
-      cx.any_inv |= s->cols[q->predicates[l].column].inv != nullptr;
+      cx.any_inv |= pred_column(P, s, q, l).inv != nullptr;
   }
   cx.qcol_key.assign(P->query_cols.size(), -1);
   cx.qcol_val.assign(P->query_cols.size(), 0);
@@ -905,9 +948,11 @@ void order_leaves(PlanCtx& cx) {
   if (P->pure_and && P->num_leaves > 1) {
     // FilterOperatorUtils.reorderAndFilterChildOperators (:143-178): sorted-index leaves, then bitmap
     // (inverted-index) leaves, then range-index leaves, then scans.
-    std::vector<int> first, second, third, rest;
+    // ... then the expression leaves (ExpressionFilterOperator: priority 10, :171-172; the sort is stable).
+    std::vector<int> first, second, third, rest, last;
     for (int l = 0; l < P->num_leaves; ++l) {
       const pgpu_predicate& pr = q->predicates[l];
+      if (P->expr_leaf(l)) { last.push_back(l); continue; }
       const bool eq_in = pr.type == PGPU_PRED_EQ || pr.type == PGPU_PRED_NOT_EQ || pr.type == PGPU_PRED_IN ||
                          pr.type == PGPU_PRED_NOT_IN;
       bool all_sorted = !P->segs.empty(), all_inv = !P->segs.empty() && eq_in && !P->no_inverted;
@@ -922,6 +967,7 @@ void order_leaves(PlanCtx& cx) {
     first.insert(first.end(), second.begin(), second.end());
     first.insert(first.end(), third.begin(), third.end());
     first.insert(first.end(), rest.begin(), rest.end());
+    first.insert(first.end(), last.begin(), last.end());
     perm = first;
     std::vector<int32_t> slots(P->num_leaves);
     for (int k = 0; k < P->num_leaves; ++k) slots[k] = P->leaf_slot[perm[k]];
@@ -939,7 +985,13 @@ int translate_leaves(const PlanCtx& cx, const Segment* s, std::vector<LeafHost>&
   for (int l = 0; l < P->num_leaves; ++l) {
     LeafHost& lh = leaves[l];
     lh.kind = LEAF_NONE; lh.negate = 0; lh.lo = 0; lh.span = 0;
-    const Column& pc = s->cols[q->predicates[l].column];
+    const Column& pc = pred_column(P, s, q, l);
+    if (P->expr_leaf(l)) {  // the raw DOUBLE evaluator over computed keys; never folded (ExpressionFilterOperator)
+      translate_raw_predicate(PGPU_DOUBLE, q->predicates[l], cx.parsed[l], &lh);
+      lh.kind = lh.kind == LEAF_RAW_IN ? LEAF_EXPR_IN : LEAF_EXPR_RANGE;
+      tri[l] = T_VAR;
+      continue;
+    }
     if (pc.raw) translate_raw_predicate(cx.t->types[q->predicates[l].column], q->predicates[l], cx.parsed[l], &lh);
     else TRY(translate_predicate(pc, q->predicates[l], cx.parsed[l], &lh, ids_scratch));
     if (!P->no_inverted && !s->star) to_inverted_leaf(pc, q->predicates[l], *s, &lh);
@@ -967,11 +1019,11 @@ int32_t segment_stats(const PlanCtx& cx, const Segment* s, const std::vector<Lea
   uint64_t sig = 0;
   for (int l = 0; l < P->num_leaves; ++l) {
     const pgpu_predicate& pr = q->predicates[l];
-    const Column& col = s->cols[pr.column];
+    const Column& col = pred_column(P, s, q, l);
     // FilterOperatorUtils.getLeafFilterOperator (:42-82): sorted column -> SortedIndexBasedFilterOperator;
     // RANGE with a range index -> RangeIndexBasedFilterOperator; other predicates with an inverted index ->
-    // BitmapBasedFilterOperator; else a scan
-    const int k = tri[l] == T_NONE ? SL_EMPTY : tri[l] == T_ALL ? SL_ALL : col.sorted ? SL_SORTED :
+    // BitmapBasedFilterOperator; else a scan.  An expression: ExpressionFilterOperator (FilterPlanNode.java:179-186)
+    const int k = P->expr_leaf(l) ? SL_EXPR : tri[l] == T_NONE ? SL_EMPTY : tri[l] == T_ALL ? SL_ALL : col.sorted ? SL_SORTED :
                   (pr.type != PGPU_PRED_RANGE && col.inv) ? SL_BITMAP :
                   (pr.type == PGPU_PRED_RANGE && col.rng && leaves[l].kind == LEAF_RANGE) ? SL_RANGEIDX : SL_SCAN;
     sig = sig * kStatLeafKinds + (uint64_t)k;
@@ -996,11 +1048,12 @@ void estimate_chunk_selectivity(const PlanCtx& cx, const Segment* s, const std::
   std::vector<double> frac(P->num_leaves, 1.0);
   for (int l = 0; l < P->num_leaves; ++l) {
     const LeafHost& lh = leaves[l];
-    const double card = std::max(1, s->cols[cx.q->predicates[l].column].card);
+    const double card = std::max(1, pred_column(P, s, cx.q, l).card);
     double f = lh.kind == LEAF_ALL ? 1.0 : lh.kind == LEAF_NONE ? 0.0 : lh.kind == LEAF_RANGE ? lh.span / card : 0.0;
     if (lh.kind == LEAF_DOCRANGE) f = (double)lh.span / std::max(1, s->num_docs);
     if (lh.kind == LEAF_BITMAP) f = lh.inv_frac;
     if (lh.kind == LEAF_RAW_RANGE || lh.kind == LEAF_RAW_IN) f = 0.5;  // no dictionary to estimate from
+    if (lh.kind == LEAF_EXPR_RANGE || lh.kind == LEAF_EXPR_IN) f = 0.5;  // likewise
     if (lh.kind == LEAF_SET) {
       int64_t ones = 0;
       for (uint32_t w : lh.set) ones += __builtin_popcount(w);
@@ -1098,6 +1151,22 @@ void emit_raw_task(Chunk& C, const Segment* s, const Column& col, const LeafHost
   kl.negate = 0;
 }
 
+// Expression leaf: evaluated per query into a docId bitmap region allocated by emit_raw_task's rule
+// (expr_leaf_bitmap_kernel, negation included) that the scan reads as a LEAF_BITMAP.
+void emit_expr_task(Chunk& C, const Segment* s, const ExprProg& prog, const LeafHost& lh, KLeaf& kl, int64_t field) {
+  C.bit_fix.emplace_back(field, C.docbit_words);
+  ExprLeafOperand ops[kExprMaxCols];
+  for (int c = 0; c < prog.ncols; ++c) {
+    const Column& col = s->cols[prog.col[c]];
+    ops[c] = ExprLeafOperand{col.d_fwd, col.d_val, col.bits};  // (d_val: ensure_values, plan_segment_arrays)
+  }
+  C.expr_tasks.push_back(make_expr_leaf_task(prog, ops, s->num_docs, lh.kind == LEAF_EXPR_IN, lh.raw, lh.negate,
+                                             C.docbit_words, 0, &C.expr_vals));
+  C.docbit_words += leaf_region_words(s->num_docs);
+  kl.kind = LEAF_BITMAP;
+  kl.negate = 0;
+}
+
 // LEAF_BITMAP of one dictId (no OR to compute): the scan reads its containers in place through a block directory --
 // BITMAP containers word by word, ARRAY containers (< 4096 docs of a block, e.g. a segment's partial last block) by a
 // binary search of their sorted offsets (array_group_mask); entry = payload address, | 1 and the entry count in bits
@@ -1172,7 +1241,7 @@ void emit_leaves(const PlanCtx& cx, const Segment* s, const std::vector<LeafHost
                  Chunk& C) {
   for (int k = 0; k < cx.P->num_leaves; ++k) {
     const LeafHost& lh = leaves[cx.perm[k]];
-    const Column& col = s->cols[cx.q->predicates[cx.perm[k]].column];
+    const Column& col = pred_column(cx.P, s, cx.q, cx.perm[k]);
     const int64_t field = kl_off + (int64_t)(k * sizeof(KLeaf) + offsetof(KLeaf, set));
     kl[k].kind = lh.kind;
     kl[k].negate = lh.negate;
@@ -1181,6 +1250,8 @@ void emit_leaves(const PlanCtx& cx, const Segment* s, const std::vector<LeafHost
     kl[k].set = nullptr;
     if (lh.kind == LEAF_SET) emit_set_words(C, lh, field);
     if (lh.kind == LEAF_RAW_RANGE || lh.kind == LEAF_RAW_IN) emit_raw_task(C, s, col, lh, kl[k], field);
+    if (lh.kind == LEAF_EXPR_RANGE || lh.kind == LEAF_EXPR_IN)
+      emit_expr_task(C, s, cx.P->leaf_exprs[cx.perm[k]], lh, kl[k], field);
     const bool bitdir = lh.kind == LEAF_BITMAP && lh.inv_ids.size() == 1 && emit_bitdir(C, s, col, lh, kl[k], field);
     if (kl[k].kind >= 0 && kl[k].kind < kLeafKinds) C.leaf_kinds[kl[k].kind]++;
     if (lh.kind == LEAF_BITMAP && !bitdir) emit_bitmap_tasks(C, s, col, lh, field);
@@ -1428,6 +1499,12 @@ void merge_chunk(pgpu_plan_s* P, Chunk& C, int64_t tile_shift) {
     P->raw_tasks.push_back(rt);
   }
   P->raw_vals.insert(P->raw_vals.end(), C.raw_vals.begin(), C.raw_vals.end());
+  for (KExprLeafTask et : C.expr_tasks) {
+    et.dst += P->docbit_words;
+    if (et.kind == LEAF_RAW_IN) et.lo += (int64_t)P->expr_vals.size();
+    P->expr_tasks.push_back(et);
+  }
+  P->expr_vals.insert(P->expr_vals.end(), C.expr_vals.begin(), C.expr_vals.end());
   P->inv_refs.insert(P->inv_refs.end(), C.inv_refs.begin(), C.inv_refs.end());
   for (auto& g : C.generic) {
     g.rec += rec0 / std::max(P->seg_stride, 1);
@@ -1462,7 +1539,7 @@ int run_streamed(PlanCtx& cx, int stream_chunks) {
     for (int l = 0; l < P->num_leaves; ++l) {
       const int ty = q->predicates[l].type;
       if (ty == PGPU_PRED_IN || ty == PGPU_PRED_NOT_IN)
-        P->set_words_bound += ((int64_t)s->cols[q->predicates[l].column].card + 31) / 32;
+        P->set_words_bound += ((int64_t)pred_column(P, s, q, l).card + 31) / 32;
     }
   }
   if (!P->scratch) return fail(PGPU_ERR_INVALID_ARGUMENT, "streamed plan without scratch");

@@ -299,10 +299,15 @@ class GpuTable:
         return [(arr[i].op, arr[i].column, arr[i].literal) for i in range(n.value)], name.value.decode()
 
     def query_c(self, query):
-        """query.to_c over this table's columns, the query's expressions (SUM(price * qty)) registered as virtual
-        columns on first use: from then on the expression's function-form name is a column of the table's index."""
+        """query.to_c over this table's columns, the query's expressions (SUM(price * qty), WHERE price * qty > 1000;
+        equal ones share a column) registered as virtual columns on first use: from then on the expression's function-form name is a column of the table's index."""
         exprs = query.expressions
-        for fn, col in query.aggregations:
+        used = [(fn, col) for fn, col in query.aggregations]
+        if query.filter is not None and exprs:  # predicates on expressions share the virtual columns
+            preds = []
+            query.filter.postfix(preds, [])
+            used += [("WHERE", p.column) for p in preds]
+        for fn, col in used:
             if col in exprs and col not in self.index and fn != "COUNT":
                 from .query import expr_program
                 ops = []
@@ -530,7 +535,7 @@ class GpuTable:
         _lib.FpSumRangeC."""
         if isinstance(query, str):
             from .query import parse_query
-            query = parse_query(query)
+            query = parse_query(query, filter_expressions=True)
         hs = np.ascontiguousarray(list(handles), dtype=np.int64)
         q, keep = self.query_c(query)
         na = len(query.aggregations)
@@ -568,7 +573,7 @@ class Plan:
         fp_sum_ranges: the agreed ranges of pgpu_plan_create_agreed (not with execute)."""
         if isinstance(query, str):
             from .query import parse_query
-            query = parse_query(query)
+            query = parse_query(query, filter_expressions=True)
         self.table = table
         self.query = query
         self.lib = table.lib

@@ -299,7 +299,8 @@ class QueryContext:
         self.group_by = list(group_by)
         # expressions: {function-form name: canonical tree} of the aggregation arguments that are expressions, as the
         # parser found them -- every other name is a column, whatever characters it has (a quoted identifier).  None
-        # (a query built by hand): an argument with one of ( ) + - * / is read as an expression's text.
+        # (a query built by hand): an argument, or a predicate's column, with one of ( ) + - * / is read as an
+        # expression's text.
         sniff = expressions is None
         for c in self.group_by:
             if sniff and is_expression(c):
@@ -317,6 +318,10 @@ class QueryContext:
                 if tree[0] != "col":
                     self.expressions[col] = tree
             self.aggregations.append((function_name(a[0], *a[2:]), col))
+        # a predicate on an expression (WHERE price * qty > 1000): its column is the canonical name too -- in a copy of
+        # the filter tree, the caller's FilterContext and Predicate objects stay as they were given
+        if sniff and filter is not None:
+            self.filter = self._canonical_filter(filter)
         self.num_groups_limit = num_groups_limit
         # SQL-mode parts (QueryContext.getSelectExpressions / getOrderByExpressions / getLimit): the SELECT list as
         # ('col', name) / ('agg', FN, col), ORDER BY as [(expr, ascending)], LIMIT; the combine's trim options
@@ -331,6 +336,24 @@ class QueryContext:
         self.end_time_ms = 0
         # the executions record HIP timing events for GpuPlan.timing_us (PGPU_OPT_TIMING; off for serving)
         self.timing = False
+
+    def _canonical_filter(self, f):
+        """f with every predicate column that reads as an expression replaced by its canonical name (the trees go into
+        self.expressions): new nodes where something changes below them, the given ones elsewhere."""
+        if f.type == FilterContext.PREDICATE:
+            p = f.predicate
+            if not is_expression(p.column):
+                return f
+            tree = parse_expression(p.column)
+            name = expr_name(tree)
+            if tree[0] != "col":
+                self.expressions[name] = tree
+            q = Predicate(p.type, name, p.values, p.lower_inclusive, p.upper_inclusive)
+            return FilterContext.pred(q)
+        kids = [self._canonical_filter(k) for k in f.children]
+        if all(k is c for k, c in zip(kids, f.children)):
+            return f
+        return FilterContext(f.type, kids)
 
     def set_timeout(self, timeout_ms):
         """End time = now + timeout_ms (the broker's arrival time + queryOptions timeoutMs,
@@ -363,7 +386,8 @@ class QueryContext:
         if self.filter is not None:
             preds = []
             self.filter.postfix(preds, [])
-            cols += [p.column for p in preds]
+            for p in preds:
+                cols += expr_columns(self.expressions[p.column]) if p.column in self.expressions else [p.column]
         cols += self.group_by
         for _, c in self.aggregations:
             cols += expr_columns(self.expressions[c]) if c in self.expressions else [c] * (c != "*")
@@ -493,11 +517,16 @@ def _tokenize(s):
     return out
 
 
+_ARITH_OPS = (("op", "+"), ("op", "-"), ("op", "*"), ("op", "/"))
+
+
 class _Parser:
-    def __init__(self, sql):
+    def __init__(self, sql, filter_expressions=False):
         self.t = _tokenize(sql)
         self.i = 0
-        self.exprs = {}  # function-form name -> tree of the aggregation arguments that are expressions
+        # function-form name -> tree of the aggregation arguments and predicate left-hand sides that are expressions
+        self.exprs = {}
+        self.filter_expressions = filter_expressions  # WHERE price * qty > 1000 (parse_query)
 
     def peek(self, k=0):
         return self.t[self.i + k] if self.i + k < len(self.t) else (None, None)
@@ -602,6 +631,33 @@ class _Parser:
             return expr_node(fn, args)
         return ("col", self.take("id"))
 
+    def rhs_literal(self, lhs):
+        """A predicate's right-hand side: a literal.  After an expression a name there is a column (a * b < c), which
+        the reference rewrites in its broker and this layer does not model.  After a plain column a name stays the
+        literal it has always been ("x" in double quotes, true): filter_expressions changes nothing for plain predicates."""
+        if lhs in self.exprs and self.peek()[0] == "id":
+            raise ValueError("column %r on the right-hand side of %s: an expression is compared with a literal"
+                             % (self.peek()[1], lhs))
+        return self.literal()
+
+    def predicate_lhs(self):
+        """A predicate's left-hand side: a column, or -- with filter_expressions -- an arithmetic expression, kept as
+        its canonical function-form name with the tree in self.exprs (the reference's ExpressionFilterOperator)."""
+        if not self.filter_expressions:
+            col = self.take("id")
+            if self.peek() in (("op", "("),) + _ARITH_OPS:
+                raise ValueError("expression in WHERE near %r: expressions are supported inside aggregations only "
+                                 "(parse_query(..., filter_expressions=True) reads them in WHERE too)" % col)
+            return col
+        tok = self.peek()
+        if tok[0] == "id" and self.peek(1) not in (("op", "("),) + _ARITH_OPS:
+            return self.take("id")  # a plain column
+        tree = self.arith_checked()
+        name = expr_name(tree)
+        if tree[0] != "col":
+            self.exprs[name] = tree
+        return name
+
     def expr_or(self):
         kids = [self.expr_and()]
         while self.kw("OR"):
@@ -621,18 +677,38 @@ class _Parser:
             self.take("id")
             return FilterContext.not_(self.expr_not())
         if self.peek() == ("op", "("):
-            self.take("op", "(")
-            e = self.expr_or()
-            self.take("op", ")")
-            return e
-        col = self.take("id")
-        if self.peek() in (("op", "("), ("op", "+"), ("op", "-"), ("op", "*"), ("op", "/")):
-            raise ValueError("expression in WHERE near %r: expressions are supported inside aggregations only" % col)
+            # a boolean group first; where that fails -- (a + b) * 2 > 3 -- the term is re-read from the same token as
+            # the arithmetic left-hand side of a comparison
+            mark, exprs = self.i, dict(self.exprs)
+            try:
+                self.take("op", "(")
+                e = self.expr_or()
+                self.take("op", ")")
+                if self.peek() in _ARITH_OPS and self.filter_expressions:
+                    raise ValueError("a boolean group is no operand of %r" % (self.peek()[1],))
+                return e
+            except ValueError as first:
+                if not self.filter_expressions:
+                    raise
+                # the error of whichever reading got further is the one about what the user wrote: a group that
+                # lacks its ")" fails at the end, its re-read as arithmetic at the first comparison inside it
+                reached = self.i
+                self.i, self.exprs = mark, exprs
+                try:
+                    return self.predicate()
+                except ValueError:
+                    if self.i > reached:
+                        raise
+                    raise first
+        return self.predicate()
+
+    def predicate(self):
+        col = self.predicate_lhs()
         if self.kw("BETWEEN"):
             self.take("id")
-            lo = self.literal()
+            lo = self.rhs_literal(col)
             self.take("id", "AND")
-            hi = self.literal()
+            hi = self.rhs_literal(col)
             return FilterContext.pred(Predicate.range(col, lo, hi, True, True))
         negate = False
         if self.kw("NOT"):
@@ -641,14 +717,14 @@ class _Parser:
         if self.kw("IN"):
             self.take("id")
             self.take("op", "(")
-            vals = [self.literal()]
+            vals = [self.rhs_literal(col)]
             while self.peek() == ("op", ","):
                 self.take("op", ",")
-                vals.append(self.literal())
+                vals.append(self.rhs_literal(col))
             self.take("op", ")")
             return FilterContext.pred(Predicate.not_in(col, vals) if negate else Predicate.in_(col, vals))
         op = self.take("op")
-        v = self.literal()
+        v = self.rhs_literal(col)
         if op == "=":
             return FilterContext.pred(Predicate.eq(col, v))
         if op in ("!=", "<>"):
@@ -664,11 +740,15 @@ class _Parser:
         raise ValueError("unsupported operator %s" % op)
 
 
-def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=False):
+def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=False, filter_expressions=False):
     """Parses `SELECT cols / aggs FROM t [WHERE ...] [GROUP BY cols] [ORDER BY expr [ASC|DESC], ...]
     [TOP n | LIMIT n]`.  Aggregations that appear only in ORDER BY are computed as well (Pinot's hidden
-    aggregations) but not selected.  exact_fp_sum: the query option of the same name (QueryContext)."""
-    p = _Parser(sql)
+    aggregations) but not selected.  exact_fp_sum: the query option of the same name (QueryContext).
+    filter_expressions: a predicate's left-hand side may be an arithmetic expression (WHERE price * qty > 1000,
+    WHERE ADD(a, b) BETWEEN 1 AND 5, IN / NOT IN; the grammar and limits of an aggregation's argument); the right-hand
+    side stays a literal.  GpuTable parses its SQL strings with it on.  The default is off only because
+    tests/test_expr_agg_cpu.py pins ValueError for such strings under the default call."""
+    p = _Parser(sql, filter_expressions)
     p.take("id", "SELECT")
     items = p.select_list()
     p.take("id", "FROM")
