@@ -315,9 +315,47 @@ typedef struct {
  * split per segment; a virtual column in GROUP BY (PGPU_ERR_INVALID_ARGUMENT: bad column).  None of this list but the
  * operand rules applies to a virtual column named by a predicate, which changes nothing after the filter.  Plans with
  * an expression aggregation never take the radix- or hash-partitioned pipelines: they are planned as with
- * pgpu_config.partitioned_group_by = 0, hash_partitions = 0 and stream_chunks = 1. */
+ * pgpu_config.partitioned_group_by = 0, hash_partitions = 0 and stream_chunks = 1.
+ *
+ * Conditional expressions -- SUM(CASE WHEN country_id = 3 THEN revenue ELSE 0 END), WHERE CASE WHEN a > 1 THEN b ELSE c
+ * END > 3: the reference's CaseTransformFunction, BinaryOperatorTransformFunction, And / OrOperatorTransformFunction and
+ * LiteralTransformFunction.  A stack entry is a number or a boolean; the program is type-checked at registration
+ * (PGPU_ERR_INVALID_ARGUMENT, "bad operand type"): arithmetic and comparisons take numbers, AND / OR booleans, SELECT
+ * (number, number, boolean), and the program leaves one number.
+ *   EQ NE GT GE LT LE  pop b, then a, push the boolean Double.compare(a, b) <op> 0: the total order of
+ *                      Double.doubleToLongBits, in which -0.0 is below +0.0 and every NaN is one value that equals itself
+ *                      and lies above +inf.  This is not the rule of a pgpu_predicate on a column, where 0.0 == -0.0.
+ *   AND OR             pop two booleans, push one; the reference's n-ary form is a left-to-right chain.
+ *   SELECT             pops cond (top), then `then`, then `else`; pushes cond ? then : else.  CASE WHEN c1 THEN r1 ..
+ *                      WHEN cN THEN rN ELSE e END is e, rN, cN, SELECT, .., r1, c1, SELECT, so the first matching WHEN
+ *                      wins (getSelectedArray) and the stack stays at 4 for any number of WHENs over simple operands.
+ *                      Every branch is evaluated for every doc; x / 0 in an unselected branch is harmless.
+ * A condition stands above the two numbers its SELECT reads, so two comparisons joined by AND / OR need a stack of 5
+ * and are refused by the depth limit: lower them to SELECTs.  WHEN c1 OR c2 THEN r is WHEN c1 THEN r WHEN c2 THEN r;
+ * WHEN c1 AND c2 THEN r ELSE e is WHEN !c1 THEN e WHEN !c2 THEN e ELSE r, where !(a > b) is a <= b in the total order.
+ * The caller's duty for literals: the evaluator is all-double, so bit parity rests on each literal being the double the
+ * reference reads.  The server sees Long.toString of an integer literal and Double.toString of a decimal one; its type
+ * is NumberUtils.createNumber of that text (commons-lang3 3.5): an integer is INT if it fits int32, else LONG if it fits
+ * int64; a decimal with at most 7 digits between the point and the E (or the end) whose float is finite and not
+ * zero-from-nonzero is FLOAT (0.1, 0.0, 2.5 and 1.0E10 are), else with at most 16 digits DOUBLE; BigInteger /
+ * BigDecimal texts, literals of more than 15 significant digits, true / false, timestamps and strings are to be
+ * declined.  The type R of a CASE (calculateResultMetadata) folds ELSE, then the THENs in order: equal types keep, INT
+ * and LONG give LONG, every other mix gives DOUBLE; an arithmetic node is DOUBLE, a nested CASE has its own R.  A THEN /
+ * ELSE literal is (double) of the literal read as R: its integer under INT / LONG, (double)(float) of it under FLOAT
+ * (all branches FLOAT: THEN 0.1 ELSE 0.0 adds 0.10000000149011612 per doc), its plain double under DOUBLE (THEN 0.1
+ * ELSE d_col adds 0.1).  A comparison's literal is read as its own type: a FLOAT one is always (double)(float) of it
+ * (d > 0.1 compares with 0.10000000149011612).  Every accepted type pair is Double.compare of the widened values
+ * (integer pairs are Integer.compare / Long.compare: the same within +-2^53).
+ * To be declined by the caller: a LONG side (column, LONG literal or LONG-typed CASE) compared with a FLOAT or DOUBLE
+ * side (the reference applies its operator twice there, BinaryOperatorTransformFunction.java:313-325, which this
+ * project does not reproduce); STRING operands; IN inside WHEN; a missing ELSE (the reference's NULL makes R a STRING); a
+ * boolean used as a number (SUM(a > 5)); a literal-only condition.  Declined at plan time (PGPU_ERR_UNSUPPORTED, the
+ * message names "expression"): a LONG column that reaches a comparison as it is -- pushed and compared, or passed on by
+ * SELECTs only -- while one of its dictionary values in a planned segment lies outside +-2^53. */
 enum pgpu_expr_opcode { PGPU_EXPR_COLUMN = 0, PGPU_EXPR_LITERAL = 1, PGPU_EXPR_ADD = 2, PGPU_EXPR_SUB = 3,
-                        PGPU_EXPR_MULT = 4, PGPU_EXPR_DIV = 5 };
+                        PGPU_EXPR_MULT = 4, PGPU_EXPR_DIV = 5,
+                        PGPU_EXPR_EQ = 6, PGPU_EXPR_NE = 7, PGPU_EXPR_GT = 8, PGPU_EXPR_GE = 9, PGPU_EXPR_LT = 10,
+                        PGPU_EXPR_LE = 11, PGPU_EXPR_AND = 12, PGPU_EXPR_OR = 13, PGPU_EXPR_SELECT = 14 };
 #define PGPU_EXPR_MAX_OPS 16
 #define PGPU_EXPR_MAX_DEPTH 4
 #define PGPU_EXPR_MAX_COLUMNS 4

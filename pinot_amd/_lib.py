@@ -32,6 +32,7 @@ PGPU_ERR_CANCELLED = -8
 
 INT, LONG, FLOAT, DOUBLE, STRING = 0, 1, 2, 3, 4
 TYPE_NAMES = {"INT": INT, "LONG": LONG, "FLOAT": FLOAT, "DOUBLE": DOUBLE, "STRING": STRING}
+TYPE_NAME_OF = {v: k for k, v in TYPE_NAMES.items()}
 FWD_FIXED_BIT, FWD_SORTED_PAIRS, FWD_RAW_FIXED = 0, 1, 2
 PRED_EQ, PRED_NOT_EQ, PRED_IN, PRED_NOT_IN, PRED_RANGE = 0, 1, 2, 3, 4
 OP_PRED, OP_AND, OP_OR, OP_NOT = 0, 1, 2, 3
@@ -96,6 +97,8 @@ class AggC(ctypes.Structure):
 
 # pgpu_expr_opcode / pgpu_expr_op: the postfix program of an expression inside an aggregation (a virtual column)
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MULT, EXPR_DIV = 0, 1, 2, 3, 4, 5
+# comparisons (Double.compare of the operands), AND / OR over their booleans, SELECT: cond ? then : else (CASE)
+EXPR_EQ, EXPR_NE, EXPR_GT, EXPR_GE, EXPR_LT, EXPR_LE, EXPR_AND, EXPR_OR, EXPR_SELECT = 6, 7, 8, 9, 10, 11, 12, 13, 14
 EXPR_MAX_OPS, EXPR_MAX_DEPTH, EXPR_MAX_COLUMNS, EXPR_MAX_PER_TABLE = 16, 4, 4, 256
 
 

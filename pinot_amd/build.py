@@ -212,6 +212,12 @@ def build_expr_check(force=False):
     return _build_header_check("expr_check", "expr_check.cpp", "expr_eval.h", force, extra=("-ffp-contract=off",))
 
 
+def build_case_check(force=False):
+    """Conditional expression programs (expr_eval.h: comparisons, AND / OR, SELECT, the type check), compiled as
+    build_expr_check compiles its tool."""
+    return _build_header_check("case_check", "case_check.cpp", "expr_eval.h", force, extra=("-ffp-contract=off",))
+
+
 def build_expr_filter_check(force=False):
     """build/expr_filter_check: tools/expr_filter_check.cpp with csrc/filter_stats.cpp -- the host code of the
     expression filter leaves (expr_leaf.h's task builder and job list, the ExpressionScanDocIdIterator replay) --

@@ -134,7 +134,10 @@ static_assert(sizeof(pgpu_expr_op) == sizeof(pgpu::ExprOpIn) && offsetof(pgpu_ex
               offsetof(pgpu_expr_op, column) == offsetof(pgpu::ExprOpIn, column), "pgpu_expr_op is ExprOpIn");
 static_assert(PGPU_EXPR_COLUMN == pgpu::EXPR_COLUMN && PGPU_EXPR_LITERAL == pgpu::EXPR_LITERAL &&
               PGPU_EXPR_ADD == pgpu::EXPR_ADD && PGPU_EXPR_SUB == pgpu::EXPR_SUB && PGPU_EXPR_MULT == pgpu::EXPR_MULT &&
-              PGPU_EXPR_DIV == pgpu::EXPR_DIV && PGPU_EXPR_MAX_OPS == pgpu::kExprMaxOps &&
+              PGPU_EXPR_DIV == pgpu::EXPR_DIV && PGPU_EXPR_EQ == pgpu::EXPR_EQ && PGPU_EXPR_NE == pgpu::EXPR_NE &&
+              PGPU_EXPR_GT == pgpu::EXPR_GT && PGPU_EXPR_GE == pgpu::EXPR_GE && PGPU_EXPR_LT == pgpu::EXPR_LT &&
+              PGPU_EXPR_LE == pgpu::EXPR_LE && PGPU_EXPR_AND == pgpu::EXPR_AND && PGPU_EXPR_OR == pgpu::EXPR_OR &&
+              PGPU_EXPR_SELECT == pgpu::EXPR_SELECT && PGPU_EXPR_MAX_OPS == pgpu::kExprMaxOps &&
               PGPU_EXPR_MAX_DEPTH == pgpu::kExprMaxDepth && PGPU_EXPR_MAX_COLUMNS == pgpu::kExprMaxCols &&
               PGPU_EXPR_MAX_PER_TABLE == pgpu::kMaxTableExprs, "the header's limits are expr_eval.h's");
 
@@ -149,11 +152,16 @@ static std::string expr_default_name(const pgpu_table_s* t, const pgpu::ExprProg
       char buf[40];
       snprintf(buf, sizeof buf, "%.17g", g.lit[arg]);
       st.push_back(buf);
+    } else if (op == pgpu::EXPR_SELECT) {  // (else, then, cond): case(cond,then,else)
+      const std::string cond = st.back(), then = st[st.size() - 2];
+      st.resize(st.size() - 2);
+      st.back() = "case(" + cond + "," + then + "," + st.back() + ")";
     } else {
+      static const char* const kFn[] = {"add", "sub", "mult", "div", "equals", "not_equals", "greater_than",
+                                        "greater_than_or_equal", "less_than", "less_than_or_equal", "and", "or"};
       const std::string b = st.back();
       st.pop_back();
-      const char* fn = op == pgpu::EXPR_ADD ? "add" : op == pgpu::EXPR_SUB ? "sub" : op == pgpu::EXPR_MULT ? "mult" : "div";
-      st.back() = std::string(fn) + "(" + st.back() + "," + b + ")";
+      st.back() = std::string(kFn[op - pgpu::EXPR_ADD]) + "(" + st.back() + "," + b + ")";
     }
   }
   return st.back();

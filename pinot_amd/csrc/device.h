@@ -1231,12 +1231,7 @@ __device__ __forceinline__ void expr_eval_group(const ExprProg& P, const SegView
         s0[i] = x[i];
       }
     } else {
-#pragma unroll
-      for (int i = 0; i < kExprStep; ++i) {
-        s0[i] = expr_apply(op, s1[i], s0[i]);
-        s1[i] = s2[i];
-        s2[i] = s3[i];
-      }
+      expr_stack_op<kExprStep>(op, s0, s1, s2, s3);
     }
   }
 #pragma unroll

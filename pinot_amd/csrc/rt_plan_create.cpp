@@ -90,6 +90,24 @@ int acquire_segments(PlanCtx& cx, const int64_t* handles, int32_t nsegs) {
   return 0;
 }
 
+// A comparison inside a program (CASE WHEN a > 1 ..) compares doubles, where the reference compares INT / LONG operands
+// as integers: the same thing within +-2^53.  A LONG column that reaches a comparison as it is (expr_compared_columns)
+// is declined where a planned segment's dictionary (sorted: its ends) goes beyond.
+int check_compared_longs(PlanCtx& cx, const ExprProg& prog) {
+  constexpr int64_t kExact = 1ll << 53;
+  const uint32_t compared = expr_compared_columns(prog);
+  for (int c = 0; c < prog.ncols; ++c) {
+    const int col = prog.col[c];
+    if (!((compared >> c) & 1u) || cx.t->types[col] != PGPU_LONG) continue;
+    for (const Segment* s : cx.P->segs) {
+      const std::vector<int64_t>& iv = s->cols[col].dict.iv;
+      if (!iv.empty() && (iv.front() < -kExact || iv.back() > kExact))
+        return fail(PGPU_ERR_UNSUPPORTED, "expression compares LONG column %d, whose values go beyond +-2^53", col);
+    }
+  }
+  return 0;
+}
+
 // The program of predicate i's virtual column vcol (ExpressionFilterOperator), copied under the table mutex as
 // plan_expr copies an aggregation's.  Operands are those of expression aggregations: dictionary columns (STRING and
 // virtual operands were refused when the expression was registered).
@@ -106,6 +124,7 @@ int bind_expr_leaf(PlanCtx& cx, int i, int vcol) {
     for (const Segment* s : P->segs)
       if (s->cols[prog.col[c]].raw)
         return fail(PGPU_ERR_UNSUPPORTED, "predicate %d: expression over raw (no-dictionary) column %d", i, prog.col[c]);
+  TRY(check_compared_longs(cx, prog));
   cx.any_raw_leaf = true;  // planned and launched as a raw-value leaf is: a docbits region per query
   return 0;
 }
@@ -270,6 +289,7 @@ int plan_expr(PlanCtx& cx, int vcol, int* out) {
         return fail(PGPU_ERR_UNSUPPORTED, "expression over raw (no-dictionary) column %d", pe.prog.col[c]);
     query_col(P, pe.prog.col[c]);
   }
+  TRY(check_compared_longs(cx, pe.prog));
   P->exprs.push_back(pe);
   *out = (int)P->exprs.size() - 1;
   return 0;

@@ -309,9 +309,13 @@ class GpuTable:
             used += [("WHERE", p.column) for p in preds]
         for fn, col in used:
             if col in exprs and col not in self.index and fn != "COUNT":
-                from .query import expr_program
+                from .query import expr_columns, expr_program
                 ops = []
-                for op, c, lit in expr_program(exprs[col]):
+                types = {n: L.TYPE_NAME_OF[t] for n, t in zip(self.names, self.types)}  # (a CASE's literals need them)
+                for c in expr_columns(exprs[col]):
+                    if c not in types:
+                        raise KeyError("unknown column %r" % c)
+                for op, c, lit in expr_program(exprs[col], types):
                     if c is not None and c not in self.index:
                         raise KeyError("unknown column %r" % c)
                     ops.append((op, self.index[c] if c is not None else 0, lit))

@@ -89,32 +89,204 @@ _EXPR_FUNCTIONS = {"ADD": "add", "PLUS": "add", "SUB": "sub", "MINUS": "sub", "M
                    "DIV": "div", "DIVIDE": "div"}
 _EXPR_OPCODE = {"add": L.EXPR_ADD, "sub": L.EXPR_SUB, "mult": L.EXPR_MULT, "div": L.EXPR_DIV}
 _EXPR_CHARS = re.compile(r"[()+\-*/]")
+_CASE_START = re.compile(r"\s*case\s+when\s", re.I)
 
 
 def is_expression(column):
     """An aggregation's argument that is no plain column name (and not COUNT's *)."""
-    return isinstance(column, str) and column != "*" and _EXPR_CHARS.search(column) is not None
+    return isinstance(column, str) and column != "*" and \
+        (_EXPR_CHARS.search(column) is not None or _CASE_START.match(column) is not None)
+
+
+# Conditional expressions (CASE WHEN clicks > 100 THEN 1 ELSE 0 END): the reference's CaseTransformFunction,
+# BinaryOperatorTransformFunction, And / OrOperatorTransformFunction and LiteralTransformFunction.  Nodes: a comparison
+# (equals(a,b) ..), ("and" / "or", [conditions]) and ("case", [when1..whenN, then1..thenN, else]) -- the reference's
+# argument order.  A literal that is a direct operand of a comparison or a THEN / ELSE is ("lit", its typed text): what
+# the server sees, Long.toString of an integer literal and Double.toString of a decimal one.
+_CMP_FUNCTIONS = {"EQUALS": "equals", "NOT_EQUALS": "not_equals", "GREATER_THAN": "greater_than",
+                  "GREATER_THAN_OR_EQUAL": "greater_than_or_equal", "LESS_THAN": "less_than",
+                  "LESS_THAN_OR_EQUAL": "less_than_or_equal"}
+_CMP_SQL = {"=": "equals", "!=": "not_equals", "<>": "not_equals", ">": "greater_than", ">=": "greater_than_or_equal",
+            "<": "less_than", "<=": "less_than_or_equal"}
+_CMP_OPCODE = {"equals": L.EXPR_EQ, "not_equals": L.EXPR_NE, "greater_than": L.EXPR_GT,
+               "greater_than_or_equal": L.EXPR_GE, "less_than": L.EXPR_LT, "less_than_or_equal": L.EXPR_LE}
+_CMP_NOT = {"equals": "not_equals", "not_equals": "equals", "greater_than": "less_than_or_equal",
+            "less_than_or_equal": "greater_than", "less_than": "greater_than_or_equal",
+            "greater_than_or_equal": "less_than"}
+_BOOL_NODES = tuple(_CMP_OPCODE) + ("and", "or")
+INT, LONG, FLOAT, DOUBLE = "INT", "LONG", "FLOAT", "DOUBLE"  # the types of section "typing" below; BOOLEAN beside them
+BOOLEAN = "BOOLEAN"
+
+
+class _Lit(str):
+    """A literal's name in arithmetic (the double's shortest form, as before) that remembers the text it was read
+    from: a comparison or a CASE branch types its literal operands by that text (0 is not 0.0)."""
+    raw = None
+
+
+def java_double_text(d):
+    """Double.toString(d) for a finite double of at most 15 significant digits (ValueError beyond: older JDKs do not
+    always print the shortest digits there): plain notation with at least one digit after the point for
+    1e-3 <= |d| < 1e7, d.dddE[-]n otherwise."""
+    if d != d or d in (float("inf"), float("-inf")):
+        raise ValueError("literal %r is not a finite number" % (d,))
+    sign, digits, exp = decimal.Decimal(repr(d)).as_tuple()
+    digits = list(digits)
+    while len(digits) > 1 and digits[-1] == 0:  # 1e22's repr is exact digits and zeros
+        digits.pop()
+        exp += 1
+    neg = "-" if repr(d).startswith("-") else ""
+    if d == 0:
+        return neg + "0.0"
+    if len(digits) > 15:
+        raise ValueError("literal %r has more than 15 significant digits: its text on the server is not certain" % (d,))
+    s = "".join(map(str, digits))
+    point = len(s) + exp  # the value is 0.s * 10^point
+    if 1e-3 <= abs(d) < 1e7:
+        if point <= 0:
+            return neg + "0." + "0" * -point + s
+        whole, frac = (s + "0" * (point - len(s)))[:point], s[point:]
+        return neg + whole + "." + (frac or "0")
+    return neg + s[0] + "." + (s[1:] or "0") + "E%d" % (point - 1)
+
+
+def typed_literal_text(raw):
+    """The text of a literal as the server sees it (RequestContextUtils.getExpression): Long.toString of an integer
+    literal, Double.toString of a decimal one.  ValueError for anything that is no number (strings, true / false)."""
+    raw = str(raw).strip()
+    if re.fullmatch(r"[+-]?\d+", raw):
+        return str(int(raw))
+    if not re.fullmatch(r"[+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?", raw):
+        raise ValueError("%r is not a numeric literal (strings, timestamps and true / false are not supported in a "
+                         "comparison or a CASE branch)" % (raw,))
+    return java_double_text(float(raw))
+
+
+def literal_type(text):
+    """NumberUtils.createNumber (commons-lang3 3.5) of a typed literal text, as LiteralTransformFunction types it: an
+    integer is INT where it fits int32, else LONG where it fits int64; a decimal with at most 7 digits between the
+    point and the E (or the end) whose float is finite and not zero-from-nonzero is FLOAT, else with at most 16 DOUBLE.
+    Everything else (BigInteger, BigDecimal) is declined."""
+    if re.fullmatch(r"-?\d+", text):
+        v = int(text)
+        if -2 ** 31 <= v < 2 ** 31:
+            return INT
+        if -2 ** 63 <= v < 2 ** 63:
+            return LONG
+        raise ValueError("integer literal %s does not fit a LONG" % text)
+    m = re.fullmatch(r"-?\d+\.(\d+)(E-?\d+)?", text)
+    if not m:
+        raise ValueError("%r is no typed literal text" % (text,))
+    d, ndec = float(text), len(m.group(1))
+    if ndec <= 7:
+        f = _f32(d)
+        if f == f and abs(f) != float("inf") and not (f == 0.0 and d != 0.0):
+            return FLOAT
+    if ndec <= 16:
+        return DOUBLE
+    raise ValueError("literal %s is a BigDecimal on the server" % text)
+
+
+def _f32(d):
+    """(double)(float)d."""
+    try:
+        return ctypes.c_float(d).value
+    except OverflowError:
+        return float("inf") if d > 0 else float("-inf")
+
+
+def _typed(arg):
+    """A comparison's or a CASE branch's direct operand: a literal becomes its typed text."""
+    if arg[0] == "col" and arg[1].lower() in ("true", "false", "null"):
+        raise ValueError("%s in a comparison or a CASE branch: boolean and NULL literals are not supported" % arg[1])
+    if arg[0] != "lit":
+        return arg
+    text = typed_literal_text(getattr(arg[1], "raw", None) or arg[1])
+    literal_type(text)  # (declines what has no type)
+    return ("lit", text)
+
+
+def _is_bool(tree):
+    return tree[0] in _BOOL_NODES
+
+
+def _number(tree, where):
+    if _is_bool(tree):
+        raise ValueError("boolean %s used as a number in %s: a condition stands after WHEN only" % (expr_name(tree), where))
+    return tree
+
+
+def cmp_node(fn, a, b):
+    """The comparison node `fn` (a canonical name) over two numbers; a literal-only condition is declined."""
+    a, b = _typed(_number(a, fn)), _typed(_number(b, fn))
+    if not expr_columns(a) and not expr_columns(b):
+        raise ValueError("literal-only condition %s(%s,%s): a condition needs a column operand" % (fn, a[1], b[1]))
+    return (fn, [a, b])
+
+
+def logic_node(fn, args):
+    """and(..) / or(..) over conditions (the reference's n-ary form)."""
+    if len(args) < 2:
+        raise ValueError("%s takes at least 2 arguments, got %d" % (fn.upper(), len(args)))
+    for a in args:
+        if not _is_bool(a):
+            raise ValueError("%s of %s: AND / OR join conditions" % (fn.upper(), expr_name(a)))
+    return (fn, list(args))
+
+
+def case_node(whens, thens, els):
+    """case(when1..whenN, then1..thenN, else).  A missing ELSE is declined: the reference's NULL there makes the
+    result a STRING."""
+    if els is None:
+        raise ValueError("CASE without ELSE: the reference's result type is then STRING, which no aggregation here reads")
+    if not whens or len(whens) != len(thens):
+        raise ValueError("CASE takes as many THENs as WHENs, and at least one")
+    for w in whens:
+        if not _is_bool(w):
+            raise ValueError("CASE WHEN %s: a WHEN takes a condition (a comparison, AND, OR)" % expr_name(w))
+    return ("case", list(whens) + [_typed(_number(t, "a THEN")) for t in thens] + [_typed(_number(els, "an ELSE"))])
+
+
+def case_parts(tree):
+    """(whens, thens, else) of a case node."""
+    n = (len(tree[1]) - 1) // 2
+    return tree[1][:n], tree[1][n:2 * n], tree[1][2 * n]
 
 
 def expr_node(fn, args):
     """The node of function `fn` (a name or SQL alias, any case) over `args`, its argument count checked."""
-    name = _EXPR_FUNCTIONS.get(fn.upper())
+    up = fn.upper()
+    if up in _CMP_FUNCTIONS:
+        if len(args) != 2:
+            raise ValueError("%s takes exactly 2 arguments, got %d" % (up, len(args)))
+        return cmp_node(_CMP_FUNCTIONS[up], args[0], args[1])
+    if up in ("AND", "OR"):
+        return logic_node(up.lower(), args)
+    if up == "CASE":
+        if len(args) % 2 == 0:
+            raise ValueError("case(when.., then.., else) takes an odd number of arguments (a missing ELSE is not "
+                             "supported), got %d" % len(args))
+        n = (len(args) - 1) // 2
+        return case_node(args[:n], args[n:2 * n], args[2 * n])
+    name = _EXPR_FUNCTIONS.get(up)
     if name is None:
         raise ValueError("unknown function %s in an aggregation's argument (ADD, SUB, MULT, DIV and their aliases "
-                         "PLUS, MINUS, TIMES, DIVIDE are supported)" % fn)
+                         "PLUS, MINUS, TIMES, DIVIDE, the comparison functions, AND, OR and CASE are supported)" % fn)
     if name in ("sub", "div") and len(args) != 2:
         raise ValueError("%s takes exactly 2 arguments, got %d" % (name.upper(), len(args)))
     if len(args) < 2:
         raise ValueError("%s takes at least 2 arguments, got %d" % (name.upper(), len(args)))
-    return (name, list(args))
+    return (name, [_number(a, name.upper()) for a in args])
 
 
 def expr_literal(text):
     """A numeric literal node: Double.parseDouble of its text, named by the double's shortest form."""
     try:
-        return ("lit", repr(float(text)))
+        name = _Lit(repr(float(text)))
     except ValueError:
         raise ValueError("%r is not a numeric literal" % (text,))
+    name.raw = str(text)
+    return ("lit", name)
 
 
 def expr_columns(tree):
@@ -132,6 +304,50 @@ def expr_columns(tree):
     return out
 
 
+def has_conditional(tree):
+    """Whether a tree holds a comparison, AND / OR or a CASE: its program then depends on the columns' types."""
+    return tree[0] not in ("col", "lit") and (tree[0] in _BOOL_NODES + ("case",) or any(has_conditional(a) for a in tree[1]))
+
+
+def _widen(a, b):
+    """calculateResultMetadata's fold of two branch types."""
+    if a == b:
+        return a
+    if {a, b} == {INT, LONG}:
+        return LONG
+    return DOUBLE
+
+
+def expr_type(tree, types):
+    """The reference's data type of a numeric tree: a column's, a typed literal's, DOUBLE of an arithmetic node, R of a
+    CASE (folded over ELSE, then the THENs in order).  types: column name -> 'INT' | 'LONG' | 'FLOAT' | 'DOUBLE' |
+    'STRING'.  STRING operands are declined."""
+    if tree[0] == "col":
+        t = types[tree[1]]
+        t = L.TYPE_NAME_OF.get(t, t) if not isinstance(t, str) else t
+        if t not in (INT, LONG, FLOAT, DOUBLE):
+            raise ValueError("expression over %s column %s" % (t, tree[1]))
+        return t
+    if tree[0] == "lit":
+        return literal_type(tree[1])
+    if tree[0] == "case":
+        _, thens, els = case_parts(tree)
+        r = expr_type(els, types)
+        for t in thens:
+            r = _widen(r, expr_type(t, types))
+        return r
+    if _is_bool(tree):
+        return BOOLEAN
+    return DOUBLE
+
+
+class _AnyDouble(dict):
+    """Column types for counting ops only (check_expr_limits): the count does not depend on them."""
+
+    def __missing__(self, key):
+        return DOUBLE
+
+
 def expr_name(tree):
     """The expression in the reference's function form: mult(price,qty), add(div(a,b),2.5)."""
     if tree[0] in ("col", "lit"):
@@ -139,17 +355,96 @@ def expr_name(tree):
     return "%s(%s)" % (tree[0], ",".join(expr_name(a) for a in tree[1]))
 
 
-def expr_program(tree):
+def _negated(cond):
+    """The condition that holds exactly where `cond` does not.  Comparisons are Double.compare's total order, so the
+    negation of a > b is a <= b for every pair of values, NaN included."""
+    if cond[0] == "and":
+        return ("or", [_negated(c) for c in cond[1]])
+    if cond[0] == "or":
+        return ("and", [_negated(c) for c in cond[1]])
+    return (_CMP_NOT[cond[0]], cond[1])
+
+
+def _literal_value(text, as_type):
+    """The double the reference reads a typed literal as under `as_type`: its integer under INT / LONG, (double)(float)
+    under FLOAT, its plain double under DOUBLE."""
+    if as_type == FLOAT:
+        return _f32(float(text))
+    if as_type in (INT, LONG) and re.fullmatch(r"-?\d+", text):
+        return float(int(text))
+    return float(text)
+
+
+def expr_program(tree, types=None):
     """The postfix program of a tree as (op, column name or None, literal) triples, all ops binary: ADD(x1..xn) is
     ((0.0 + the literal arguments in order) + v1) + v2 ... over the non-literal arguments in order, MULT likewise from
-    1.0 (AdditionTransformFunction.java:44-82, MultiplicationTransformFunction.java:34-82); SUB and DIV are a op b."""
+    1.0 (AdditionTransformFunction.java:44-82, MultiplicationTransformFunction.java:34-82); SUB and DIV are a op b.
+
+    A tree with a comparison or a CASE needs `types` (column name -> 'INT' | 'LONG' | 'FLOAT' | 'DOUBLE' | 'STRING'):
+    the value of a literal there depends on them.  A comparison is a, b, CMP with each literal read as its own type; a
+    LONG side against a FLOAT or DOUBLE side is declined.  CASE WHEN c1 THEN r1 .. ELSE e END is e, rN, cN, SELECT, ..,
+    r1, c1, SELECT with each THEN / ELSE literal read as the CASE's result type R.  A condition joined by AND / OR would
+    stand as two booleans and two operands above ELSE and THEN, a stack of 5, so it is lowered to further SELECTs that
+    choose the same branch for every doc: WHEN c1 OR c2 THEN r is WHEN c1 THEN r WHEN c2 THEN r, and WHEN c1 AND c2 THEN
+    r ELSE e is WHEN not c1 THEN e WHEN not c2 THEN e ELSE r (_negated).  Every branch is evaluated for every doc
+    anyway, so a branch emitted twice has the same bits both times."""
     ops = []
+    if types is None and has_conditional(tree):
+        raise ValueError("expression %s: the program of a comparison or a CASE depends on the column types "
+                         "(expr_program(tree, types))" % expr_name(tree))
+
+    def emit_cmp(c):
+        a, b = c[1]
+        ta, tb = expr_type(a, types), expr_type(b, types)
+        for x, y in ((ta, tb), (tb, ta)):
+            if x == LONG and y in (FLOAT, DOUBLE) and not isinstance(types, _AnyDouble):
+                raise ValueError("%s compares a LONG with a %s: the reference's result there is a known bug that is "
+                                 "not reproduced" % (expr_name(c), y))
+        for x, t in ((a, ta), (b, tb)):
+            if x[0] == "lit":
+                ops.append((L.EXPR_LITERAL, None, _literal_value(x[1], t)))
+            else:
+                emit(x)
+        ops.append((_CMP_OPCODE[c[0]], None, 0.0))
+
+    def emit_select(cond, then, els):
+        """cond ? then() : els(), the else emitted first."""
+        if cond[0] == "or":
+            rest = cond[1][1:]
+            emit_select(cond[1][0], then, lambda: emit_select(rest[0] if len(rest) == 1 else ("or", rest), then, els))
+        elif cond[0] == "and":
+            rest = cond[1][1:]
+            emit_select(_negated(cond[1][0]), els, lambda: emit_select(rest[0] if len(rest) == 1 else ("and", rest), then, els))
+        else:
+            els()
+            then()
+            emit_cmp(cond)
+            ops.append((L.EXPR_SELECT, None, 0.0))
+
+    def emit_case(t):
+        whens, thens, els = case_parts(t)
+        r = expr_type(t, types)
+
+        def branch(x):
+            if x[0] == "lit":
+                return lambda: ops.append((L.EXPR_LITERAL, None, _literal_value(x[1], r)))
+            return lambda: emit(x)
+
+        def chain(k):
+            if k == len(whens):
+                return branch(els)
+            return lambda: emit_select(whens[k], branch(thens[k]), chain(k + 1))
+        chain(0)()
 
     def emit(t):
         if t[0] == "col":
             ops.append((L.EXPR_COLUMN, t[1], 0.0))
         elif t[0] == "lit":
             ops.append((L.EXPR_LITERAL, None, float(t[1])))
+        elif t[0] == "case":
+            emit_case(t)
+        elif _is_bool(t):
+            raise ValueError("boolean %s used as a number" % expr_name(t))
         elif t[0] in ("sub", "div"):
             emit(t[1][0])
             emit(t[1][1])
@@ -159,11 +454,18 @@ def expr_program(tree):
             for a in t[1]:
                 if a[0] == "lit":
                     acc = acc + float(a[1]) if t[0] == "add" else acc * float(a[1])
+            rest = [a for a in t[1] if a[0] != "lit"]
+            # A CASE needs the whole stack.  As the first operand it is emitted before the folded literal: acc op v and
+            # v op acc are the same double (IEEE addition and multiplication commute).
+            first_below = has_conditional(rest[0])
+            if first_below:
+                emit(rest[0])
             ops.append((L.EXPR_LITERAL, None, acc))
-            for a in t[1]:
-                if a[0] != "lit":
-                    emit(a)
-                    ops.append((_EXPR_OPCODE[t[0]], None, 0.0))
+            if first_below:
+                ops.append((_EXPR_OPCODE[t[0]], None, 0.0))
+            for a in rest[first_below:]:
+                emit(a)
+                ops.append((_EXPR_OPCODE[t[0]], None, 0.0))
     emit(tree)
     return ops
 
@@ -173,13 +475,15 @@ def check_expr_limits(tree):
     evaluation stack of 4, 4 distinct columns).  Every ADD / MULT node spends one op and one stack level on its folded
     literal, so a long infix chain -- a + b + c + d + e nests four binary nodes -- is deeper than it looks: the n-ary
     form ADD(a, b, c, d, e) is one node."""
-    ops = expr_program(tree)
+    ops = expr_program(tree, _AnyDouble())  # (the count does not depend on the column types)
     depth = most = 0
     for op, _, _ in ops:
-        depth += 1 if op in (L.EXPR_COLUMN, L.EXPR_LITERAL) else -1
+        depth += 1 if op in (L.EXPR_COLUMN, L.EXPR_LITERAL) else -2 if op == L.EXPR_SELECT else -1
         most = max(most, depth)
     name = expr_name(tree)
     hint = "; the n-ary forms ADD(x1, .., xn) / MULT(x1, .., xn) take one op per argument more and no nesting"
+    if has_conditional(tree):
+        hint += "; a CASE spends ELSE, THEN and the two operands of a comparison, and four ops per comparison"
     if len(ops) > L.EXPR_MAX_OPS:
         raise ValueError("expression %s compiles to %d ops, more than %d%s" % (name, len(ops), L.EXPR_MAX_OPS, hint))
     if most > L.EXPR_MAX_DEPTH:
@@ -208,6 +512,7 @@ def parse_expression(text):
         raise ValueError("cannot parse expression %r near %r" % (text, p.peek()[1]))
     if tree[0] == "lit":
         raise ValueError("literal-only expression %s: an expression needs a column operand" % text)
+    _number(tree, "an aggregation's argument")
     _check_expr(tree)
     check_expr_limits(tree)
     return tree
@@ -588,6 +893,7 @@ class _Parser:
         tree = self.arith()
         if tree[0] == "lit":
             raise ValueError("literal-only expression %s: an expression needs a column operand" % tree[1])
+        _number(tree, "an aggregation's argument or a predicate's left-hand side")
         _check_expr(tree)
         check_expr_limits(tree)
         return tree
@@ -620,6 +926,8 @@ class _Parser:
             return expr_literal("-" + self.take("lit"))
         if tok[0] == "lit":
             return expr_literal(self.take("lit"))
+        if self.case_ahead():
+            return self.case()
         if tok[0] == "id" and self.peek(1) == ("op", "("):
             fn = self.take("id")
             self.take("op", "(")
@@ -630,6 +938,65 @@ class _Parser:
             self.take("op", ")")
             return expr_node(fn, args)
         return ("col", self.take("id"))
+
+    # ---- CASE WHEN cond THEN arith (WHEN cond THEN arith)* ELSE arith END; cond := conj (OR conj)*,
+    # conj := ctest (AND ctest)*, ctest := ( cond ) | arith cmp arith, cmp one of = != <> < <= > >=
+    def case_ahead(self):
+        return self.kw("CASE") and self.peek(1)[0] == "id" and self.peek(1)[1].upper() == "WHEN"
+
+    def case(self):
+        self.take("id", "CASE")
+        whens, thens, els = [], [], None
+        while self.kw("WHEN"):
+            self.take("id")
+            whens.append(self.cond())
+            self.take("id", "THEN")
+            thens.append(self.arith())
+        if not whens:
+            raise ValueError("CASE: WHEN expected, got %r (the simple form CASE x WHEN v is not supported)" % (self.peek(),))
+        if self.kw("ELSE"):
+            self.take("id")
+            els = self.arith()
+        self.take("id", "END")
+        return case_node(whens, thens, els)
+
+    def cond(self):
+        kids = [self.cond_and()]
+        while self.kw("OR"):
+            self.take("id")
+            kids.append(self.cond_and())
+        return kids[0] if len(kids) == 1 else logic_node("or", kids)
+
+    def cond_and(self):
+        kids = [self.cond_test()]
+        while self.kw("AND"):
+            self.take("id")
+            kids.append(self.cond_test())
+        return kids[0] if len(kids) == 1 else logic_node("and", kids)
+
+    def cond_test(self):
+        if self.peek() == ("op", "("):  # a condition in parentheses, or -- (a + b) * 2 > 3 -- an arithmetic operand
+            mark = self.i
+            try:
+                self.take("op", "(")
+                c = self.cond()
+                self.take("op", ")")
+                if self.peek() not in _ARITH_OPS and not (self.peek()[0] == "op" and self.peek()[1] in _CMP_SQL):
+                    return c
+            except ValueError:
+                pass
+            self.i = mark
+        left = self.arith()
+        if _is_bool(left):  # the function form: greater_than(a, 1), and(.., ..)
+            return left
+        if self.kw("IN", "NOT", "BETWEEN"):
+            raise ValueError("%s inside a CASE WHEN is not supported: a condition is a comparison (= != <> < <= > >=), "
+                             "AND, OR" % self.peek()[1].upper())
+        tok = self.peek()
+        if tok[0] != "op" or tok[1] not in _CMP_SQL:
+            raise ValueError("comparison expected in a CASE WHEN, got %r" % (tok,))
+        self.take("op")
+        return cmp_node(_CMP_SQL[tok[1]], left, self.arith())
 
     def rhs_literal(self, lhs):
         """A predicate's right-hand side: a literal.  After an expression a name there is a column (a * b < c), which
@@ -650,7 +1017,7 @@ class _Parser:
                                  "(parse_query(..., filter_expressions=True) reads them in WHERE too)" % col)
             return col
         tok = self.peek()
-        if tok[0] == "id" and self.peek(1) not in (("op", "("),) + _ARITH_OPS:
+        if tok[0] == "id" and self.peek(1) not in (("op", "("),) + _ARITH_OPS and not self.case_ahead():
             return self.take("id")  # a plain column
         tree = self.arith_checked()
         name = expr_name(tree)
@@ -762,6 +1129,8 @@ def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=Fal
         p.take("id")
         p.take("id", "BY")
         def group_by_column():
+            if p.case_ahead():
+                raise ValueError("expression in GROUP BY near 'CASE': expressions are supported inside aggregations only")
             col = p.take("id")
             if p.peek() in (("op", "("), ("op", "+"), ("op", "-"), ("op", "*"), ("op", "/")):
                 raise ValueError("expression in GROUP BY near %r: expressions are supported inside aggregations only" % col)
