@@ -375,6 +375,45 @@ int pgpu_table_add_expression(pgpu_table table, const pgpu_expr_op* ops, int32_t
 int pgpu_table_expression(pgpu_table table, int32_t column, pgpu_expr_op* ops, int32_t cap, int32_t* n, char* name,
                           int32_t name_cap);
 
+/* Expressions in GROUP BY -- GROUP BY CASE WHEN age < 18 THEN 0 WHEN age < 65 THEN 1 ELSE 2 END, GROUP BY a + b, GROUP
+ * BY country, clicks / impressions: the reference's NoDictionary*GroupKeyGenerator over a transform function.  A
+ * group-by expression is a *derived column* of the table: per pinned segment a dictionary and a fixed-bit forward
+ * index, what the segment creator would have written had the expression been ingested as a column.  It is built on the
+ * GPU when a plan (or one of the readers below) first names it in a segment, under the table's mutex, and kept with the
+ * segment until the segment is unpinned; pgpu_table_device_bytes counts it.  Everything after the scan's forward-index
+ * read sees an ordinary dictionary column: every group table (LDS, global, hash, partitioned), numGroupsLimit with its
+ * first-seen meaning, DISTINCTCOUNT / PERCENTILE / expression aggregations beside it, finalize, ORDER BY and the trims.
+ * pgpu_table_add_group_expression registers the program (pgpu_table_add_expression's validation and limits) with the
+ * reference's result type R of the expression -- DOUBLE for arithmetic; INT, LONG, FLOAT or DOUBLE as a CASE folds its
+ * branches -- and returns an index in a range of its own, PGPU_GROUP_EXPR_COLUMN_BASE + k, above every real column and
+ * every index pgpu_table_add_expression returns.  The identity is (program, result_type): an identical registration
+ * returns the same index.  pgpu_query.group_by[] may name the index; a predicate or an aggregation naming it is
+ * PGPU_ERR_INVALID_ARGUMENT, as a pgpu_table_add_expression column in group_by stays (bad column).
+ * Values: the evaluator's double per doc, read as R -- the integer of it under INT / LONG, the float under FLOAT (the
+ * double is (double)(float) of one by construction), the double itself under DOUBLE.  Two docs share a group iff their
+ * values have the same bits in the dictionaries' order (Double.doubleToLongBits, as the reference's
+ * Double2IntOpenHashMap compares): -0.0 and +0.0 are two groups, every NaN is one group that sorts above +inf.  The
+ * result's key column has type R (pgpu_result_key_dictionary*) and is named by the expression's function form.
+ * numEntriesScannedPostFilter counts the distinct real columns the query projects -- the operands of group-by
+ * expressions among them, the derived column itself not.  A segment carrying a star-tree is scanned for such a query.
+ * Readers that accept the index (and build the derived column of that segment on first use):
+ * pgpu_segment_column_info / _bytes, pgpu_read_dict_ids, pgpu_table_dictionary_size / _i64 / _f64.
+ * Declined with PGPU_ERR_UNSUPPORTED (the message names "GROUP BY expression"): a STRING operand (at registration); a
+ * raw (no-dictionary) operand in a planned segment; a product of the operands' dictionary sizes in a planned segment
+ * above PGPU_GROUP_EXPR_MAX_PRODUCT (the candidate values are enumerated over it); R = LONG with an operand LONG column
+ * whose dictionary in a planned segment leaves +-2^53 (a LONG operand that reaches a comparison as it is likewise, as
+ * in an aggregation's CASE); an external d_table (pgpu_plan_create_execute, pgpu_plan_execute, pgpu_plan_finalize);
+ * every cross-GPU or key-range entry point -- pgpu_plan_finalize_range, pgpu_plan_exchange_*, pgpu_result_exchange_rows
+ * / _merge_rows, pgpu_plan_combine_mode, pgpu_plan_combine, pgpu_result_combine_rows: a derived dictionary belongs to
+ * one table on one rank, and merging them is not built.  pgpu_result_datatable is made (values travel in it, not
+ * dictIds).  No group-table path is declined on account of a derived column.  At most PGPU_GROUP_EXPR_MAX_PER_TABLE
+ * expressions per table (PGPU_ERR_INVALID_ARGUMENT). */
+#define PGPU_GROUP_EXPR_COLUMN_BASE (1 << 20)
+#define PGPU_GROUP_EXPR_MAX_PER_TABLE 64
+#define PGPU_GROUP_EXPR_MAX_PRODUCT (1 << 22)
+int pgpu_table_add_group_expression(pgpu_table table, const pgpu_expr_op* ops, int32_t n, const char* name,
+                                    int32_t result_type /* PGPU_INT .. PGPU_DOUBLE */, int32_t* column);
+
 typedef struct {
   int32_t num_predicates;
   int32_t num_filter_ops;     /* 0 = no filter (MatchAllFilterOperator) */

@@ -100,6 +100,9 @@ EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MULT, EXPR_DIV = 0, 1, 2, 3,
 # comparisons (Double.compare of the operands), AND / OR over their booleans, SELECT: cond ? then : else (CASE)
 EXPR_EQ, EXPR_NE, EXPR_GT, EXPR_GE, EXPR_LT, EXPR_LE, EXPR_AND, EXPR_OR, EXPR_SELECT = 6, 7, 8, 9, 10, 11, 12, 13, 14
 EXPR_MAX_OPS, EXPR_MAX_DEPTH, EXPR_MAX_COLUMNS, EXPR_MAX_PER_TABLE = 16, 4, 4, 256
+# group-by expressions (pgpu_table_add_group_expression): their column indexes start here; per table; the cap on the
+# product of the operands' segment-local dictionary sizes
+GROUP_EXPR_COLUMN_BASE, GROUP_EXPR_MAX_PER_TABLE, GROUP_EXPR_MAX_PRODUCT = 1 << 20, 64, 1 << 22
 
 
 class ExprOpC(ctypes.Structure):
@@ -211,6 +214,7 @@ _PROTOS = {
     "pgpu_table_get_config": (c_int, [c_voidp, ctypes.POINTER(ConfigC)]),
     "pgpu_table_destroy": (c_int, [c_voidp]),
     "pgpu_table_add_expression": (c_int, [c_voidp, ctypes.POINTER(ExprOpC), c_i32, ctypes.c_char_p, c_i32p]),
+    "pgpu_table_add_group_expression": (c_int, [c_voidp, ctypes.POINTER(ExprOpC), c_i32, ctypes.c_char_p, c_i32, c_i32p]),
     "pgpu_table_expression": (c_int, [c_voidp, c_i32, ctypes.POINTER(ExprOpC), c_i32, c_i32p, ctypes.c_char_p, c_i32]),
     "pgpu_pin_segment": (c_int, [c_voidp, ctypes.POINTER(SegmentDesc), c_i64p]),
     "pgpu_unpin_segment": (c_int, [c_voidp, c_i64]),

@@ -18,14 +18,14 @@ RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_plan_create", "rt_exec", "rt_fin
 SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTIME] + [("startree.cpp", [], "startree"),
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
            ("k_partition.hip", [], "k_partition"), ("k_partition_fx.hip", [], "k_partition_fx"),
-           ("k_hashfinal.hip", [], "k_hashfinal")] + \
+           ("k_hashfinal.hip", [], "k_hashfinal"), ("k_derive.hip", [], "k_derive")] + \
     [("k_%s.hip" % k, ["-DPGPU_FAMILY=%d" % f, "-DPGPU_MODE=%d" % m], "k_%s%s_%d" % (k, ("", "_fx", "_dc", "_hist", "_expr")[f], m))
      for k, f, modes in (("direct", 0, 3), ("startree", 0, 3), ("direct", 1, 3), ("startree", 1, 3), ("direct", 2, 2),
                          ("direct", 3, 2), ("direct", 4, 3))
      for m in range(modes)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "derive.h", "group_expr.h", "scan_direct_body.inc", "part_aggregate_body.inc",
            "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
@@ -216,6 +216,13 @@ def build_case_check(force=False):
     """Conditional expression programs (expr_eval.h: comparisons, AND / OR, SELECT, the type check), compiled as
     build_expr_check compiles its tool."""
     return _build_header_check("case_check", "case_check.cpp", "expr_eval.h", force, extra=("-ffp-contract=off",))
+
+
+def build_group_expr_check(force=False):
+    """The host steps of a derived column's build (group_expr.h: sort-unique, used-compaction, remap, bits), with the
+    keys of expr_eval.h."""
+    return _build_header_check("group_expr_check", "group_expr_check.cpp", "group_expr.h", force,
+                               extra=("-ffp-contract=off",))
 
 
 def build_expr_filter_check(force=False):

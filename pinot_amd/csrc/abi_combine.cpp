@@ -8,6 +8,7 @@ namespace {
 int exchangeable(pgpu_plan P) {
   if (!P) return fail(PGPU_ERR_INVALID_ARGUMENT, "null plan");
   if (plan_has_percentile(P)) return percentile_decline("a cross-GPU exchange");
+  if (plan_has_group_expr(P)) return group_expr_decline("a cross-GPU exchange");
   if (plan_has_distinct(P)) return distinct_decline("a cross-GPU exchange");
   if (P->composite) return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit plan: exchange its finalized result rows");
   if (!P->hash) return fail(PGPU_ERR_UNSUPPORTED, "dense group tables merge element-wise (all-reduce / reduce-scatter)");
@@ -195,6 +196,7 @@ int pgpu_result_exchange_rows(pgpu_result r, int32_t nparts, const int32_t* kind
   if (!r || nparts < 1 || nparts > (1 << 20) || !counts || (r->n > 0 && !rows))
     return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (result_has_percentile(r)) return percentile_decline("a cross-GPU exchange of rows");
+  if (result_has_group_expr(r)) return group_expr_decline("a cross-GPU exchange of rows");
   if (result_has_distinct(r)) return distinct_decline("a cross-GPU exchange of rows");
   TRY(fx_rows_ready(r, "a cross-GPU exchange of rows"));
   if ((int)r->slot_kind.size() != r->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
@@ -231,6 +233,7 @@ int pgpu_result_merge_rows(pgpu_result tmpl, const int64_t* rows, int64_t n, con
   PGPU_ABI_GUARD;
   if (!tmpl || !out || n < 0 || (n > 0 && !rows)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (result_has_percentile(tmpl)) return percentile_decline("a cross-GPU merge of rows");
+  if (result_has_group_expr(tmpl)) return group_expr_decline("a cross-GPU merge of rows");
   if (result_has_distinct(tmpl)) return distinct_decline("a cross-GPU merge of rows");
   TRY(fx_rows_ready(tmpl, "a cross-GPU merge of rows"));
   if ((int)tmpl->slot_kind.size() != tmpl->num_slots) return fail(PGPU_ERR_UNSUPPORTED, "result without slot kinds");
@@ -644,6 +647,7 @@ int pgpu_plan_combine_mode(pgpu_plan P, pgpu_comm c, int64_t shard_bytes, int32_
   if (!P || !c || !mode) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
   if (plan_has_percentile(P)) return percentile_decline("a cross-GPU combine");  // (... and the function)
+  if (plan_has_group_expr(P)) return group_expr_decline("a cross-GPU combine");
   pgpu::CommWaitScope wait_limits(P->end_time_ms, &P->cancel);
   const int N = c->impl->nranks;
   int local;
@@ -715,6 +719,7 @@ int pgpu_plan_combine(pgpu_plan P, pgpu_comm c, void* stream, void* d_table, int
   if (!P || !c) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (plan_fx_local(P)) return fx_decline("a cross-GPU combine");  // every rank's query carries the option
   if (plan_has_percentile(P)) return percentile_decline("a cross-GPU combine");  // (... and the function)
+  if (plan_has_group_expr(P)) return group_expr_decline("a cross-GPU combine");
   // DISTINCTCOUNT: the side bitmaps belong to the plan's own table (a caller table is declined at execute already)
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");  // (every rank passes one or none)
   if (d_table && plan_has_expr(P)) return expr_decline("external table");
@@ -868,6 +873,7 @@ int pgpu_result_combine_rows(pgpu_result r, pgpu_comm c, pgpu_result* out) try {
   if (!r || !c || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (result_fx_local(r)) return fx_decline("a cross-GPU combine of rows");  // every rank's query carries the option
   if (result_has_percentile(r)) return percentile_decline("a cross-GPU combine of rows");
+  if (result_has_group_expr(r)) return group_expr_decline("a cross-GPU combine of rows");
   if (result_has_distinct(r)) return distinct_decline("a cross-GPU combine of rows");
   pgpu::Comm* C = c->impl.get();
   const int N = C->nranks, me = C->rank;

@@ -218,27 +218,33 @@ int pgpu_table_add_dictionary_values(pgpu_table t, int col, int64_t n, const int
 
 int pgpu_table_dictionary_size(pgpu_table t, int col, int64_t* size) try {
   PGPU_ABI_GUARD;
-  if (!t || !size || col < 0 || col >= (int)t->names.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (!t || !size) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard g(t->device);
   std::lock_guard<std::mutex> lk(t->mu);
-  *size = (int64_t)t->global[col]->size();
+  TRY(table_reader_dict(t, col));
+  *size = (int64_t)t->col_global(col)->size();
   return 0;
 } PGPU_ABI_CATCH
 
 int pgpu_table_dictionary_i64(pgpu_table t, int col, int64_t* out) try {
   PGPU_ABI_GUARD;
-  if (!t || !out || col < 0 || col >= (int)t->names.size() || !is_int_type(t->types[col]))
-    return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (!t || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard g(t->device);
   std::lock_guard<std::mutex> lk(t->mu);
-  std::copy(t->global[col]->iv.begin(), t->global[col]->iv.end(), out);
+  TRY(table_reader_dict(t, col));
+  if (!is_int_type(t->col_type(col))) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  std::copy(t->col_global(col)->iv.begin(), t->col_global(col)->iv.end(), out);
   return 0;
 } PGPU_ABI_CATCH
 
 int pgpu_table_dictionary_f64(pgpu_table t, int col, double* out) try {
   PGPU_ABI_GUARD;
-  if (!t || !out || col < 0 || col >= (int)t->names.size() || !is_fp_type(t->types[col]))
-    return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (!t || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard g(t->device);
   std::lock_guard<std::mutex> lk(t->mu);
-  std::copy(t->global[col]->dv.begin(), t->global[col]->dv.end(), out);
+  TRY(table_reader_dict(t, col));
+  if (!is_fp_type(t->col_type(col))) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  std::copy(t->col_global(col)->dv.begin(), t->col_global(col)->dv.end(), out);
   return 0;
 } PGPU_ABI_CATCH
 
@@ -266,13 +272,14 @@ int pgpu_read_dict_ids(pgpu_table t, int64_t h, int col, const int32_t* docs, in
   if (!t || (n > 0 && (!docs || !out))) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   DeviceGuard g(t->device);
   std::shared_ptr<Segment> s;
+  const Column* cp = nullptr;
   {
     std::lock_guard<std::mutex> lk(t->mu);
     auto it = t->segments.find(h);
     if (it == t->segments.end()) return fail(PGPU_ERR_NOT_FOUND, "unknown segment handle");
     s = it->second;
+    TRY(segment_column(t, *s, col, &cp));
   }
-  if (col < 0 || col >= (int)s->cols.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad column");
   if (n <= 0) return 0;
   for (int32_t i = 0; i < n; ++i)
     if (docs[i] < 0 || docs[i] >= s->num_docs) return fail(PGPU_ERR_INVALID_ARGUMENT, "docId %d out of range", docs[i]);
@@ -280,7 +287,7 @@ int pgpu_read_dict_ids(pgpu_table t, int64_t h, int col, const int32_t* docs, in
   HIP_TRY(hipMallocAsync((void**)&d_docs, (size_t)n * 4, t->stream));
   HIP_TRY(hipMallocAsync((void**)&d_out, (size_t)n * 4, t->stream));
   HIP_TRY(hipMemcpyAsync(d_docs, docs, (size_t)n * 4, hipMemcpyHostToDevice, t->stream));
-  if (launch_gather_ids(s->cols[col].d_fwd, s->cols[col].bits, d_docs, n, d_out, t->stream))
+  if (launch_gather_ids(cp->d_fwd, cp->bits, d_docs, n, d_out, t->stream))
     return fail(PGPU_ERR_DEVICE, "gather launch failed");
   HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, t->stream));
   HIP_TRY(hipFreeAsync(d_docs, t->stream));
@@ -484,6 +491,7 @@ int pgpu_plan_create_execute(pgpu_table t, const int64_t* handles, int32_t nsegs
   if (d_table && (q->options & PGPU_OPT_EXACT_FP_SUM))
     return fail(PGPU_ERR_UNSUPPORTED, "external table with PGPU_OPT_EXACT_FP_SUM: ranks would have to agree on the fixed-point format first");
   if (d_table && query_has_percentile(q)) return percentile_decline("external table");
+  if (d_table && query_has_group_expr(q)) return group_expr_decline("external table");
   if (d_table && query_has_distinct(q)) return distinct_decline("external table");
   StreamExec se;
   se.stream = stream ? reinterpret_cast<hipStream_t>(stream) : t->stream;
@@ -531,6 +539,7 @@ int pgpu_plan_execute(pgpu_plan P, void* stream, void* d_table) try {
   if (P->hash && d_table) return fail(PGPU_ERR_UNSUPPORTED, "external table with a hash-mode plan");
   if (d_table && plan_fx_local(P)) return fx_decline("external table");
   if (d_table && plan_has_percentile(P)) return percentile_decline("external table");
+  if (d_table && plan_has_group_expr(P)) return group_expr_decline("external table");
   if (d_table && plan_has_expr(P)) return expr_decline("external table");
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");
   DeviceGuard g(P->table->device);
@@ -543,6 +552,7 @@ int pgpu_plan_finalize(pgpu_plan P, void* stream, const void* d_table, pgpu_resu
   if (!P || !out) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (d_table && plan_fx_local(P)) return fx_decline("external table");
   if (d_table && plan_has_percentile(P)) return percentile_decline("external table");
+  if (d_table && plan_has_group_expr(P)) return group_expr_decline("external table");
   if (d_table && plan_has_expr(P)) return expr_decline("external table");
   if (d_table && plan_has_distinct(P)) return distinct_decline("external table");
   DeviceGuard g(P->table->device);
@@ -569,6 +579,7 @@ int pgpu_plan_finalize_range(pgpu_plan P, void* stream, const void* d_table_shar
   if (P->hash) return fail(PGPU_ERR_UNSUPPORTED, "hash-mode group tables are not key-range shardable");
   if (plan_fx_local(P)) return fx_decline("a key-range shard");
   if (plan_has_percentile(P)) return percentile_decline("a key-range shard");
+  if (plan_has_group_expr(P)) return group_expr_decline("a key-range shard");
   if (plan_has_distinct(P)) return distinct_decline("a key-range shard");
   if (P->composite)
     return fail(PGPU_ERR_UNSUPPORTED, "numGroupsLimit below the key space: finalize the whole table");

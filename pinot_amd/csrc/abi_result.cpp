@@ -429,11 +429,13 @@ int pgpu_segment_column_info(pgpu_table t, int64_t h, int col, int32_t* card, in
                              int64_t* fwd_len) try {
   PGPU_ABI_GUARD;
   if (!t) return fail(PGPU_ERR_INVALID_ARGUMENT, "null table");
+  DeviceGuard g(t->device);  // (a derived column is built on first use)
   std::lock_guard<std::mutex> lk(t->mu);
   auto it = t->segments.find(h);
   if (it == t->segments.end()) return fail(PGPU_ERR_NOT_FOUND, "unknown segment handle");
-  if (col < 0 || col >= (int)it->second->cols.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad column");
-  const Column& c = it->second->cols[col];
+  const Column* cp = nullptr;
+  TRY(segment_column(t, *it->second, col, &cp));
+  const Column& c = *cp;
   if (card) *card = c.card;
   if (bits) *bits = c.bits;
   if (dict_len) *dict_len = (int64_t)c.raw_dict.size();
@@ -446,14 +448,15 @@ int pgpu_segment_column_bytes(pgpu_table t, int64_t h, int col, uint8_t* dict_ou
   if (!t) return fail(PGPU_ERR_INVALID_ARGUMENT, "null table");
   DeviceGuard g(t->device);
   std::shared_ptr<Segment> s;
+  const Column* cp = nullptr;
   {
     std::lock_guard<std::mutex> lk(t->mu);
     auto it = t->segments.find(h);
     if (it == t->segments.end()) return fail(PGPU_ERR_NOT_FOUND, "unknown segment handle");
     s = it->second;
+    TRY(segment_column(t, *s, col, &cp));
   }
-  if (col < 0 || col >= (int)s->cols.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad column");
-  const Column& c = s->cols[col];
+  const Column& c = *cp;
   if (dict_out && !c.raw_dict.empty()) memcpy(dict_out, c.raw_dict.data(), c.raw_dict.size());
   if (fwd_out && c.fwd_bytes > 0) {
     HIP_TRY(hipMemcpyAsync(fwd_out, c.d_fwd, (size_t)c.fwd_bytes, hipMemcpyDeviceToHost, t->stream));

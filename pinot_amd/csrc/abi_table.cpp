@@ -74,6 +74,13 @@ int pgpu_table_create(int device, int num_columns, const char* const* names, con
     if (types[i] < PGPU_INT || types[i] > PGPU_STRING) return fail(PGPU_ERR_INVALID_ARGUMENT, "column %d: bad type", i);
   auto t = std::make_unique<pgpu_table_s>();
   t->device = device;
+  // room for the group expressions' slots (pgpu_table_s::col_slot): a registration never moves the vectors that
+  // planning threads index without the table mutex
+  t->types.reserve((size_t)num_columns + kMaxGroupExprs);
+  t->global.reserve((size_t)num_columns + kMaxGroupExprs);
+  t->global_version.reserve((size_t)num_columns + kMaxGroupExprs);
+  t->gvalues.reserve((size_t)num_columns + kMaxGroupExprs);
+  t->gexprs.reserve(kMaxGroupExprs);
   for (int i = 0; i < num_columns; ++i) {
     t->names.push_back(names && names[i] ? names[i] : ("col" + std::to_string(i)));
     t->types.push_back(types[i]);
@@ -167,6 +174,73 @@ static std::string expr_default_name(const pgpu_table_s* t, const pgpu::ExprProg
   return st.back();
 }
 
+// (under the table mutex) the operand rules of a registered program: real columns that are no STRING.  `what` names the
+// kind in the messages ("expression", "GROUP BY expression").
+static int check_expr_operands(const pgpu_table_s* t, const pgpu::ExprProg& prog, const char* what) {
+  const int ncols = (int)t->names.size();
+  // (a virtual operand before a bad index: at or above the real columns it is either, and the caller meant the former)
+  for (int c = 0; c < prog.ncols; ++c) {
+    const int col = prog.col[c];
+    if (col >= ncols && col < ncols + (int)t->exprs.size())
+      return fail(PGPU_ERR_UNSUPPORTED, "%s over virtual column %d: an operand is a real column", what, col);
+    if (col >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "%s: bad column %d", what, col);
+    if (t->types[col] == PGPU_STRING)
+      return fail(PGPU_ERR_UNSUPPORTED, "%s over STRING column %d (%s)", what, col, t->names[col].c_str());
+  }
+  return 0;
+}
+
+// The program as registered, for the identity test: only the fields an op reads count.
+static std::vector<pgpu::ExprOpIn> normalized_ops(const pgpu::ExprOpIn* in, int32_t n) {
+  std::vector<pgpu::ExprOpIn> ops(in, in + n);
+  for (pgpu::ExprOpIn& o : ops) {
+    if (o.op != pgpu::EXPR_COLUMN) o.column = 0;
+    if (o.op != pgpu::EXPR_LITERAL) o.literal = 0.0;
+  }
+  return ops;
+}
+static bool same_ops(const std::vector<pgpu::ExprOpIn>& x, const std::vector<pgpu::ExprOpIn>& y) {
+  auto same = [](const pgpu::ExprOpIn& a, const pgpu::ExprOpIn& b) {
+    return a.op == b.op && a.column == b.column && pgpu::bits_of_double(a.literal) == pgpu::bits_of_double(b.literal);
+  };
+  return x.size() == y.size() && std::equal(x.begin(), x.end(), y.begin(), same);
+}
+
+int pgpu_table_add_group_expression(pgpu_table t, const pgpu_expr_op* ops, int32_t n, const char* name,
+                                    int32_t result_type, int32_t* column) try {
+  PGPU_ABI_GUARD;
+  if (!t || !column) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (result_type < PGPU_INT || result_type > PGPU_DOUBLE)
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "GROUP BY expression: result type %d is none of INT, LONG, FLOAT, DOUBLE", result_type);
+  pgpu_table_s::GroupExpr e;
+  const pgpu::ExprOpIn* in = reinterpret_cast<const pgpu::ExprOpIn*>(ops);
+  if (const int rc = pgpu::expr_compile(in, n, &e.prog))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "GROUP BY expression: %s", pgpu::expr_error_text(rc));
+  std::lock_guard<std::mutex> g(t->mu);
+  TRY(check_expr_operands(t, e.prog, "GROUP BY expression"));
+  e.ops = normalized_ops(in, n);
+  e.type = result_type;
+  for (size_t i = 0; i < t->gexprs.size(); ++i)
+    if (t->gexprs[i].type == e.type && same_ops(t->gexprs[i].ops, e.ops)) {
+      *column = kGroupExprBase + (int32_t)i;
+      return 0;
+    }
+  if ((int)t->gexprs.size() >= kMaxGroupExprs)
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "GROUP BY expression: the table already has %d of them", kMaxGroupExprs);
+  e.name = name && *name ? std::string(name) : expr_default_name(t, e.prog);
+  // what the table keeps per column (pgpu_table_s::col_slot): type, global dictionary and version, value arrays
+  auto d = std::make_shared<Dict>();
+  d->type = result_type;
+  d->id = g_dict_ids.fetch_add(1);
+  t->types.push_back(result_type);
+  t->global.push_back(std::move(d));
+  t->global_version.push_back(0);
+  t->gvalues.emplace_back();
+  t->gexprs.push_back(std::move(e));
+  *column = kGroupExprBase + (int32_t)t->gexprs.size() - 1;
+  return 0;
+} PGPU_ABI_CATCH
+
 int pgpu_table_add_expression(pgpu_table t, const pgpu_expr_op* ops, int32_t n, const char* name, int32_t* column) try {
   PGPU_ABI_GUARD;
   if (!t || !column) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
@@ -175,26 +249,11 @@ int pgpu_table_add_expression(pgpu_table t, const pgpu_expr_op* ops, int32_t n, 
   const pgpu::ExprOpIn* in = reinterpret_cast<const pgpu::ExprOpIn*>(ops);
   if (const int rc = pgpu::expr_compile(in, n, &e.prog))
     return fail(PGPU_ERR_INVALID_ARGUMENT, "expression: %s", pgpu::expr_error_text(rc));
-  // (a virtual operand before a bad index: at or above the real columns it is either, and the caller meant the former)
   std::lock_guard<std::mutex> g(t->mu);
-  for (int c = 0; c < e.prog.ncols; ++c) {
-    const int col = e.prog.col[c];
-    if (col >= ncols && col < ncols + (int)t->exprs.size())
-      return fail(PGPU_ERR_UNSUPPORTED, "expression over virtual column %d: an operand is a real column", col);
-    if (col >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "expression: bad column %d", col);
-    if (t->types[col] == PGPU_STRING)
-      return fail(PGPU_ERR_UNSUPPORTED, "expression over STRING column %d (%s)", col, t->names[col].c_str());
-  }
-  e.ops.assign(in, in + n);
-  for (pgpu::ExprOpIn& o : e.ops) {  // only the fields the op reads count
-    if (o.op != pgpu::EXPR_COLUMN) o.column = 0;
-    if (o.op != pgpu::EXPR_LITERAL) o.literal = 0.0;
-  }
-  auto same = [](const pgpu::ExprOpIn& a, const pgpu::ExprOpIn& b) {
-    return a.op == b.op && a.column == b.column && pgpu::bits_of_double(a.literal) == pgpu::bits_of_double(b.literal);
-  };
+  TRY(check_expr_operands(t, e.prog, "expression"));
+  e.ops = normalized_ops(in, n);
   for (size_t i = 0; i < t->exprs.size(); ++i)
-    if (t->exprs[i].ops.size() == e.ops.size() && std::equal(e.ops.begin(), e.ops.end(), t->exprs[i].ops.begin(), same)) {
+    if (same_ops(t->exprs[i].ops, e.ops)) {
       *column = ncols + (int32_t)i;
       return 0;
     }

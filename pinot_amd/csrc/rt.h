@@ -267,6 +267,13 @@ constexpr int kExprColumnBase = -16;
 inline int expr_tcol(int e) { return kExprColumnBase - e; }
 inline bool is_expr_tcol(int c) { return c <= kExprColumnBase; }
 
+// Column indexes of group-by expressions (pgpu_table_add_group_expression): kGroupExprBase + k, above every real and
+// virtual column.
+constexpr int kGroupExprBase = PGPU_GROUP_EXPR_COLUMN_BASE;
+constexpr int kMaxGroupExprs = PGPU_GROUP_EXPR_MAX_PER_TABLE;
+constexpr int64_t kGroupExprMaxProduct = PGPU_GROUP_EXPR_MAX_PRODUCT;
+inline bool is_group_expr_col(int c) { return c >= kGroupExprBase; }
+
 inline bool is_int_type(int t) { return t == PGPU_INT || t == PGPU_LONG; }
 inline bool is_fp_type(int t) { return t == PGPU_FLOAT || t == PGPU_DOUBLE; }
 
@@ -413,6 +420,15 @@ struct Segment {
   int32_t num_docs = 0;
   void* d_block = nullptr;
   std::vector<Column> cols;
+  // Derived columns of group-by expressions (pgpu_table_add_group_expression): entry k is the column of the table's
+  // group expression k in this segment -- a dictionary and a fixed-bit forward index of its own allocation
+  // (ensure_derived, rt_dict.cpp), null until a plan or a reader first names it.  Built and installed under the table
+  // mutex and never replaced or removed while the segment lives, so a plan reads the ones it ensured without the lock.
+  std::array<std::unique_ptr<Column>, PGPU_GROUP_EXPR_MAX_PER_TABLE> derived;
+  // Column index -> the column of this segment: a real column, or the derived column of a group expression (which
+  // must have been built: ensure_derived).
+  Column& col(int c) { return is_group_expr_col(c) ? *derived[c - kGroupExprBase] : cols[c]; }
+  const Column& col(int c) const { return is_group_expr_col(c) ? *derived[c - kGroupExprBase] : cols[c]; }
   std::unique_ptr<StarTreeDev> star;
   Segment() = default;
   Segment(const Segment&) = delete;
@@ -421,6 +437,12 @@ struct Segment {
     for (auto& c : cols) {
       if (c.d_key) hipFree(c.d_key);
       if (c.d_val) hipFree(c.d_val);
+    }
+    for (auto& d : derived) {
+      if (!d) continue;
+      if (d->d_fwd) hipFree(d->d_fwd);
+      if (d->d_key) hipFree(d->d_key);
+      if (d->d_val) hipFree(d->d_val);
     }
     if (d_block) hipFree(d_block);
     if (star && star->d_block) hipFree(star->d_block);
@@ -576,6 +598,27 @@ struct pgpu_table_s {
     std::string name;
   };
   std::vector<Expr> exprs;
+  // Group-by expressions (pgpu_table_add_group_expression): expression k is column kGroupExprBase + k, a dictionary
+  // column of type `type` whose per-segment form is Segment::derived[k].  The table keeps for it what it keeps per
+  // real column: the global dictionary snapshot, its version and the global value arrays.  Under mu; never removed.
+  struct GroupExpr {
+    pgpu::ExprProg prog;
+    std::vector<pgpu::ExprOpIn> ops;
+    std::string name;
+    int32_t type = PGPU_DOUBLE;
+  };
+  std::vector<GroupExpr> gexprs;
+  // Column index -> its slot in types / global / global_version / gvalues: real columns first, then the group
+  // expressions (the vectors grow by one per registration; names keeps the real columns only).
+  int col_slot(int c) const { return is_group_expr_col(c) ? (int)names.size() + (c - kGroupExprBase) : c; }
+  // a real column, or a registered group expression (under mu)
+  bool has_dict_col(int c) const {
+    return c >= 0 && (c < (int)names.size() || (is_group_expr_col(c) && c - kGroupExprBase < (int)gexprs.size()));
+  }
+  int32_t col_type(int c) const { return types[col_slot(c)]; }
+  std::shared_ptr<const Dict>& col_global(int c) { return global[col_slot(c)]; }
+  uint64_t& col_global_version(int c) { return global_version[col_slot(c)]; }
+  const std::string& col_name(int c) const { return is_group_expr_col(c) ? gexprs[c - kGroupExprBase].name : names[c]; }
   std::unordered_map<int64_t, std::shared_ptr<Segment>> segments;
   std::vector<std::shared_ptr<Segment>> by_handle;  // handle -> segment (handles are dense), null once unpinned
   int64_t next_handle = 1;
@@ -590,6 +633,7 @@ struct pgpu_table_s {
     int64_t n = 0;  // entries of the current arrays (device_bytes holds 16 n for them)
   };
   std::vector<GlobalValues> gvalues;
+  GlobalValues& col_gvalues(int c) { return gvalues[col_slot(c)]; }
   hipStream_t stream = nullptr;
   std::vector<std::unique_ptr<Scratch>> scratch_pool;
   GenScratch gen;
@@ -676,6 +720,15 @@ struct pgpu_plan_s {
   bool pure_and = false;
   int max_depth = 0;
   std::vector<int32_t> key_cols;          // table columns of group-by expressions
+  // Group-by expressions among key_cols (columns at or above kGroupExprBase): their derived columns were built for
+  // every plan segment when the query's columns were bound; operands: the real columns the expression reads
+  // (numEntriesScannedPostFilter counts those, not the derived column).  The flag the cross-GPU and external-merge
+  // entry points check (plan_has_group_expr).
+  struct GroupExprRef {
+    int32_t col = 0;
+    std::vector<int32_t> operands;
+  };
+  std::vector<GroupExprRef> group_exprs;
   std::vector<std::shared_ptr<const Dict>> key_dicts;  // global dictionary snapshots the key space is built on
   std::vector<int64_t> key_card;          // key digit ranges (global cardinalities, or the filter's bound)
   std::vector<int64_t> key_off;           // first global id of each key digit (filter-restricted key spaces)
@@ -960,6 +1013,27 @@ inline bool result_has_percentile(const pgpu_result_s* r) {
 inline int percentile_decline(const char* what) {
   return fail(PGPU_ERR_UNSUPPORTED, "%s with PERCENTILE: per-rank percentiles do not merge (the value histograms would "
                          "have to be added)", what);
+}
+// Plans / results grouped by an expression (a derived column): every cross-GPU or external-merge entry point declines
+// them, where it declines PERCENTILE -- each rank's derived dictionary holds the values its own segments produced, and
+// merging them across ranks is not built.
+inline bool query_has_group_expr(const pgpu_query* q) {
+  for (int i = 0; q && q->group_by && i < q->num_group_by; ++i)
+    if (is_group_expr_col(q->group_by[i])) return true;
+  return false;
+}
+inline bool plan_has_group_expr(const pgpu_plan_s* P) {
+  if (!P->group_exprs.empty()) return true;
+  for (const auto& part : P->parts)
+    if (part.plan && !part.plan->group_exprs.empty()) return true;
+  return false;
+}
+inline bool result_has_group_expr(const pgpu_result_s* r) {
+  return std::any_of(r->key_cols.begin(), r->key_cols.end(), [](int32_t c) { return is_group_expr_col(c); });
+}
+inline int group_expr_decline(const char* what) {
+  return fail(PGPU_ERR_UNSUPPORTED, "%s with a GROUP BY expression: a derived dictionary belongs to one table on one rank (merging them is "
+                         "not built)", what);
 }
 // Plans with expression aggregations: their rows are ordinary rows of a DOUBLE column, so the cross-GPU entry points
 // take them as they are; a caller's table (d_table) is declined, as for the other families with a parameter block of

@@ -38,6 +38,7 @@ void crash_trace_handler(int sig, siginfo_t* si, void* uc) {
 // changes a result: "1" (per-phase host times of every plan, execution and finalize on stderr), "crash" (on
 // SIGSEGV / SIGBUS / SIGABRT print the native frames), "check" (a scan launch's records and tile map are read back
 // and checked before the launch), "serialize" (entry points run one at a time: isolates host races from device ones).
+// "derive" (the kernels of every derived-column build between event pairs: one line per build, tools/group_expr_cost.py).
 // Executor settings are pgpu_config's (pgpu_table_set_config), never the environment.
 bool diag(const char* word) {
   static const std::string v = [] {
@@ -118,24 +119,29 @@ int pgpu::abi_exception() noexcept {
 
 
 int pgpu::table_dict_view(pgpu_table t, int col, DictView* out) {
-  if (!t || col < 0 || col >= (int)t->names.size()) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
+  if (!t) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
   std::shared_ptr<const Dict> d;
   {
     std::lock_guard<std::mutex> g(t->mu);
-    d = t->global[col];
+    if (!t->has_dict_col(col)) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
+    d = t->col_global(col);
+    out->name = t->col_name(col);
   }
   out->keep = d;
   out->type = d->type;
   out->iv = &d->iv;
   out->dv = &d->dv;
   out->sv = &d->sv;
-  out->name = t->names[col];
   return 0;
 }
 
 int pgpu::table_column_name(pgpu_table t, int col, std::string* out) {
   if (!t || col < 0) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
   std::lock_guard<std::mutex> g(t->mu);
+  if (is_group_expr_col(col) && t->has_dict_col(col)) {  // a group-by expression: its function form
+    *out = t->col_name(col);
+    return 0;
+  }
   const int e = col - (int)t->names.size();
   if (e >= (int)t->exprs.size()) return host_fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
   *out = e < 0 ? t->names[col] : t->exprs[e].name;
@@ -151,7 +157,8 @@ int pgpu::result_key_dict_view(const pgpu_result_s* r, pgpu_table t, int key, Di
   out->iv = &d->iv;
   out->dv = &d->dv;
   out->sv = &d->sv;
-  out->name = t && r->key_cols[key] >= 0 && r->key_cols[key] < (int)t->names.size() ? t->names[r->key_cols[key]] : "";
+  out->name = "";
+  if (t && r->key_cols[key] >= 0) table_column_name(t, r->key_cols[key], &out->name);  // (an unknown column: no name)
   return 0;
 }
 

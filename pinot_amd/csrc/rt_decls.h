@@ -23,6 +23,9 @@ int ensure_values(pgpu_table_s* t, Segment& s, int col, hipStream_t stream);
 int ensure_global_values(pgpu_table_s* t, int col, hipStream_t stream);
 int ensure_value_map(pgpu_table_s* t, Segment& s, int col);
 int ensure_docid(pgpu_table_s* t, int64_t n, hipStream_t stream);
+int ensure_derived(pgpu_table_s* t, Segment& s, int col, hipStream_t stream);
+int segment_column(pgpu_table_s* t, Segment& s, int col, const Column** out);
+int table_reader_dict(pgpu_table_s* t, int col);
 void account_unpin(pgpu_table_s* t, const Segment* s);
 int64_t padded_fwd_words(int64_t num_docs, int bits);
 int64_t lz4_decode_block(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap);

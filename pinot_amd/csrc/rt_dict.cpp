@@ -1,4 +1,6 @@
 // rt_dict.cpp -- segment and table-global dictionaries, LUTs, value arrays (rt.h).
+#include "derive.h"
+#include "group_expr.h"
 #include "rt_decls.h"
 
 namespace pgpu {
@@ -108,11 +110,11 @@ int64_t global_index_of(const Dict& g, const Dict& local, size_t i) {
 
 // Makes the local->global LUT of (seg, col) current.
 int ensure_lut(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
-  Column& c = s.cols[col];
-  if (c.lut_version == t->global_version[col] && c.lut) return 0;
+  Column& c = s.col(col);
+  if (c.lut_version == t->col_global_version(col) && c.lut) return 0;
   std::vector<int32_t> lut(std::max<int32_t>(c.card, 1));
   for (int32_t i = 0; i < c.card; ++i) {
-    int64_t g = global_index_of(*t->global[col], c.dict, i);
+    int64_t g = global_index_of(*t->col_global(col), c.dict, i);
     if (g < 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "value missing from the global dictionary (column %d)", col);
     lut[i] = (int32_t)g;
   }
@@ -122,7 +124,7 @@ int ensure_lut(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
   HIP_TRY(hipMemcpyAsync(m->p, lut.data(), sizeof(int32_t) * lut.size(), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   c.lut = std::move(m);  // the previous version lives on in the plans that reference it
-  c.lut_version = t->global_version[col];
+  c.lut_version = t->col_global_version(col);
   // strictly increasing (both dictionaries sorted), so the ends decide whether it is a contiguous run
   c.lut_off = c.card > 0 && lut[c.card - 1] - lut[0] == c.card - 1 ? lut[0] : -1;
   return 0;
@@ -130,7 +132,7 @@ int ensure_lut(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
 
 // Dictionary values for aggregation (Dictionary.readDoubleValues, DataFetcher.java:469-478).
 int ensure_values(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
-  Column& c = s.cols[col];
+  Column& c = s.col(col);
   if (c.d_key) return 0;
   const size_t n = std::max<int32_t>(c.card, 1);
   std::vector<int64_t> key(n, 0);
@@ -161,9 +163,9 @@ int ensure_values(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
 
 // The table-global value arrays of `col` for its current global dictionary (under the table mutex).
 int ensure_global_values(pgpu_table_s* t, int col, hipStream_t stream) {
-  auto& gv = t->gvalues[col];
-  if (gv.version == t->global_version[col] && gv.keys) return 0;
-  const Dict& g = *t->global[col];
+  auto& gv = t->col_gvalues(col);
+  if (gv.version == t->col_global_version(col) && gv.keys) return 0;
+  const Dict& g = *t->col_global(col);
   const size_t n = std::max<size_t>(g.size(), 1);
   std::vector<int64_t> key(n, 0);
   std::vector<double> val(n, 0.0);
@@ -188,7 +190,7 @@ int ensure_global_values(pgpu_table_s* t, int col, hipStream_t stream) {
   gv.n = (int64_t)n;
   gv.keys = std::move(k);
   gv.vals = std::move(v);
-  gv.version = t->global_version[col];
+  gv.version = t->col_global_version(col);
   return 0;
 }
 
@@ -197,13 +199,13 @@ int ensure_global_values(pgpu_table_s* t, int col, hipStream_t stream) {
 // thresholds (KCol.gaps, vidx) -- or not at all (dictionaries below kGlobalValuesMinCard, or more missing values: the
 // segment's own arrays).
 int ensure_value_map(pgpu_table_s* t, Segment& s, int col) {
-  Column& c = s.cols[col];
-  if (c.vmap_version == t->global_version[col]) return 0;
+  Column& c = s.col(col);
+  if (c.vmap_version == t->col_global_version(col)) return 0;
   c.vgap_first = -1;
   c.vgaps.clear();
-  c.vmap_version = t->global_version[col];
+  c.vmap_version = t->col_global_version(col);
   if (c.raw || c.card < kGlobalValuesMinCard) return 0;
-  const Dict& g = *t->global[col];
+  const Dict& g = *t->col_global(col);
   int64_t prev = -1, first = -1;
   std::vector<uint32_t> gaps;
   for (int32_t i = 0; i < c.card; ++i) {
@@ -253,6 +255,159 @@ int ensure_docid(pgpu_table_s* t, int64_t n, hipStream_t stream) {
   return 0;
 }
 
+// The derived column of group expression `col` (kGroupExprBase + k) in segment s, built on first use (under the table
+// mutex, like the LUTs): candidates over the operands' local dictionaries, the docs' candidate ids, the used candidates
+// compacted into the dictionary on the host (group_expr.h), the forward index packed (k_derive.hip).  The column is an
+// ordinary dictionary Column -- no inverted, sorted or range index, not raw -- and its values join the expression's
+// table-global dictionary as a pinned segment's join a real column's.
+int ensure_derived(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
+  const int k = col - kGroupExprBase;
+  if (k < 0 || k >= (int)t->gexprs.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
+  if (s.derived[k]) return 0;
+  const pgpu_table_s::GroupExpr& ge = t->gexprs[k];
+  constexpr int64_t kExact = 1ll << 53;
+  const uint32_t compared = expr_compared_columns(ge.prog);
+  KDeriveTask T;
+  memset(&T, 0, sizeof T);
+  T.prog = ge.prog;
+  T.num_docs = s.num_docs;
+  int64_t product = s.num_docs > 0 ? 1 : 0;
+  for (int c = 0; c < ge.prog.ncols; ++c) {
+    const int oc = ge.prog.col[c];
+    Column& o = s.cols[oc];
+    if (o.raw)
+      return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s over raw (no-dictionary) column %d", ge.name.c_str(), oc);
+    // A LONG operand past +-2^53 is not the double the evaluator reads: a LONG result would not be the reference's
+    // long, and a comparison not its Long.compare (check_compared_longs, rt_plan_create.cpp).
+    if (t->types[oc] == PGPU_LONG && (ge.type == PGPU_LONG || ((compared >> c) & 1u)) && !o.dict.iv.empty() &&
+        (o.dict.iv.front() < -kExact || o.dict.iv.back() > kExact))
+      return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s over LONG column %d, whose values go beyond +-2^53",
+                  ge.name.c_str(), oc);
+    product *= std::max<int64_t>(o.card, 1);
+    if (product > kGroupExprMaxProduct)
+      return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s: the operands' dictionaries of segment %lld have more "
+                  "than %lld combinations", ge.name.c_str(), (long long)s.handle, (long long)kGroupExprMaxProduct);
+  }
+  for (int c = 0; c < ge.prog.ncols; ++c) {
+    const int oc = ge.prog.col[c];
+    TRY(ensure_values(t, s, oc, stream));
+    const Column& o = s.cols[oc];
+    T.fwd[c] = o.d_fwd;
+    T.dval[c] = o.d_val;
+    T.bits[c] = o.bits;
+    T.card[c] = std::max(o.card, 1);
+  }
+  // PGPU_TRACE=derive: the build's three kernels between event pairs, one line per derived column on stderr
+  static const bool timed = diag("derive");
+  struct Events {
+    hipEvent_t e[6] = {};
+    bool on;
+    explicit Events(bool on_) : on(on_) { for (auto& x : e) if (on) hipEventCreate(&x); }
+    ~Events() { for (auto& x : e) if (x) hipEventDestroy(x); }
+    void mark(int k, hipStream_t st) { if (on) hipEventRecord(e[k], st); }
+    double us(int k) const { float ms = 0; return on && hipEventElapsedTime(&ms, e[k], e[k + 1]) == hipSuccess ? ms * 1e3 : 0.0; }
+  } ev(timed);
+  const double t_begin = timed ? now_us() : 0;
+  // device temporaries of the build, freed with it
+  struct Tmp {
+    void* p = nullptr;
+    ~Tmp() { if (p) hipFree(p); }
+  } d_keys, d_scratch, d_used, d_remap;
+  std::vector<int64_t> cand((size_t)product);
+  if (product > 0) {
+    HIP_TRY(hipMalloc(&d_keys.p, (size_t)product * 8));
+    ev.mark(0, stream);
+    if (launch_derive_candidates(T, product, reinterpret_cast<int64_t*>(d_keys.p), stream))
+      return fail(PGPU_ERR_DEVICE, "derive candidates launch failed: %s", hipGetErrorString(hipGetLastError()));
+    ev.mark(1, stream);
+    HIP_TRY(hipMemcpyAsync(cand.data(), d_keys.p, (size_t)product * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  group_expr_sort_unique(&cand);
+  const int32_t ncand = (int32_t)cand.size();
+  std::vector<uint32_t> used((size_t)ncand, 0u);
+  if (ncand > 0) {
+    HIP_TRY(hipMalloc(&d_scratch.p, (size_t)s.num_docs * 4));
+    HIP_TRY(hipMalloc(&d_used.p, (size_t)ncand * 4));
+    HIP_TRY(hipMemcpyAsync(d_keys.p, cand.data(), (size_t)ncand * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d_used.p, 0, (size_t)ncand * 4, stream));
+    ev.mark(2, stream);
+    if (launch_derive_ids(T, reinterpret_cast<const int64_t*>(d_keys.p), ncand, reinterpret_cast<uint32_t*>(d_scratch.p),
+                          reinterpret_cast<uint32_t*>(d_used.p), stream))
+      return fail(PGPU_ERR_DEVICE, "derive ids launch failed: %s", hipGetErrorString(hipGetLastError()));
+    ev.mark(3, stream);
+    HIP_TRY(hipMemcpyAsync(used.data(), d_used.p, (size_t)ncand * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  GroupExprDict gd = group_expr_compact(cand, used, ge.type);
+  auto col_out = std::make_unique<Column>();
+  Column& d = *col_out;
+  d.card = gd.card;
+  d.bits = gd.bits;
+  d.entry_width = gd.entry_width;
+  d.dict.type = ge.type;
+  d.dict.iv = std::move(gd.iv);
+  d.dict.dv = std::move(gd.dv);
+  d.raw_dict = std::move(gd.bytes);
+  d.fwd_bytes = ((int64_t)s.num_docs * d.bits + 7) / 8;
+  d.fwd_words = padded_fwd_words(s.num_docs, d.bits);
+  void* fwd = nullptr;
+  HIP_TRY(hipMalloc(&fwd, (size_t)d.fwd_words * 4));
+  d.d_fwd = reinterpret_cast<uint32_t*>(fwd);  // (freed with col_out on an early return: see below)
+  struct FreeFwd {
+    Column* c;
+    ~FreeFwd() { if (c && c->d_fwd) hipFree(c->d_fwd); }
+  } free_fwd{&d};
+  if (ncand > 0) {
+    HIP_TRY(hipMalloc(&d_remap.p, (size_t)ncand * 4));
+    HIP_TRY(hipMemcpyAsync(d_remap.p, gd.remap.data(), (size_t)ncand * 4, hipMemcpyHostToDevice, stream));
+    ev.mark(4, stream);
+    if (launch_derive_pack(reinterpret_cast<const uint32_t*>(d_scratch.p), reinterpret_cast<const int32_t*>(d_remap.p),
+                           s.num_docs, d.bits, d.d_fwd, d.fwd_words, stream))
+      return fail(PGPU_ERR_DEVICE, "derive pack launch failed: %s", hipGetErrorString(hipGetLastError()));
+    ev.mark(5, stream);
+  } else {
+    HIP_TRY(hipMemsetAsync(d.d_fwd, 0, (size_t)d.fwd_words * 4, stream));
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  free_fwd.c = nullptr;  // the segment owns it from here (~Segment)
+  if (timed && ncand > 0)
+    fprintf(stderr, "[pgpu] derive %s segment %lld docs %d candidates %lld unique %d card %d bits %d fwd_bytes %lld: "
+            "candidates_us %.1f ids_us %.1f pack_us %.1f build_us %.1f\n", ge.name.c_str(), (long long)s.handle, s.num_docs,
+            (long long)product, ncand, d.card, d.bits, (long long)d.fwd_words * 4, ev.us(0), ev.us(2), ev.us(4),
+            now_us() - t_begin);
+  t->device_bytes += d.fwd_words * 4;
+  if (merge_dict(t->col_global(col), d.dict)) {
+    t->col_global_version(col)++;
+    t->version++;  // compiled plans over the expression were sized by the previous dictionary
+    plan_cache_clear(t);
+  }
+  s.derived[k] = std::move(col_out);
+  return 0;
+}
+
+// (under the table mutex) column `col` of segment s for a reader of the C ABI: a real column, or the derived column of a
+// group expression, built here where this is its first use.
+int segment_column(pgpu_table_s* t, Segment& s, int col, const Column** out) {
+  if (is_group_expr_col(col)) {
+    TRY(ensure_derived(t, s, col, t->stream));
+    *out = &s.col(col);
+    return 0;
+  }
+  if (col < 0 || col >= (int)s.cols.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad column");
+  *out = &s.cols[col];
+  return 0;
+}
+
+// (under the table mutex) column `col` for a reader of its table-global dictionary: a real column, or a group
+// expression, whose dictionary is that of the derived columns -- every pinned segment's is built first.
+int table_reader_dict(pgpu_table_s* t, int col) {
+  if (!t->has_dict_col(col)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  if (is_group_expr_col(col))
+    for (auto& hs : t->segments) TRY(ensure_derived(t, *hs.second, col, t->stream));
+  return 0;
+}
+
 // Unpin accounting: the segment's device bytes leave the table's total now; the memory itself goes with the last
 // reference (~Segment).
 void account_unpin(pgpu_table_s* t, const Segment* s) {
@@ -263,6 +418,9 @@ void account_unpin(pgpu_table_s* t, const Segment* s) {
                        (c.d_key ? 16 * (c.raw ? raw_padded_docs(s->num_docs) : std::max(c.card, 1)) : 0);
     if (!c.raw) fwd_words += (c.fwd_words + 63) & ~int64_t(63);
   }
+  for (const auto& d : s->derived)  // derived columns: a forward index of their own, LUT and value arrays as above
+    if (d)
+      t->device_bytes -= d->fwd_words * 4 + (d->lut ? 4 * std::max(d->card, 1) : 0) + (d->d_key ? 16 * std::max(d->card, 1) : 0);
   if (s->d_block) t->device_bytes -= std::max<int64_t>(fwd_words, 64) * 4;
   if (s->star) t->device_bytes -= s->star->bytes;
 }

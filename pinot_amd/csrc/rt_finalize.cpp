@@ -414,7 +414,7 @@ void describe_result(const pgpu_plan_s* P, pgpu_result_s* R) {
   R->key_cols = P->key_cols;
   R->key_dicts.assign(P->key_dicts.begin(), P->key_dicts.end());
   R->key_types.clear();
-  for (int c : P->key_cols) R->key_types.push_back(P->table->types[c]);
+  for (int c : P->key_cols) R->key_types.push_back(P->table->col_type(c));
   R->agg_fn = P->agg_fn;
   R->agg_col = P->agg_col;
   R->agg_conv.assign(na, RCONV_I64);
@@ -430,7 +430,7 @@ void describe_result(const pgpu_plan_s* P, pgpu_result_s* R) {
       R->agg_conv[a] = P->slot_kind[P->agg_slot[a]] == SLOT_SUM_I64 ? RCONV_I64 : RCONV_F64;
     else
       // (MIN / MAX of an expression, a virtual column past the table's real ones: the key of its double)
-      R->agg_conv[a] = P->agg_col[a] < (int)P->table->types.size() && is_int_type(P->table->types[P->agg_col[a]])
+      R->agg_conv[a] = P->agg_col[a] < (int)P->table->names.size() && is_int_type(P->table->types[P->agg_col[a]])
                            ? RCONV_I64 : RCONV_KEY_F64;
   }
   // fixed-point FLOAT / DOUBLE sums (PGPU_OPT_EXACT_FP_SUM): W digit sums from the aggregation's slot on, converted to

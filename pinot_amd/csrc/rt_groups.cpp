@@ -26,20 +26,23 @@ int split_for_groups_limit(pgpu_table_s* t, const int64_t* handles, int32_t nseg
     std::lock_guard<std::mutex> g(t->mu);
     for (int k = 0; k < q->num_group_by; ++k) {
       const int c = q->group_by[k];
-      if (c < 0 || c >= (int)t->names.size()) return 0;
-      const int64_t card = std::max<int64_t>((int64_t)t->global[c]->size(), 1);
-      global_keys = global_keys > INT64_MAX / card ? INT64_MAX : global_keys * card;
+      if (!t->has_dict_col(c)) return 0;
     }
     for (int i = 0; i < nsegs; ++i) {
       const int64_t h = handles[i];
-      const Segment* sp = h > 0 && h < (int64_t)t->by_handle.size() ? t->by_handle[h].get() : nullptr;
+      Segment* sp = h > 0 && h < (int64_t)t->by_handle.size() ? t->by_handle[h].get() : nullptr;
       if (!sp) return 0;  // plan_create_impl reports it
       for (int k = 0; k < q->num_group_by; ++k) {
         const int c = q->group_by[k];
-        if (c < 0 || c >= (int)t->names.size()) return 0;
-        const int64_t card = std::max<int64_t>(sp->cols[c].card, 1);
+        // (a group-by expression: its derived column decides the segment's key space, so it is built here)
+        if (is_group_expr_col(c)) TRY(ensure_derived(t, *sp, c, t->stream));
+        const int64_t card = std::max<int64_t>(sp->col(c).card, 1);
         prod[i] = prod[i] > INT64_MAX / card ? INT64_MAX : prod[i] * card;
       }
+    }
+    for (int k = 0; k < q->num_group_by; ++k) {  // (after the derived columns: they grow their global dictionary)
+      const int64_t card = std::max<int64_t>((int64_t)t->col_global(q->group_by[k])->size(), 1);
+      global_keys = global_keys > INT64_MAX / card ? INT64_MAX : global_keys * card;
     }
   }
   const bool pql = !(q->options & PGPU_OPT_SQL_GROUP_BY);

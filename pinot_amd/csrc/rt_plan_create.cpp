@@ -129,6 +129,22 @@ int bind_expr_leaf(PlanCtx& cx, int i, int vcol) {
   return 0;
 }
 
+// Group-by i names the group expression gcol (pgpu_table_add_group_expression): every planned segment gets its derived
+// column now (under the table mutex; built on the GPU where this is its first use, ensure_derived), before anything
+// reads a key column's cardinality.  Declined here: an external table, as for the other plans that are not a plain
+// table of real columns; the cross-GPU entry points check pgpu_plan_s::group_exprs.
+int bind_group_expr(PlanCtx& cx, int i, int gcol) {
+  pgpu_table_s* t = cx.t;
+  pgpu_plan_s* P = cx.P;
+  if (cx.se && cx.se->d_table) return fail(PGPU_ERR_UNSUPPORTED, "a GROUP BY expression with an external table");
+  std::lock_guard<std::mutex> g(t->mu);
+  if (!t->has_dict_col(gcol)) return fail(PGPU_ERR_INVALID_ARGUMENT, "group-by %d: bad column %d", i, gcol);
+  for (Segment* s : P->segs) TRY(ensure_derived(t, *s, gcol, t->stream));
+  const ExprProg& prog = t->gexprs[gcol - kGroupExprBase].prog;
+  P->group_exprs.push_back({gcol, std::vector<int32_t>(prog.col, prog.col + prog.ncols)});
+  return 0;
+}
+
 // Predicate and group-by columns become query columns.  Raw (no-dictionary) columns: aggregation operands and
 // raw-value predicate leaves; a group-by on one runs on Pinot's NoDictionary*GroupKeyGenerator, not here.
 int bind_query_columns(PlanCtx& cx) {
@@ -150,7 +166,11 @@ int bind_query_columns(PlanCtx& cx) {
   P->num_leaves = q->num_predicates;
   for (int i = 0; i < q->num_group_by; ++i) {
     const int c = q->group_by[i];
-    if (c < 0 || c >= ncols) return fail(PGPU_ERR_INVALID_ARGUMENT, "group-by %d: bad column %d", i, c);
+    if (is_group_expr_col(c)) {  // a group-by expression: from here on the dictionary column Segment::col(c) resolves
+      TRY(bind_group_expr(cx, i, c));
+    } else if (c < 0 || c >= ncols) {
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "group-by %d: bad column %d", i, c);
+    }
     P->key_cols.push_back(c);
     query_col(P, c);
   }
@@ -163,7 +183,7 @@ int bind_query_columns(PlanCtx& cx) {
         return fail(PGPU_ERR_UNSUPPORTED, "predicate on raw STRING column %d", q->predicates[i].column);
     }
     for (int i = 0; i < q->num_group_by; ++i)
-      if (s->cols[q->group_by[i]].raw)
+      if (s->col(q->group_by[i]).raw)
         return fail(PGPU_ERR_UNSUPPORTED, "group-by on raw (no-dictionary) column %d", q->group_by[i]);
   }
   return 0;
@@ -497,7 +517,11 @@ int assign_slots(PlanCtx& cx) {
   if ((int)P->query_cols.size() > kMaxQueryCols) return fail(PGPU_ERR_UNSUPPORTED, "too many columns");
   // TransformOperator.getNumColumnsProjected: distinct group-by and aggregation columns -- for an expression the
   // columns it names (AggregationOperator.java:90 counts the projection's columns, each once)
-  std::vector<int> proj(P->key_cols.begin(), P->key_cols.end());
+  // (a group-by expression projects its operands; its derived column is no column of the reference's segment)
+  std::vector<int> proj;
+  for (int c : P->key_cols)
+    if (!is_group_expr_col(c)) proj.push_back(c);
+  for (const pgpu_plan_s::GroupExprRef& ge : P->group_exprs) proj.insert(proj.end(), ge.operands.begin(), ge.operands.end());
   for (int i = 0; i < q->num_aggs; ++i) {
     if (q->aggs[i].column >= ncols) {  // (a COUNT never reads its argument: of an expression it projects nothing)
       for (const pgpu_plan_s::PlanExpr& pe : P->exprs)
@@ -521,7 +545,7 @@ void note_groups_limit(PlanCtx& cx) {
   for (Segment* s : P->segs) {
     int64_t prod = 1;
     for (int c : P->key_cols) {
-      const int64_t card = std::max<int64_t>(s->cols[c].card, 1);
+      const int64_t card = std::max<int64_t>(s->col(c).card, 1);
       prod = prod > INT64_MAX / card ? INT64_MAX : prod * card;
     }
     if (prod > q->num_groups_limit) P->limit_sensitive = true;
@@ -549,7 +573,7 @@ int plan_segment_arrays(PlanCtx& cx) {
     for (size_t j = 0; j < nk; ++j) {
       const int c = P->key_cols[j];
       TRY(ensure_lut(t, *s, c, stream));
-      const Column& col = s->cols[c];
+      const Column& col = s->col(c);
       P->refs->luts.push_back(col.lut);
       KeyLut& kl = P->key_lut[i * nk + j];
       kl.lut = col.lut_off >= 0 ? nullptr : reinterpret_cast<const int32_t*>(col.lut->p);
@@ -672,7 +696,7 @@ int build_device_arrays(PlanCtx& cx) {
   std::lock_guard<std::mutex> table_lock(t->mu);
   P->key_dicts.resize(nk);
   for (size_t j = 0; j < nk; ++j) {
-    P->key_dicts[j] = t->global[P->key_cols[j]];
+    P->key_dicts[j] = t->col_global(P->key_cols[j]);
     cx.gcard[j] = (int64_t)P->key_dicts[j]->size();
   }
   for (pgpu_plan_s::Distinct& d : P->dc) {  // the bitmap's width: the snapshot the LUTs taken below map into
@@ -734,7 +758,7 @@ int restrict_key_space(PlanCtx& cx, std::vector<int64_t>* kspan_out) {
         const pgpu_predicate& pr = q->predicates[l];
         if (pr.column != c || (pr.type != PGPU_PRED_EQ && pr.type != PGPU_PRED_IN && pr.type != PGPU_PRED_RANGE)) continue;
         ParsedPred pp;
-        TRY(parse_predicate(cx.t->types[c], pr, &pp));
+        TRY(parse_predicate(cx.t->col_type(c), pr, &pp));
         int64_t a = 0, b = 0;
         admitted_ids(gd, pr, pp, &a, &b);
         lo = std::max(lo, a);
@@ -857,7 +881,7 @@ void choose_table_mode(PlanCtx& cx) {
     for (Segment* s : P->segs) {
       int64_t local = 1;
       for (int c : P->key_cols) {
-        const int64_t card = std::max<int64_t>(s->cols[c].card, 1);
+        const int64_t card = std::max<int64_t>(s->col(c).card, 1);
         local = local > (int64_t)s->num_docs / card ? (int64_t)s->num_docs + 1 : local * card;
       }
       bound += std::min<int64_t>(local, s->num_docs);
@@ -1093,7 +1117,7 @@ bool fill_kcols(const PlanCtx& cx, size_t i, KCol* kc) {
   bool gathers = false;
   for (int j = 0; j < nqc; ++j) {
     const int tc = P->query_cols[j];
-    const Column* c = tc == kDocIdColumn ? nullptr : &s->cols[tc];
+    const Column* c = tc == kDocIdColumn ? nullptr : &s->col(tc);
     if (!c || c->raw) {  // the virtual $docId, or values per doc: addressed through the identity docId index
       kc[j].fwd = P->docid_fwd;
       kc[j].lut = nullptr;

@@ -231,6 +231,7 @@ class GpuTable:
         self.handle = h
         self._dict_cache = {}
         self._snapshots = {}  # dictionary snapshot id -> values (results index the snapshot their plan saw)
+        self.group_types = {}  # group-by expression (function-form name) -> the type code of its derived column
         if config:
             self.set_config(**config)
 
@@ -290,6 +291,28 @@ class GpuTable:
                                                    ctypes.byref(out)))
         return out.value
 
+    def add_group_expression(self, ops, result_type, name=None):
+        """pgpu_table_add_group_expression: registers a postfix program as a group-by expression of result type
+        `result_type` ('INT' | 'LONG' | 'FLOAT' | 'DOUBLE' or the code) and returns the index of its derived column (at or
+        above _lib.GROUP_EXPR_COLUMN_BASE).  An identical (program, type) registered before returns the same index."""
+        arr = (L.ExprOpC * max(len(ops), 1))()
+        for i, (op, col, lit) in enumerate(ops):
+            arr[i].op, arr[i].column, arr[i].literal = int(op), int(col), float(lit)
+        rt = L.TYPE_NAMES[result_type] if isinstance(result_type, str) else int(result_type)
+        out = ctypes.c_int32()
+        L.check(self.lib.pgpu_table_add_group_expression(self.handle, arr, len(ops), name.encode() if name else None, rt,
+                                                         ctypes.byref(out)))
+        return out.value
+
+    def _expr_ops(self, tree):
+        """(ops over this table's column indexes, {column name: type name}) of an expression tree."""
+        from .query import expr_columns, expr_program
+        types = {n: L.TYPE_NAME_OF[t] for n, t in zip(self.names, self.types)}  # (a CASE's literals need them)
+        for c in expr_columns(tree):
+            if c not in types:
+                raise KeyError("unknown column %r" % c)
+        return [(op, self.names.index(c) if c is not None else 0, lit) for op, c, lit in expr_program(tree, types)], types
+
     def expression(self, column):
         """pgpu_table_expression: a virtual column's (ops, name), ops as (op, column index, literal) triples."""
         n = ctypes.c_int32()
@@ -309,17 +332,17 @@ class GpuTable:
             used += [("WHERE", p.column) for p in preds]
         for fn, col in used:
             if col in exprs and col not in self.index and fn != "COUNT":
-                from .query import expr_columns, expr_program
-                ops = []
-                types = {n: L.TYPE_NAME_OF[t] for n, t in zip(self.names, self.types)}  # (a CASE's literals need them)
-                for c in expr_columns(exprs[col]):
-                    if c not in types:
-                        raise KeyError("unknown column %r" % c)
-                for op, c, lit in expr_program(exprs[col], types):
-                    if c is not None and c not in self.index:
-                        raise KeyError("unknown column %r" % c)
-                    ops.append((op, self.index[c] if c is not None else 0, lit))
+                ops, _ = self._expr_ops(exprs[col])
                 self.index[col] = self.add_expression(ops, col)
+        # group-by expressions: derived columns, under a key of their own -- SUM(a*b) .. GROUP BY a*b uses both the
+        # virtual column mult(a,b) and the derived column ("group", mult(a,b)) -- typed by the expression's result type
+        for col in query.group_by:
+            if col in exprs and ("group", col) not in self.index:
+                from .query import expr_type
+                ops, types = self._expr_ops(exprs[col])
+                rtype = expr_type(exprs[col], types)
+                self.index[("group", col)] = self.add_group_expression(ops, rtype, col)
+                self.group_types[col] = L.TYPE_NAMES[rtype]
         return query.to_c(self.index)
 
     # ------------------------------------------------------------------ segments
@@ -452,13 +475,15 @@ class GpuTable:
         self._dict_cache.clear()
 
     def dictionary(self, column):
-        """Table-global dictionary of `column` (sorted values; the group ids of results index it)."""
+        """Table-global dictionary of `column` (sorted values; the group ids of results index it).  The readers of this
+        class take ("group", function-form name) for the derived column of a registered group-by expression."""
         if column in self._dict_cache:
             return self._dict_cache[column]
         ci = self.index[column]
         n = ctypes.c_int64()
         L.check(self.lib.pgpu_table_dictionary_size(self.handle, ci, ctypes.byref(n)))
-        t = self.types[ci]
+        # (("group", name): the derived column of a group-by expression query_c registered, typed by its result type)
+        t = self.group_types[column[1]] if isinstance(column, tuple) else self.types[ci]
         if t in (L.INT, L.LONG):
             a = np.zeros(max(n.value, 1), dtype=np.int64)
             L.check(self.lib.pgpu_table_dictionary_i64(self.handle, ci, L.ptr(a, ctypes.c_int64)))
@@ -478,16 +503,17 @@ class GpuTable:
         self._dict_cache[column] = vals
         return vals
 
-    def result_dictionary(self, r, key, column):
+    def result_dictionary(self, r, key, column, group_expr=False):
         """Values of the table-global dictionary snapshot that group-by key `key` of C result `r` indexes (cached
-        by snapshot id: unchanged until a pin grows the column's dictionary)."""
+        by snapshot id: unchanged until a pin grows the column's dictionary).  group_expr: `column` names a group-by
+        expression, whose keys have its result type (ints for INT / LONG, floats for FLOAT / DOUBLE)."""
         sid, n = ctypes.c_uint64(), ctypes.c_int64()
         L.check(self.lib.pgpu_result_key_dictionary(r, key, ctypes.byref(sid), ctypes.byref(n)))
         vals = self._snapshots.get(sid.value)
         if vals is not None:
             return vals
         n = n.value
-        t = self.types[self.index[column]]
+        t = self.group_types[column] if group_expr else self.types[self.index[column]]
         if t in (L.INT, L.LONG):
             a = np.zeros(max(n, 1), dtype=np.int64)
             L.check(self.lib.pgpu_result_key_dictionary_i64(r, key, L.ptr(a, ctypes.c_int64)))
@@ -539,7 +565,7 @@ class GpuTable:
         _lib.FpSumRangeC."""
         if isinstance(query, str):
             from .query import parse_query
-            query = parse_query(query, filter_expressions=True)
+            query = parse_query(query, filter_expressions=True, group_by_expressions=True)
         hs = np.ascontiguousarray(list(handles), dtype=np.int64)
         q, keep = self.query_c(query)
         na = len(query.aggregations)
@@ -577,7 +603,7 @@ class Plan:
         fp_sum_ranges: the agreed ranges of pgpu_plan_create_agreed (not with execute)."""
         if isinstance(query, str):
             from .query import parse_query
-            query = parse_query(query, filter_expressions=True)
+            query = parse_query(query, filter_expressions=True, group_by_expressions=True)
         self.table = table
         self.query = query
         self.lib = table.lib
@@ -792,7 +818,7 @@ def _decode_result(table, query, holder):
         for j in range(nk):
             L.check(lib.pgpu_result_group_ids_view(r, j, ctypes.byref(ptr)))
             cols.append(_view(holder, ptr.value, n, np.int32))
-        dicts = [table.result_dictionary(r, j, c) for j, c in enumerate(query.group_by)]
+        dicts = [table.result_dictionary(r, j, c, group_expr=c in query.expressions) for j, c in enumerate(query.group_by)]
         aggs = []
         exact = {}
         form = ctypes.c_int32()

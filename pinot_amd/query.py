@@ -606,10 +606,14 @@ class QueryContext:
         # parser found them -- every other name is a column, whatever characters it has (a quoted identifier).  None
         # (a query built by hand): an argument, or a predicate's column, with one of ( ) + - * / is read as an
         # expression's text.
+        # A group_by entry that is a key of the given `expressions` is a group-by expression (GROUP BY a + b, kept as
+        # its function-form name add(a,b): parse_query(..., group_by_expressions=True)); a bare "a+b" is not parsed here.
         sniff = expressions is None
         for c in self.group_by:
             if sniff and is_expression(c):
-                raise ValueError("expression %r in GROUP BY: expressions are supported inside aggregations only" % (c,))
+                raise ValueError("expression %r in GROUP BY: expressions are supported inside aggregations only "
+                                 "(parse_query(..., group_by_expressions=True) reads them in GROUP BY; a query built by "
+                                 "hand names the expression's function form and gives its tree in `expressions`)" % (c,))
         # (fn, column) or, for the exact percentile, ("PERCENTILE", column, percentile); kept as (canonical name, column).
         # An argument that is an arithmetic expression (SUM(price * qty)) is kept as its canonical function-form name
         # (mult(price,qty)); expressions: name -> canonical tree.  Equal expressions share one name, so one virtual column.
@@ -666,6 +670,10 @@ class QueryContext:
         self.end_time_ms = 0 if timeout_ms is None else int(time.time() * 1000) + int(timeout_ms)
         return self
 
+    def group_expr(self, column):
+        """The tree of group-by entry `column` if it is an expression, else None."""
+        return self.expressions.get(column) if column in self.group_by else None
+
     def expr_ref(self, expr):
         """(kind, index) of a SELECT / ORDER BY expression over the result: (0, group-by position) or
         (1, aggregation position)."""
@@ -693,7 +701,8 @@ class QueryContext:
             self.filter.postfix(preds, [])
             for p in preds:
                 cols += expr_columns(self.expressions[p.column]) if p.column in self.expressions else [p.column]
-        cols += self.group_by
+        for c in self.group_by:  # (a group-by expression reads its operands)
+            cols += expr_columns(self.expressions[c]) if c in self.expressions else [c]
         for _, c in self.aggregations:
             cols += expr_columns(self.expressions[c]) if c in self.expressions else [c] * (c != "*")
         out = []
@@ -761,7 +770,10 @@ class QueryContext:
         oc = (L.FilterOpC * max(len(ops), 1))()
         for i, (o, a) in enumerate(ops):
             oc[i].op, oc[i].arg = o, a
-        gb = (ctypes.c_int32 * max(len(self.group_by), 1))(*[column_index[c] for c in self.group_by])
+        # (a group-by expression: GpuTable registers it under ("group", name) -- the aggregation's virtual column of the
+        # same name, SUM(a*b) .. GROUP BY a*b, is another index)
+        gb = (ctypes.c_int32 * max(len(self.group_by), 1))(
+            *[column_index[("group", c) if c in self.expressions else c] for c in self.group_by])
         ac = (L.AggC * max(len(self.aggregations), 1))()
         for i, (fn, col) in enumerate(self.aggregations):
             p_e4 = percentile_e4(fn)
@@ -826,9 +838,15 @@ _ARITH_OPS = (("op", "+"), ("op", "-"), ("op", "*"), ("op", "/"))
 
 
 class _Parser:
-    def __init__(self, sql, filter_expressions=False):
+    def __init__(self, sql, filter_expressions=False, group_by_expressions=False):
         self.t = _tokenize(sql)
         self.i = 0
+        # GROUP BY a + b (parse_query): function-form name -> tree of the expressions met in GROUP BY and, in SELECT and
+        # ORDER BY, of the items that are expressions over columns (named_exprs: their names, matched to the GROUP BY
+        # entries once those are known)
+        self.group_by_expressions = group_by_expressions
+        self.group_exprs = {}
+        self.named_exprs = []
         # function-form name -> tree of the aggregation arguments and predicate left-hand sides that are expressions
         self.exprs = {}
         self.filter_expressions = filter_expressions  # WHERE price * qty > 1000 (parse_query)
@@ -847,8 +865,36 @@ class _Parser:
         self.i += 1
         return tok[1]
 
+    def group_expr_ahead(self):
+        """Whether the SELECT / ORDER BY item at hand is an expression over columns, not an aggregation or a plain
+        column: a CASE, a parenthesis, a number, a transform function (whose names no aggregation function has), or a
+        column followed by an arithmetic operator."""
+        tok = self.peek()
+        if self.case_ahead() or tok in (("op", "("), ("op", "-")) or tok[0] == "lit":
+            return True
+        if tok[0] != "id":
+            return False
+        if self.peek(1) == ("op", "("):
+            up = tok[1].upper()
+            return up in _EXPR_FUNCTIONS or up in _CMP_FUNCTIONS or up in ("AND", "OR", "CASE")
+        return self.peek(1) in _ARITH_OPS
+
+    def group_expr_item(self):
+        """A GROUP BY item, or a SELECT / ORDER BY item that group_expr_ahead: the grammar and limits of an
+        aggregation's argument, kept as its canonical function-form name."""
+        tree = self.arith_checked()
+        name = expr_name(tree)
+        if tree[0] != "col":
+            self.group_exprs[name] = tree
+        return name
+
     def select_list_item(self):
         tok = self.peek()
+        if self.group_by_expressions and self.group_expr_ahead():
+            name = self.group_expr_item()
+            if name in self.group_exprs:
+                self.named_exprs.append(name)
+            return ("col", name)
         if tok[0] == "id" and self.peek(1) == ("op", "("):
             fn = self.take("id")
             self.take("op", "(")
@@ -1107,15 +1153,22 @@ class _Parser:
         raise ValueError("unsupported operator %s" % op)
 
 
-def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=False, filter_expressions=False):
+def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=False, filter_expressions=False,
+                group_by_expressions=False):
     """Parses `SELECT cols / aggs FROM t [WHERE ...] [GROUP BY cols] [ORDER BY expr [ASC|DESC], ...]
     [TOP n | LIMIT n]`.  Aggregations that appear only in ORDER BY are computed as well (Pinot's hidden
     aggregations) but not selected.  exact_fp_sum: the query option of the same name (QueryContext).
     filter_expressions: a predicate's left-hand side may be an arithmetic expression (WHERE price * qty > 1000,
     WHERE ADD(a, b) BETWEEN 1 AND 5, IN / NOT IN; the grammar and limits of an aggregation's argument); the right-hand
     side stays a literal.  GpuTable parses its SQL strings with it on.  The default is off only because
-    tests/test_expr_agg_cpu.py pins ValueError for such strings under the default call."""
-    p = _Parser(sql, filter_expressions)
+    tests/test_expr_agg_cpu.py pins ValueError for such strings under the default call.
+    group_by_expressions: a GROUP BY item may be an expression -- GROUP BY a + b, GROUP BY CASE WHEN age < 18 THEN 0 ELSE
+    1 END, GROUP BY add(a, b): the grammar, limits and typing of an aggregation's argument.  It is kept as its canonical
+    function-form name (add(a,b)) with the tree in QueryContext.expressions; a SELECT or ORDER BY item that is such an
+    expression, in any accepted spelling, is matched to the GROUP BY entry by that name and becomes ("col", name), and
+    one that matches none is a ValueError.  GpuTable parses its SQL strings with it on; the default is off for the
+    same reason as filter_expressions."""
+    p = _Parser(sql, filter_expressions, group_by_expressions)
     p.take("id", "SELECT")
     items = p.select_list()
     p.take("id", "FROM")
@@ -1129,6 +1182,8 @@ def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=Fal
         p.take("id")
         p.take("id", "BY")
         def group_by_column():
+            if group_by_expressions:
+                return p.group_expr_item()
             if p.case_ahead():
                 raise ValueError("expression in GROUP BY near 'CASE': expressions are supported inside aggregations only")
             col = p.take("id")
@@ -1155,10 +1210,15 @@ def parse_query(sql, num_groups_limit=DEFAULT_NUM_GROUPS_LIMIT, exact_fp_sum=Fal
     if p.kw("TOP", "LIMIT"):
         p.take("id")
         limit = int(p.literal())
+    for name in p.named_exprs:
+        if name not in group_by:
+            raise ValueError("expression %s in SELECT / ORDER BY is no GROUP BY expression of the query" % name)
+    exprs = dict(p.exprs)
+    exprs.update({c: p.group_exprs[c] for c in group_by if c in p.group_exprs})
     select = [("col", it[1]) if it[0] == "col" else ("agg", it[1], it[2]) for it in items]
     aggs = []
     for e in [x for x in select if x[0] == "agg"] + [e for e, _ in order_by if e[0] == "agg"]:
         if (e[1], e[2]) not in aggs:
             aggs.append((e[1], e[2]))
     return QueryContext(group_by, aggs, flt, num_groups_limit, select=select, order_by=order_by, limit=limit,
-                        exact_fp_sum=exact_fp_sum, expressions=p.exprs)
+                        exact_fp_sum=exact_fp_sum, expressions=exprs)
