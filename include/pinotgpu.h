@@ -351,11 +351,50 @@ typedef struct {
  * project does not reproduce); STRING operands; IN inside WHEN; a missing ELSE (the reference's NULL makes R a STRING); a
  * boolean used as a number (SUM(a > 5)); a literal-only condition.  Declined at plan time (PGPU_ERR_UNSUPPORTED, the
  * message names "expression"): a LONG column that reaches a comparison as it is -- pushed and compared, or passed on by
- * SELECTs only -- while one of its dictionary values in a planned segment lies outside +-2^53. */
+ * SELECTs only -- while one of its dictionary values in a planned segment lies outside +-2^53.
+ *
+ * Math and time functions -- SUM(price * floor(qty / 10)), GROUP BY dateTimeConvert(ts,'1:MILLISECONDS:EPOCH',
+ * '1:HOURS:EPOCH','1:HOURS'), WHERE timeConvert(days,'DAYS','SECONDS') = x: the reference's
+ * SingleParamMathTransformFunction, ModuloTransformFunction, TimeConversionTransformFunction and the epoch-to-epoch form
+ * of DateTimeConversionTransformFunction.  Op code 15 is not an op.
+ *   ABS CEIL FLOOR SQRT  number -> number, the depth stays: Java's Math.abs / ceil / floor / sqrt, bit for bit (all four
+ *                      are correctly rounded).  abs(-0.0) is +0.0, ceil(-0.5) is -0.0, sqrt of a negative is NaN,
+ *                      sqrt(-0.0) is -0.0.
+ *   MOD                pop b, then a, push a % b of Java's doubles (C's fmod): exact, the dividend's sign; x % 0 and
+ *                      inf % y are NaN, x % inf is x.
+ *   LDIV               pop b, then a, push (double)((long)a / (long)b): Java's long division, truncated toward zero
+ *                      (-1 / 86400000 is 0, and a zero quotient is +0.0).  The divisor is the LITERAL op right before
+ *                      it, a positive integer of at most 2^53.  The dividend is integral: a COLUMN of type INT or LONG;
+ *                      x, LITERAL n, MULT over an integral x and a positive integer n of at most 2^53 (the literal on
+ *                      top: the long product -- LITERAL, x, MULT is arithmetic's double product and not integral); or
+ *                      another LDIV.  PGPU_ERR_INVALID_ARGUMENT otherwise, as for a boolean operand of any of these ops.
+ * EXP and LN are not ops: Java's Math.exp / Math.log are not correctly rounded, so their bits cannot be promised.
+ * A time function is a chain of such MULTs and LDIVs over its column, in the reference's order of operations:
+ * timeConvert(x, IN, OUT) is TimeUnit.convert -- x * (IN / OUT) where OUT is finer, x / (OUT / IN) where it is coarser,
+ * x itself for equal units; OUT = WEEKS is toMillis then / 604800000 (CustomTimeUnitTransformer).
+ * dateTimeConvert(x, 'n:IN:EPOCH', 'm:OUT:EPOCH', 'g:UNIT') is EpochToEpochTransformer: x * n, toMillis (a MULT; an LDIV
+ * for MICROSECONDS and NANOSECONDS), / G then * G with G the granularity in milliseconds, fromMillis (an LDIV; a MULT for
+ * MICROSECONDS and NANOSECONDS; WEEKS is / 604800000), / m.  Steps by 1 are left out and adjacent MULTs may be one; the
+ * longest chain is 13 ops.  The result type of both is LONG, that of the math functions DOUBLE.
+ * Declined at plan time (PGPU_ERR_UNSUPPORTED; the message names "expression", or "GROUP BY expression" for a derived
+ * column): a chain -- any x, LITERAL n, MULT or LDIV run that starts at an INT or LONG column -- whose column, any
+ * intermediate value or result leaves +-2^53 over the ends of that column's dictionary in a planned segment (all
+ * constants are positive, so a chain is monotone; the check is exact integer arithmetic).  Past +-2^53 a double is no
+ * longer the long, and further out Java's TimeUnit saturates.
+ * The caller's duty: a time function's first argument is an INT or LONG column (the reference casts every other
+ * argument to long, and there is no cast op); SIMPLE_DATE_FORMAT formats (their values are strings), MONTHS / YEARS as
+ * an output unit (the joda chronology) and WEEKS / MONTHS / YEARS as an input unit are to be declined.  A predicate on
+ * a LONG-typed expression (pgpu_predicate.column naming the virtual column of a time function) is the reference's raw
+ * LONG evaluator: each literal is read by Long.parseLong -- a decimal (= 1.5) or a value past int64 is its
+ * BadQueryRequestException and is to be declined -- and passed on as decimal text.  Within +-2^53, which the plan
+ * guarantees, comparing the doubles is comparing the longs, and no -0.0 can arise. */
 enum pgpu_expr_opcode { PGPU_EXPR_COLUMN = 0, PGPU_EXPR_LITERAL = 1, PGPU_EXPR_ADD = 2, PGPU_EXPR_SUB = 3,
                         PGPU_EXPR_MULT = 4, PGPU_EXPR_DIV = 5,
                         PGPU_EXPR_EQ = 6, PGPU_EXPR_NE = 7, PGPU_EXPR_GT = 8, PGPU_EXPR_GE = 9, PGPU_EXPR_LT = 10,
-                        PGPU_EXPR_LE = 11, PGPU_EXPR_AND = 12, PGPU_EXPR_OR = 13, PGPU_EXPR_SELECT = 14 };
+                        PGPU_EXPR_LE = 11, PGPU_EXPR_AND = 12, PGPU_EXPR_OR = 13, PGPU_EXPR_SELECT = 14,
+                        /* (15 is not an op) */
+                        PGPU_EXPR_ABS = 16, PGPU_EXPR_CEIL = 17, PGPU_EXPR_FLOOR = 18, PGPU_EXPR_SQRT = 19,
+                        PGPU_EXPR_MOD = 20, PGPU_EXPR_LDIV = 21 };
 #define PGPU_EXPR_MAX_OPS 16
 #define PGPU_EXPR_MAX_DEPTH 4
 #define PGPU_EXPR_MAX_COLUMNS 4

@@ -99,6 +99,9 @@ class AggC(ctypes.Structure):
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MULT, EXPR_DIV = 0, 1, 2, 3, 4, 5
 # comparisons (Double.compare of the operands), AND / OR over their booleans, SELECT: cond ? then : else (CASE)
 EXPR_EQ, EXPR_NE, EXPR_GT, EXPR_GE, EXPR_LT, EXPR_LE, EXPR_AND, EXPR_OR, EXPR_SELECT = 6, 7, 8, 9, 10, 11, 12, 13, 14
+# math and time functions: ABS / CEIL / FLOOR / SQRT take one operand, MOD is Java's % on doubles, LDIV the truncating
+# division of two longs (its divisor the positive integer literal right before it)
+EXPR_ABS, EXPR_CEIL, EXPR_FLOOR, EXPR_SQRT, EXPR_MOD, EXPR_LDIV = 16, 17, 18, 19, 20, 21  # (15 is no op)
 EXPR_MAX_OPS, EXPR_MAX_DEPTH, EXPR_MAX_COLUMNS, EXPR_MAX_PER_TABLE = 16, 4, 4, 256
 # group-by expressions (pgpu_table_add_group_expression): their column indexes start here; per table; the cap on the
 # product of the operands' segment-local dictionary sizes

@@ -218,6 +218,12 @@ def build_case_check(force=False):
     return _build_header_check("case_check", "case_check.cpp", "expr_eval.h", force, extra=("-ffp-contract=off",))
 
 
+def build_math_check(force=False):
+    """The math and time ops of the expression programs (expr_eval.h: ABS, CEIL, FLOOR, SQRT, MOD, LDIV) against libm,
+    int64 division and a direct evaluation of random programs; compiled as build_expr_check compiles its tool."""
+    return _build_header_check("math_check", "math_check.cpp", "expr_eval.h", force, extra=("-ffp-contract=off",))
+
+
 def build_group_expr_check(force=False):
     """The host steps of a derived column's build (group_expr.h: sort-unique, used-compaction, remap, bits), with the
     keys of expr_eval.h."""

@@ -144,7 +144,9 @@ static_assert(PGPU_EXPR_COLUMN == pgpu::EXPR_COLUMN && PGPU_EXPR_LITERAL == pgpu
               PGPU_EXPR_DIV == pgpu::EXPR_DIV && PGPU_EXPR_EQ == pgpu::EXPR_EQ && PGPU_EXPR_NE == pgpu::EXPR_NE &&
               PGPU_EXPR_GT == pgpu::EXPR_GT && PGPU_EXPR_GE == pgpu::EXPR_GE && PGPU_EXPR_LT == pgpu::EXPR_LT &&
               PGPU_EXPR_LE == pgpu::EXPR_LE && PGPU_EXPR_AND == pgpu::EXPR_AND && PGPU_EXPR_OR == pgpu::EXPR_OR &&
-              PGPU_EXPR_SELECT == pgpu::EXPR_SELECT && PGPU_EXPR_MAX_OPS == pgpu::kExprMaxOps &&
+              PGPU_EXPR_SELECT == pgpu::EXPR_SELECT && PGPU_EXPR_ABS == pgpu::EXPR_ABS && PGPU_EXPR_CEIL == pgpu::EXPR_CEIL &&
+              PGPU_EXPR_FLOOR == pgpu::EXPR_FLOOR && PGPU_EXPR_SQRT == pgpu::EXPR_SQRT && PGPU_EXPR_MOD == pgpu::EXPR_MOD &&
+              PGPU_EXPR_LDIV == pgpu::EXPR_LDIV && PGPU_EXPR_MAX_OPS == pgpu::kExprMaxOps &&
               PGPU_EXPR_MAX_DEPTH == pgpu::kExprMaxDepth && PGPU_EXPR_MAX_COLUMNS == pgpu::kExprMaxCols &&
               PGPU_EXPR_MAX_PER_TABLE == pgpu::kMaxTableExprs, "the header's limits are expr_eval.h's");
 
@@ -163,6 +165,13 @@ static std::string expr_default_name(const pgpu_table_s* t, const pgpu::ExprProg
       const std::string cond = st.back(), then = st[st.size() - 2];
       st.resize(st.size() - 2);
       st.back() = "case(" + cond + "," + then + "," + st.back() + ")";
+    } else if (op >= pgpu::EXPR_ABS && op <= pgpu::EXPR_SQRT) {
+      static const char* const kMath[] = {"abs", "ceil", "floor", "sqrt"};
+      st.back() = std::string(kMath[op - pgpu::EXPR_ABS]) + "(" + st.back() + ")";
+    } else if (op == pgpu::EXPR_MOD || op == pgpu::EXPR_LDIV) {
+      const std::string b = st.back();
+      st.pop_back();
+      st.back() = std::string(op == pgpu::EXPR_MOD ? "mod(" : "ldiv(") + st.back() + "," + b + ")";
     } else {
       static const char* const kFn[] = {"add", "sub", "mult", "div", "equals", "not_equals", "greater_than",
                                         "greater_than_or_equal", "less_than", "less_than_or_equal", "and", "or"};
@@ -187,6 +196,12 @@ static int check_expr_operands(const pgpu_table_s* t, const pgpu::ExprProg& prog
     if (t->types[col] == PGPU_STRING)
       return fail(PGPU_ERR_UNSUPPORTED, "%s over STRING column %d (%s)", what, col, t->names[col].c_str());
   }
+  // (an LDIV's dividend starts at an INT or LONG column: expr_compile took the column's word for it)
+  const uint32_t integral = pgpu::expr_integral_columns(prog);
+  for (int c = 0; c < prog.ncols; ++c)
+    if (((integral >> c) & 1u) && t->types[prog.col[c]] != PGPU_INT && t->types[prog.col[c]] != PGPU_LONG)
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "%s: %s (column %d, %s, is neither)", what,
+                  pgpu::expr_error_text(pgpu::EXPR_BAD_DIVIDEND), prog.col[c], t->names[prog.col[c]].c_str());
   return 0;
 }
 

@@ -27,6 +27,19 @@
 // they fit the type rules and refused by the depth limit like any other program that is too deep.
 // The VM is all-double.  Bit parity with the reference therefore is the caller's duty for literals (include/pinotgpu.h,
 // pgpu_expr_opcode): each literal is given as the double the reference reads under its type.
+//
+// Math and time functions (SingleParamMathTransformFunction, ModuloTransformFunction, TimeConversionTransformFunction,
+// DateTimeConversionTransformFunction's epoch-to-epoch form):
+//   ABS CEIL FLOOR SQRT  number -> number, the depth stays: Java's Math.abs / ceil / floor / sqrt, all correctly rounded
+//                      (abs(-0.0) is +0.0, ceil(-0.5) is -0.0, sqrt of a negative is NaN, sqrt(-0.0) is -0.0).
+//   MOD                pop b, then a; push a % b of Java's doubles, C's fmod: exact, the dividend's sign.
+//   LDIV               pop b, then a; push (double)((long)a / (long)b): the truncating division of two longs held in
+//                      doubles.  expr_compile admits it only where that reading is exact: b is the literal right before
+//                      it, a positive integer of at most 2^53, and a is integral -- an INT / LONG column
+//                      (expr_integral_columns: the caller checks the types), MULT of an integral value and a positive
+//                      integer literal, or another LDIV.  Within +-2^53 (the plan checks every chain against the
+//                      dictionaries: expr_chains_exact) the quotient of the doubles, truncated and put right by the exact
+//                      remainder, is the quotient of the longs.  A zero quotient is +0.0.
 #pragma once
 #include <stdint.h>
 
@@ -48,8 +61,11 @@ constexpr int kMaxPlanExprs = 8;   // distinct expressions aggregated by one pla
 enum ExprOpCode : int32_t {
   EXPR_COLUMN = 0, EXPR_LITERAL = 1, EXPR_ADD = 2, EXPR_SUB = 3, EXPR_MULT = 4, EXPR_DIV = 5,
   EXPR_EQ = 6, EXPR_NE = 7, EXPR_GT = 8, EXPR_GE = 9, EXPR_LT = 10, EXPR_LE = 11, EXPR_AND = 12, EXPR_OR = 13,
-  EXPR_SELECT = 14
+  EXPR_SELECT = 14,
+  // (15 is no op: the code the suite pins as the unknown one)
+  EXPR_ABS = 16, EXPR_CEIL = 17, EXPR_FLOOR = 18, EXPR_SQRT = 19, EXPR_MOD = 20, EXPR_LDIV = 21
 };
+constexpr double kExprExact = 9007199254740992.0;  // 2^53: up to here every integer is a double
 
 // One op as the caller states it (the layout of pgpu_expr_op, include/pinotgpu.h).
 struct ExprOpIn {
@@ -71,7 +87,7 @@ struct ExprProg {
 
 enum ExprError : int {
   EXPR_OK = 0, EXPR_BAD_LENGTH, EXPR_BAD_OP, EXPR_UNDERFLOW, EXPR_TOO_DEEP, EXPR_TOO_MANY_COLUMNS, EXPR_LEFTOVER,
-  EXPR_NO_COLUMN, EXPR_BAD_COLUMN, EXPR_BAD_TYPE
+  EXPR_NO_COLUMN, EXPR_BAD_COLUMN, EXPR_BAD_TYPE, EXPR_BAD_DIVISOR, EXPR_BAD_DIVIDEND, EXPR_BAD_MATH_TYPE
 };
 inline const char* expr_error_text(int e) {
   switch (e) {
@@ -86,6 +102,12 @@ inline const char* expr_error_text(int e) {
     case EXPR_BAD_TYPE:
       return "bad operand type: arithmetic and comparisons take numbers, AND / OR booleans, SELECT (number, number, "
              "boolean), and the program leaves a number";
+    case EXPR_BAD_DIVISOR:
+      return "LDIV's divisor is the LITERAL right before it, a positive integer of at most 2^53";
+    case EXPR_BAD_DIVIDEND:
+      return "LDIV's dividend is integral: an INT or LONG column, MULT of an integral value and a positive integer "
+             "literal, or another LDIV";
+    case EXPR_BAD_MATH_TYPE: return "bad operand type: ABS, CEIL, FLOOR, SQRT, MOD and LDIV take numbers, not booleans";
     default: return "negative column";
   }
 }
@@ -96,8 +118,11 @@ inline int expr_compile(const ExprOpIn* ops, int n, ExprProg* out) {
   *out = ExprProg{};
   if (!ops || n < 1 || n > kExprMaxOps) return EXPR_BAD_LENGTH;
   int depth = 0, nlit = 0;
-  uint32_t boolean = 0;
+  // `integral` likewise where entry d is an integral value (an LDIV's dividend; a column provisionally: its type is the
+  // caller's to check, expr_integral_columns), `posint` where it is a positive integer literal of at most 2^53.
+  uint32_t boolean = 0, integral = 0, posint = 0;
   auto is_bool = [&](int from_top) { return (boolean >> (depth - 1 - from_top)) & 1u; };
+  auto bit = [&](uint32_t m, int from_top) { return (m >> (depth - 1 - from_top)) & 1u; };
   for (int k = 0; k < n; ++k) {
     const int op = ops[k].op;
     int arg = 0;
@@ -111,15 +136,38 @@ inline int expr_compile(const ExprOpIn* ops, int n, ExprProg* out) {
       }
       arg = c;
       ++depth;
+      integral |= 1u << (depth - 1);
     } else if (op == EXPR_LITERAL) {
-      out->lit[nlit] = ops[k].literal;
+      const double l = ops[k].literal;
+      out->lit[nlit] = l;
       arg = nlit++;
       ++depth;
+      if (l >= 1.0 && l <= kExprExact && l == (double)(int64_t)l) posint |= 1u << (depth - 1);
     } else if (op >= EXPR_ADD && op <= EXPR_LE) {  // (number, number) -> number, or -> boolean of a comparison
       if (depth < 2) return EXPR_UNDERFLOW;
       if (is_bool(0) || is_bool(1)) return EXPR_BAD_TYPE;
+      // x, LITERAL n, MULT over an integral x is the long product x * n (the literal on top, as LDIV's divisor stands);
+      // LITERAL, x, MULT is arithmetic's double product, as the n-ary MULT of a caller starts.
+      const bool whole = op == EXPR_MULT && bit(integral, 1) && bit(posint, 0);
       --depth;
       if (op >= EXPR_EQ) boolean |= 1u << (depth - 1);
+      integral = (integral & ~(1u << (depth - 1))) | ((whole ? 1u : 0u) << (depth - 1));
+      posint &= ~(1u << (depth - 1));
+    } else if (op >= EXPR_ABS && op <= EXPR_SQRT) {  // number -> number
+      if (depth < 1) return EXPR_UNDERFLOW;
+      if (is_bool(0)) return EXPR_BAD_MATH_TYPE;
+      integral &= ~(1u << (depth - 1));
+      posint &= ~(1u << (depth - 1));
+    } else if (op == EXPR_MOD || op == EXPR_LDIV) {
+      if (depth < 2) return EXPR_UNDERFLOW;
+      if (is_bool(0) || is_bool(1)) return EXPR_BAD_MATH_TYPE;
+      if (op == EXPR_LDIV) {
+        if (ops[k - 1].op != EXPR_LITERAL || !bit(posint, 0)) return EXPR_BAD_DIVISOR;
+        if (!bit(integral, 1)) return EXPR_BAD_DIVIDEND;
+      }
+      --depth;
+      integral = (integral & ~(1u << (depth - 1))) | ((op == EXPR_LDIV ? 1u : 0u) << (depth - 1));
+      posint &= ~(1u << (depth - 1));
     } else if (op == EXPR_AND || op == EXPR_OR) {
       if (depth < 2) return EXPR_UNDERFLOW;
       if (!is_bool(0) || !is_bool(1)) return EXPR_BAD_TYPE;
@@ -128,11 +176,15 @@ inline int expr_compile(const ExprOpIn* ops, int n, ExprProg* out) {
       if (depth < 3) return EXPR_UNDERFLOW;
       if (!is_bool(0) || is_bool(1) || is_bool(2)) return EXPR_BAD_TYPE;
       depth -= 2;
+      integral &= ~(1u << (depth - 1));
+      posint &= ~(1u << (depth - 1));
     } else {
       return EXPR_BAD_OP;
     }
     if (depth > kExprMaxDepth) return EXPR_TOO_DEEP;
     boolean &= (1u << depth) - 1u;
+    integral &= (1u << depth) - 1u;
+    posint &= (1u << depth) - 1u;
     out->code[k] = op | (arg << 8);
   }
   if (depth != 1) return EXPR_LEFTOVER;
@@ -171,6 +223,44 @@ PGPU_HD inline double expr_apply(int op, double a, double b) {
 #endif
 }
 
+// ABS / CEIL / FLOOR / SQRT: one instruction each on the device (v_and, v_ceil_f64, v_floor_f64) but the square root,
+// which is the correctly rounded sequence of __dsqrt_rn.
+PGPU_HD inline double expr_unary(int op, double a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return op == EXPR_ABS ? __builtin_fabs(a) : op == EXPR_CEIL ? __builtin_ceil(a) : op == EXPR_FLOOR ? __builtin_floor(a)
+                                                                                                     : __dsqrt_rn(a);
+#else
+  return op == EXPR_ABS ? __builtin_fabs(a) : op == EXPR_CEIL ? __builtin_ceil(a) : op == EXPR_FLOOR ? __builtin_floor(a)
+                                                                                                     : __builtin_sqrt(a);
+#endif
+}
+
+// (double)((long)a / (long)b) for integers |a| <= 2^53 and 1 <= b <= 2^53 held in doubles, without a 64-bit integer
+// division.  a / b rounds to nearest, so its truncation is the quotient or, where the exact quotient lies just under an
+// integer that it rounds up to, one further from zero.  The remainder a - q * b of either candidate is an integer of
+// magnitude at most b <= 2^53, so the one rounding of a fused multiply-add returns it exactly, and its sign against a's
+// tells which candidate q is.  Adding +0.0 turns a -0.0 quotient (-1 / 86400000) into +0.0, as a long has one zero.
+PGPU_HD inline double expr_ldiv(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double q = __builtin_trunc(__ddiv_rn(a, b));
+#else
+  double q = __builtin_trunc(a / b);
+#endif
+  const double r = __builtin_fma(-q, b, a);
+  if (a >= 0.0 ? r < 0.0 : r > 0.0) q += a >= 0.0 ? -1.0 : 1.0;
+  return q + 0.0;
+}
+
+// MOD and LDIV.  The device's fmod is the library's exact one (the compiler's own expansion of a remainder,
+// x - trunc(x / y) * y, is not, so no builtin here).
+PGPU_HD inline double expr_divide(int op, double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return op == EXPR_MOD ? ::fmod(a, b) : expr_ldiv(a, b);
+#else
+  return op == EXPR_MOD ? __builtin_fmod(a, b) : expr_ldiv(a, b);
+#endif
+}
+
 // The columns of P (a mask over P.col[]) whose value reaches a comparison as it is: pushed and compared, or passed on
 // by SELECTs only.  The reference compares such an INT / LONG operand as an integer and this VM as a double, which is
 // the same thing within +-2^53: the plan checks the dictionaries of these columns.
@@ -182,6 +272,7 @@ inline uint32_t expr_compared_columns(const ExprProg& P) {
     if (op == EXPR_COLUMN) st[depth++] = 1u << arg;
     else if (op == EXPR_LITERAL) st[depth++] = 0;
     else if (op == EXPR_SELECT) { depth -= 2; st[depth - 1] |= st[depth]; }  // else | then (the condition is no value)
+    else if (op >= EXPR_ABS && op <= EXPR_SQRT) st[depth - 1] = 0;  // (one operand: the depth stays)
     else {
       if (op >= EXPR_EQ && op <= EXPR_LE) marked |= st[depth - 1] | st[depth - 2];
       --depth;
@@ -189,6 +280,79 @@ inline uint32_t expr_compared_columns(const ExprProg& P) {
     }
   }
   return marked;
+}
+
+// The integral chains of P: a chain starts at a column and goes on through x, LITERAL n, MULT and x, LITERAL n, LDIV (n a
+// positive integer of at most 2^53; what expr_compile calls integral), and ends where any other op reads it.  `visit`
+// is called for every chain op as visit(chain, op, n) before chain.len, the count of chain ops so far, goes up; lo / hi /
+// live are the visitor's to keep per chain.  A false answer ends the walk with false.
+struct ExprChain {
+  int col;  // of P.col[]; < 0: no chain value
+  int len;
+  int64_t lo, hi;
+  bool live;
+};
+template <typename Visit>
+inline bool expr_walk_chains(const ExprProg& P, Visit&& visit) {
+  ExprChain st[kExprMaxDepth + 1] = {};
+  const ExprChain none = {-1, 0, 0, 0, false};
+  int depth = 0;
+  for (int k = 0; k < P.nops; ++k) {
+    const int op = P.code[k] & 0xFF, arg = P.code[k] >> 8;
+    if (op == EXPR_COLUMN) { st[depth] = none; st[depth++].col = arg; }
+    else if (op == EXPR_LITERAL) st[depth++] = none;
+    else if (op >= EXPR_ABS && op <= EXPR_SQRT) st[depth - 1] = none;
+    else if (op == EXPR_SELECT) { depth -= 2; st[depth - 1] = none; }
+    else {
+      const int prev = k > 0 ? P.code[k - 1] : 0;
+      const double n = (prev & 0xFF) == EXPR_LITERAL ? P.lit[prev >> 8] : 0.0;
+      const bool posint = n >= 1.0 && n <= kExprExact && n == (double)(int64_t)n;
+      --depth;
+      ExprChain& e = st[depth - 1];
+      if ((op == EXPR_MULT || op == EXPR_LDIV) && posint && e.col >= 0) {
+        if (!visit(e, op, (int64_t)n)) return false;
+        ++e.len;
+      } else {
+        e = none;
+      }
+    }
+  }
+  return true;
+}
+
+// The columns of P (a mask over P.col[]) that an LDIV divides, directly or through a chain: they are to be INT or LONG
+// columns, which the caller -- who knows the table -- checks at registration.
+inline uint32_t expr_integral_columns(const ExprProg& P) {
+  uint32_t mask = 0;
+  expr_walk_chains(P, [&](ExprChain& e, int op, int64_t) {
+    if (op == EXPR_LDIV) mask |= 1u << e.col;
+    return true;
+  });
+  return mask;
+}
+
+// Whether every integral chain of P stays within +-2^53 -- where a double is the long, and short of where Java's
+// TimeUnit saturates -- at its column, at every intermediate value and at its result.  range(c, &lo, &hi) gives the
+// least and greatest value of column c of P.col[] (a sorted dictionary's ends) and answers false for a column that
+// holds no integers (FLOAT / DOUBLE: its chain is plain double arithmetic) or no values.  Every constant is positive,
+// so a chain is monotone and its ends are those of its values; the arithmetic is exact (overflow is detected).
+template <typename Range>
+inline bool expr_chains_exact(const ExprProg& P, Range&& range) {
+  constexpr int64_t kExact = 1ll << 53;
+  return expr_walk_chains(P, [&](ExprChain& e, int op, int64_t n) {
+    if (e.len == 0) {
+      e.live = range(e.col, &e.lo, &e.hi);
+      if (e.live && (e.lo < -kExact || e.hi > kExact)) return false;
+    }
+    if (!e.live) return true;
+    if (op == EXPR_LDIV) {
+      e.lo /= n;
+      e.hi /= n;
+    } else if (__builtin_mul_overflow(e.lo, n, &e.lo) || __builtin_mul_overflow(e.hi, n, &e.hi)) {
+      return false;
+    }
+    return e.lo >= -kExact && e.hi <= kExact;
+  });
 }
 
 // A comparison's outcomes as a mask over (a < b, a == b, a > b) in the total order: bits 0, 1, 2.
@@ -242,10 +406,30 @@ PGPU_HD inline void expr_stack_op(int op, double (&s0)[N], double (&s1)[N], doub
       s0[b] = s0[b] != 0.0 ? s1[b] : s2[b];
       s1[b] = s3[b];
     }
-  } else {
+  } else if (op < EXPR_SELECT) {
 #pragma unroll
     for (int b = 0; b < N; ++b) {
       s0[b] = expr_logic(op, s1[b], s0[b]);
+      s1[b] = s2[b];
+      s2[b] = s3[b];
+    }
+  } else if (op < EXPR_SQRT) {  // (the math and time ops last: the programs without them fetch what they fetched)
+#pragma unroll
+    for (int b = 0; b < N; ++b) s0[b] = expr_unary(op, s0[b]);
+  } else if (op == EXPR_SQRT) {  // (the long sequences each behind a branch of their own)
+#pragma unroll
+    for (int b = 0; b < N; ++b) s0[b] = expr_unary(EXPR_SQRT, s0[b]);
+  } else if (op == EXPR_LDIV) {
+#pragma unroll
+    for (int b = 0; b < N; ++b) {
+      s0[b] = expr_divide(EXPR_LDIV, s1[b], s0[b]);
+      s1[b] = s2[b];
+      s2[b] = s3[b];
+    }
+  } else {
+#pragma unroll
+    for (int b = 0; b < N; ++b) {
+      s0[b] = expr_divide(EXPR_MOD, s1[b], s0[b]);
       s1[b] = s2[b];
       s2[b] = s3[b];
     }

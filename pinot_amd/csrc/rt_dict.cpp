@@ -288,6 +288,19 @@ int ensure_derived(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
       return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s: the operands' dictionaries of segment %lld have more "
                   "than %lld combinations", ge.name.c_str(), (long long)s.handle, (long long)kGroupExprMaxProduct);
   }
+  {  // the integral chains (time conversions, long divisions) within +-2^53, as check_compared_longs has them for a plan
+    auto range = [&](int c, int64_t* lo, int64_t* hi) {
+      const int oc = ge.prog.col[c];
+      const std::vector<int64_t>& iv = s.cols[oc].dict.iv;
+      if ((t->types[oc] != PGPU_INT && t->types[oc] != PGPU_LONG) || iv.empty()) return false;
+      *lo = iv.front();
+      *hi = iv.back();
+      return true;
+    };
+    if (!expr_chains_exact(ge.prog, range))
+      return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s: a time conversion or long division leaves +-2^53 over the "
+                  "values of segment %lld", ge.name.c_str(), (long long)s.handle);
+  }
   for (int c = 0; c < ge.prog.ncols; ++c) {
     const int oc = ge.prog.col[c];
     TRY(ensure_values(t, s, oc, stream));

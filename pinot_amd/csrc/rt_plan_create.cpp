@@ -105,6 +105,22 @@ int check_compared_longs(PlanCtx& cx, const ExprProg& prog) {
         return fail(PGPU_ERR_UNSUPPORTED, "expression compares LONG column %d, whose values go beyond +-2^53", col);
     }
   }
+  // The integral chains (timeConvert, dateTimeConvert: x * n and the truncating x / n over an INT / LONG column) are the
+  // reference's long arithmetic only while every value stays within +-2^53: run over the ends of each planned
+  // segment's dictionary (expr_chains_exact).
+  for (const Segment* s : cx.P->segs) {
+    auto range = [&](int c, int64_t* lo, int64_t* hi) {
+      const int col = prog.col[c];
+      const std::vector<int64_t>& iv = s->cols[col].dict.iv;
+      if ((cx.t->types[col] != PGPU_INT && cx.t->types[col] != PGPU_LONG) || iv.empty()) return false;
+      *lo = iv.front();
+      *hi = iv.back();
+      return true;
+    };
+    if (!expr_chains_exact(prog, range))
+      return fail(PGPU_ERR_UNSUPPORTED, "expression: a time conversion or long division leaves +-2^53 over the values of "
+                  "segment %lld, where the reference's long arithmetic is no longer a double's", (long long)s->handle);
+  }
   return 0;
 }
 

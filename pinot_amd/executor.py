@@ -313,6 +313,18 @@ class GpuTable:
                 raise KeyError("unknown column %r" % c)
         return [(op, self.names.index(c) if c is not None else 0, lit) for op, c, lit in expr_program(tree, types)], types
 
+    def _check_long_leaves(self, f, exprs):
+        """ValueError for a predicate on a LONG-typed expression (a time function, a CASE over INT / LONG branches) whose
+        literal is no long (query.long_literal_text)."""
+        from .query import FilterContext, LONG, expr_type, long_predicate
+        if f.type != FilterContext.PREDICATE:
+            for k in f.children:
+                self._check_long_leaves(k, exprs)
+        elif f.predicate.column in exprs:
+            types = {n: L.TYPE_NAME_OF[t] for n, t in zip(self.names, self.types)}
+            if expr_type(exprs[f.predicate.column], types) == LONG:
+                long_predicate(f.predicate)
+
     def expression(self, column):
         """pgpu_table_expression: a virtual column's (ops, name), ops as (op, column index, literal) triples."""
         n = ctypes.c_int32()
@@ -334,6 +346,8 @@ class GpuTable:
             if col in exprs and col not in self.index and fn != "COUNT":
                 ops, _ = self._expr_ops(exprs[col])
                 self.index[col] = self.add_expression(ops, col)
+        if query.filter is not None and exprs:  # a LONG-typed left-hand side reads its literals as longs
+            self._check_long_leaves(query.filter, exprs)
         # group-by expressions: derived columns, under a key of their own -- SUM(a*b) .. GROUP BY a*b uses both the
         # virtual column mult(a,b) and the derived column ("group", mult(a,b)) -- typed by the expression's result type
         for col in query.group_by:

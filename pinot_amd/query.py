@@ -118,6 +118,148 @@ INT, LONG, FLOAT, DOUBLE = "INT", "LONG", "FLOAT", "DOUBLE"  # the types of sect
 BOOLEAN = "BOOLEAN"
 
 
+# Math and time functions (SingleParamMathTransformFunction, ModuloTransformFunction, TimeConversionTransformFunction,
+# DateTimeConversionTransformFunction epoch to epoch).  Nodes: ("abs" | "ceil" | "floor" | "sqrt", [x]), ("mod", [a, b]),
+# ("timeconvert", [col, ("str", in unit), ("str", out unit)]) and ("datetimeconvert", [col, ("str", in format),
+# ("str", out format), ("str", granularity)]); a ("str", text) leaf is a string argument as it was written.
+_MATH_FUNCTIONS = {"ABS": "abs", "CEIL": "ceil", "FLOOR": "floor", "SQRT": "sqrt"}
+_MATH_OPCODE = {"abs": L.EXPR_ABS, "ceil": L.EXPR_CEIL, "floor": L.EXPR_FLOOR, "sqrt": L.EXPR_SQRT}
+_TIME_FUNCTIONS = {"TIMECONVERT": "timeconvert", "DATETIMECONVERT": "datetimeconvert"}
+_DECLINED_FUNCTIONS = {"EXP": "Math.exp", "LN": "Math.log"}
+_LEAVES = ("col", "lit", "str")
+# java.util.concurrent.TimeUnit in nanoseconds; WEEKS is CustomTimeUnitTransformer's / DateTimeTransformUnit's, an output
+# unit only: the milliseconds divided by 604800000
+_UNIT_NANOS = {"NANOSECONDS": 1, "MICROSECONDS": 1000, "MILLISECONDS": 10 ** 6, "SECONDS": 10 ** 9,
+               "MINUTES": 60 * 10 ** 9, "HOURS": 3600 * 10 ** 9, "DAYS": 86400 * 10 ** 9}
+_WEEK_MILLIS = 604800000
+_CALENDAR_UNITS = ("WEEKS", "MONTHS", "YEARS")
+_EXACT = 2 ** 53
+
+
+def transform_function_name(fn):
+    """The canonical key of a transform function's name: upper case, underscores dropped (TIME_CONVERT is TIMECONVERT),
+    as the reference's TransformFunctionFactory normalises it -- for the math and time functions only; the arithmetic and
+    comparison names keep their underscores (NOT_EQUALS)."""
+    up = fn.upper().replace("_", "")
+    return up if up in _MATH_FUNCTIONS or up in _TIME_FUNCTIONS or up in _DECLINED_FUNCTIONS or up == "MOD" else fn.upper()
+
+
+def _positive_int(text, what):
+    if not re.fullmatch(r"\d+", text) or int(text) < 1:
+        raise ValueError("%s: size %r is not a positive integer" % (what, text))
+    return int(text)
+
+
+def _epoch_format(text, what, output):
+    """(size, unit) of 'n:UNIT:EPOCH'."""
+    parts = text.split(":")
+    if len(parts) >= 3 and parts[2].upper() == "SIMPLE_DATE_FORMAT":
+        raise ValueError("%s: SIMPLE_DATE_FORMAT in %r: its values are strings, only EPOCH formats are supported" % (what, text))
+    if len(parts) != 3 or parts[2].upper() != "EPOCH":
+        raise ValueError("%s: %r is no format 'size:UNIT:EPOCH'" % (what, text))
+    size, unit = _positive_int(parts[0], what), parts[1].upper()
+    _check_unit(unit, what, output)
+    return size, unit
+
+
+def _check_unit(unit, what, output):
+    if unit in _CALENDAR_UNITS and not (output and unit == "WEEKS"):
+        raise ValueError("%s: %s as the %s unit is not supported (%s)" % (
+            what, unit, "output" if output else "input",
+            "MONTHS and YEARS need the calendar" if output else "WEEKS, MONTHS and YEARS are output units only"))
+    if unit not in _UNIT_NANOS and unit != "WEEKS":
+        raise ValueError("%s: unknown time unit %r (NANOSECONDS .. DAYS%s)" % (what, unit, ", WEEKS" if output else ""))
+
+
+def _to_millis(unit):
+    """TimeUnit.toMillis as a chain step."""
+    nanos = _UNIT_NANOS[unit]
+    return ("mult", nanos // 10 ** 6) if nanos >= 10 ** 6 else ("ldiv", 10 ** 6 // nanos)
+
+
+def _from_millis(unit):
+    """TimeUnit.convert(ms, MILLISECONDS) / DateTimeTransformUnit.fromMillis as a chain step."""
+    if unit == "WEEKS":
+        return ("ldiv", _WEEK_MILLIS)
+    nanos = _UNIT_NANOS[unit]
+    return ("ldiv", nanos // 10 ** 6) if nanos >= 10 ** 6 else ("mult", 10 ** 6 // nanos)
+
+
+def time_chain(tree):
+    """The long arithmetic of a time node over its column as [("mult" | "ldiv", n)], n a positive integer: what the
+    program does after pushing the column (x, LITERAL n, MULT / LDIV each).  Steps by 1 are dropped and adjacent
+    multiplications folded into one constant; divisions stay apart, so the same arguments always give the same program.
+    timeconvert is TimeUnit.convert -- one multiplication where the output unit is finer, one truncating division where
+    it is coarser -- or, to WEEKS, toMillis and / 604800000 (CustomTimeUnitTransformer).  datetimeconvert is
+    EpochToEpochTransformer's order: x * n, toMillis, / G * G with G the granularity in milliseconds, fromMillis, / m."""
+    what = tree[0].upper()
+    if tree[0] == "timeconvert":
+        unit_in, unit_out = tree[1][1][1].upper(), tree[1][2][1].upper()
+        _check_unit(unit_in, what, False)
+        _check_unit(unit_out, what, True)
+        if unit_out == "WEEKS":
+            steps = [_to_millis(unit_in), ("ldiv", _WEEK_MILLIS)]
+        else:
+            a, b = _UNIT_NANOS[unit_in], _UNIT_NANOS[unit_out]
+            steps = [("mult", a // b)] if a >= b else [("ldiv", b // a)]
+    else:
+        n, unit_in = _epoch_format(tree[1][1][1], what, False)
+        m, unit_out = _epoch_format(tree[1][2][1], what, True)
+        gran = tree[1][3][1].split(":")
+        if len(gran) != 2:
+            raise ValueError("%s: %r is no granularity 'size:UNIT'" % (what, tree[1][3][1]))
+        gsize, gunit = _positive_int(gran[0], what), gran[1].upper()
+        if gunit not in _UNIT_NANOS:
+            raise ValueError("%s: unknown granularity unit %r (NANOSECONDS .. DAYS)" % (what, gunit))
+        # DateTimeGranularitySpec.granularityToMillis: TimeUnit.MILLISECONDS.convert(size, unit), truncating
+        g = gsize * _UNIT_NANOS[gunit] // 10 ** 6
+        if g < 1:
+            raise ValueError("%s: granularity %s is below one millisecond (the reference divides by zero)" % (what, tree[1][3][1]))
+        steps = [("mult", n), _to_millis(unit_in), ("ldiv", g), ("mult", g), _from_millis(unit_out), ("ldiv", m)]
+    out = []
+    for kind, k in steps:
+        if k == 1:
+            continue
+        if kind == "mult" and out and out[-1][0] == "mult":
+            out[-1] = ("mult", out[-1][1] * k)
+        else:
+            out.append((kind, k))
+    for kind, k in out:
+        if k > _EXACT:
+            raise ValueError("%s: the constant %d is beyond 2^53" % (what, k))
+    return out
+
+
+def math_node(name, args):
+    """abs / ceil / floor / sqrt of one number that is no literal; mod of two numbers (either may be a literal)."""
+    if name == "mod":
+        if len(args) != 2:
+            raise ValueError("MOD takes exactly 2 arguments, got %d" % len(args))
+        return ("mod", [_number(a, "MOD") for a in args])
+    if len(args) != 1:
+        raise ValueError("%s takes exactly 1 argument, got %d" % (name.upper(), len(args)))
+    if args[0][0] == "lit":
+        raise ValueError("%s of the literal %s: its argument is a column or an expression" % (name.upper(), args[0][1]))
+    return (name, [_number(args[0], name.upper())])
+
+
+def time_node(name, args):
+    """timeconvert(col, 'IN', 'OUT') / datetimeconvert(col, 'n:UNIT:EPOCH', 'm:UNIT:EPOCH', 'g:UNIT') over a column (INT
+    or LONG: expr_program checks where it knows the types); every other shape is declined by name."""
+    want = 3 if name == "timeconvert" else 4
+    if len(args) != want:
+        raise ValueError("%s takes exactly %d arguments, got %d" % (name.upper(), want, len(args)))
+    if args[0][0] != "col":
+        raise ValueError("%s over %s: its first argument is an INT or LONG column (the reference casts a nested "
+                         "function's value to long, and there is no cast)" % (name.upper(), expr_name(args[0])))
+    for a in args[1:]:
+        if a[0] != "str":
+            raise ValueError("%s: argument %s is no string literal" % (name.upper(), expr_name(a)))
+    tree = (name, list(args))
+    time_chain(tree)  # (declines what it cannot lower)
+    return tree
+
+
 class _Lit(str):
     """A literal's name in arithmetic (the double's shortest form, as before) that remembers the text it was read
     from: a comparison or a CASE branch types its literal operands by that text (0 is not 0.0)."""
@@ -268,10 +410,22 @@ def expr_node(fn, args):
                              "supported), got %d" % len(args))
         n = (len(args) - 1) // 2
         return case_node(args[:n], args[n:2 * n], args[2 * n])
+    key = transform_function_name(fn)
+    if key in _DECLINED_FUNCTIONS:
+        raise ValueError("%s is not supported: Java's %s is not correctly rounded, so its bits cannot be promised"
+                         % (key, _DECLINED_FUNCTIONS[key]))
+    if key in _MATH_FUNCTIONS or key == "MOD":
+        return math_node(_MATH_FUNCTIONS.get(key, "mod"), args)
+    if key in _TIME_FUNCTIONS:
+        return time_node(_TIME_FUNCTIONS[key], args)
+    for a in args:
+        if a[0] == "str":
+            raise ValueError("string literal '%s' as an argument of %s" % (a[1], fn))
     name = _EXPR_FUNCTIONS.get(up)
     if name is None:
         raise ValueError("unknown function %s in an aggregation's argument (ADD, SUB, MULT, DIV and their aliases "
-                         "PLUS, MINUS, TIMES, DIVIDE, the comparison functions, AND, OR and CASE are supported)" % fn)
+                         "PLUS, MINUS, TIMES, DIVIDE, the comparison functions, AND, OR, CASE, ABS, CEIL, FLOOR, SQRT, MOD, "
+                         "TIMECONVERT and DATETIMECONVERT are supported)" % fn)
     if name in ("sub", "div") and len(args) != 2:
         raise ValueError("%s takes exactly 2 arguments, got %d" % (name.upper(), len(args)))
     if len(args) < 2:
@@ -297,7 +451,7 @@ def expr_columns(tree):
         if t[0] == "col":
             if t[1] not in out:
                 out.append(t[1])
-        elif t[0] != "lit":
+        elif t[0] not in _LEAVES:
             for a in t[1]:
                 walk(a)
     walk(tree)
@@ -306,7 +460,7 @@ def expr_columns(tree):
 
 def has_conditional(tree):
     """Whether a tree holds a comparison, AND / OR or a CASE: its program then depends on the columns' types."""
-    return tree[0] not in ("col", "lit") and (tree[0] in _BOOL_NODES + ("case",) or any(has_conditional(a) for a in tree[1]))
+    return tree[0] not in _LEAVES and (tree[0] in _BOOL_NODES + ("case",) or any(has_conditional(a) for a in tree[1]))
 
 
 def _widen(a, b):
@@ -338,6 +492,8 @@ def expr_type(tree, types):
         return r
     if _is_bool(tree):
         return BOOLEAN
+    if tree[0] in ("timeconvert", "datetimeconvert"):
+        return LONG
     return DOUBLE
 
 
@@ -352,6 +508,8 @@ def expr_name(tree):
     """The expression in the reference's function form: mult(price,qty), add(div(a,b),2.5)."""
     if tree[0] in ("col", "lit"):
         return tree[1]
+    if tree[0] == "str":  # (as the reference prints a string literal)
+        return "'%s'" % tree[1]
     return "%s(%s)" % (tree[0], ",".join(expr_name(a) for a in tree[1]))
 
 
@@ -445,6 +603,22 @@ def expr_program(tree, types=None):
             emit_case(t)
         elif _is_bool(t):
             raise ValueError("boolean %s used as a number" % expr_name(t))
+        elif t[0] in _MATH_OPCODE:
+            emit(t[1][0])
+            ops.append((_MATH_OPCODE[t[0]], None, 0.0))
+        elif t[0] == "mod":
+            emit(t[1][0])
+            emit(t[1][1])
+            ops.append((L.EXPR_MOD, None, 0.0))
+        elif t[0] in ("timeconvert", "datetimeconvert"):
+            col = t[1][0][1]
+            if types is not None and not isinstance(types, _AnyDouble) and expr_type(t[1][0], types) not in (INT, LONG):
+                raise ValueError("%s over %s column %s: its first argument is an INT or LONG column (the reference "
+                                 "casts the value to long, and there is no cast)" % (t[0].upper(), expr_type(t[1][0], types), col))
+            ops.append((L.EXPR_COLUMN, col, 0.0))
+            for kind, k in time_chain(t):
+                ops.append((L.EXPR_LITERAL, None, float(k)))
+                ops.append((L.EXPR_MULT if kind == "mult" else L.EXPR_LDIV, None, 0.0))
         elif t[0] in ("sub", "div"):
             emit(t[1][0])
             emit(t[1][1])
@@ -478,7 +652,8 @@ def check_expr_limits(tree):
     ops = expr_program(tree, _AnyDouble())  # (the count does not depend on the column types)
     depth = most = 0
     for op, _, _ in ops:
-        depth += 1 if op in (L.EXPR_COLUMN, L.EXPR_LITERAL) else -2 if op == L.EXPR_SELECT else -1
+        depth += 1 if op in (L.EXPR_COLUMN, L.EXPR_LITERAL) else -2 if op == L.EXPR_SELECT else \
+            0 if L.EXPR_ABS <= op <= L.EXPR_SQRT else -1
         most = max(most, depth)
     name = expr_name(tree)
     hint = "; the n-ary forms ADD(x1, .., xn) / MULT(x1, .., xn) take one op per argument more and no nesting"
@@ -492,9 +667,26 @@ def check_expr_limits(tree):
         raise ValueError("expression %s names %d columns, more than %d" % (name, len(expr_columns(tree)), L.EXPR_MAX_COLUMNS))
 
 
+def long_literal_text(text, where):
+    """Long.parseLong of a predicate's literal, as the reference's raw LONG predicate evaluators read it
+    (EqualsPredicateEvaluatorFactory.java:63-64: a decimal or a value past int64 is its BadQueryRequestException), given
+    back as the decimal text that is passed on.  Within +-2^53, where the plan keeps such an expression, comparing the
+    doubles is comparing the longs."""
+    text = str(text).strip()
+    if not re.fullmatch(r"[+-]?\d+", text) or not -2 ** 63 <= int(text) < 2 ** 63:
+        raise ValueError("%r is no LONG literal: %s is LONG-typed and compares with integers that fit int64" % (text, where))
+    return str(int(text))
+
+
+def long_predicate(p):
+    """Predicate p, whose left-hand side is LONG-typed, with every literal read by long_literal_text."""
+    vals = [v if (p.type == RANGE and v == UNBOUNDED) else long_literal_text(v, p.column) for v in p.values]
+    return Predicate(p.type, p.column, vals, p.lower_inclusive, p.upper_inclusive)
+
+
 def _check_expr(tree):
     """Every function node needs a column somewhere below it: a literal-only (sub)expression is not evaluated here."""
-    if tree[0] in ("col", "lit"):
+    if tree[0] in _LEAVES:
         return
     if not expr_columns(tree):
         raise ValueError("literal-only expression %s: an expression needs a column operand" % expr_name(tree))
@@ -876,7 +1068,9 @@ class _Parser:
             return False
         if self.peek(1) == ("op", "("):
             up = tok[1].upper()
-            return up in _EXPR_FUNCTIONS or up in _CMP_FUNCTIONS or up in ("AND", "OR", "CASE")
+            key = transform_function_name(up)
+            return up in _EXPR_FUNCTIONS or up in _CMP_FUNCTIONS or up in ("AND", "OR", "CASE") or key == "MOD" or \
+                key in _MATH_FUNCTIONS or key in _TIME_FUNCTIONS or key in _DECLINED_FUNCTIONS
         return self.peek(1) in _ARITH_OPS
 
     def group_expr_item(self):
@@ -977,10 +1171,12 @@ class _Parser:
         if tok[0] == "id" and self.peek(1) == ("op", "("):
             fn = self.take("id")
             self.take("op", "(")
+            # (the unit and format arguments of the time functions are string literals, which arithmetic has none of)
+            strings = transform_function_name(fn) in _TIME_FUNCTIONS
             args = [self.arith()]
             while self.peek() == ("op", ","):
                 self.take("op", ",")
-                args.append(self.arith())
+                args.append(("str", self.take("lit")) if strings and self.peek()[0] == "lit" else self.arith())
             self.take("op", ")")
             return expr_node(fn, args)
         return ("col", self.take("id"))
@@ -1116,6 +1312,14 @@ class _Parser:
         return self.predicate()
 
     def predicate(self):
+        f = self.predicate_of()
+        tree = self.exprs.get(f.predicate.column)
+        # a time function on the left is LONG whatever its column is (a CASE's type waits for the column types: query_c)
+        if tree is not None and tree[0] in ("timeconvert", "datetimeconvert"):
+            f.predicate = long_predicate(f.predicate)
+        return f
+
+    def predicate_of(self):
         col = self.predicate_lhs()
         if self.kw("BETWEEN"):
             self.take("id")

@@ -4,7 +4,9 @@ SUM(mult(a,b)); SUM(add(div(a,b),div(c,d))) -- each under C3's selective filter 
 the sparse shape, instance 12 for an expression), under the day range alone (2 %) and with no filter at all, where
 SUM(md) takes the whole-group (dense) instance 1 and an expression plan instance 13 -- and, for the comparison of the
 two expression instances on the same scan, the unfiltered queries once more with dense_selectivity raised so that
-they run the sparse instances.  Plans are warmed, then timed in
+they run the sparse instances.  Two sums over the math ops ride along, SUM(floor(a / 10)) and SUM(mod(a, 7)); with PGPU_LIB
+naming a library from before those ops they are skipped and the others measure that library's evaluator.  Plans are
+warmed, then timed in
 alternation --repeats times of --steps executions each (PGPU_OPT_TIMING events: the whole execution and its scan
 launch).  Bytes per matched doc are what the forms gather: per operand a dictId (4-byte window of the forward index)
 and its 8-byte double.  Prints one JSON line.
@@ -20,8 +22,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SUMS = {"md": "SUM(md)", "mult": "SUM(mult(a,b))", "add_div_div": "SUM(add(div(a,b),div(c,d)))"}
-OPERANDS = {"md": 1, "mult": 2, "add_div_div": 4}
+SUMS = {"md": "SUM(md)", "mult": "SUM(mult(a,b))", "add_div_div": "SUM(add(div(a,b),div(c,d)))",
+        "floor_div": "SUM(floor(a / 10))", "mod": "SUM(mod(a, 7))"}
+OPERANDS = {"md": 1, "mult": 2, "add_div_div": 4, "floor_div": 1, "mod": 1}
+NEW = ("floor_div", "mod")  # (the ops a parent library answers "unknown op" to)
 FILTERS = {"c3": " WHERE daysSinceEpoch BETWEEN 17849 AND 17856 AND accountId IN (123456789)",
            "days": " WHERE daysSinceEpoch BETWEEN 17849 AND 17856", "all": "", "all_sparse": ""}
 CONFIG = {"all_sparse": {"dense_selectivity": 2.0}}  # (no plan's estimate reaches it: the sparse instances)
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
+    from pinot_amd import _lib as L
     from pinot_amd.executor import GpuTable
     from pinot_amd.query import parse_query
     from pinot_amd.workloads import account_ids, double_table, zipf_cdf
@@ -61,7 +66,7 @@ def main():
     current = [None]
 
     def run(name, describe=False):
-        f = name.split("_" + [s for s in SUMS if name.endswith("_" + s)][0])[0]
+        f = name[:-len("_" + max((s for s in SUMS if name.endswith("_" + s)), key=len))]
         if current[0] != f:  # (a change of settings clears the plan cache: once per block of runs)
             t.reset_config()
             if f in CONFIG:
@@ -75,14 +80,21 @@ def main():
             return r.as_dict(), {"group_path": p.group_path(), "variant": p.scan_geometry()["variant"],
                                  "docs_scanned": r.stats.as_tuple()[0], "entries_post_filter": r.stats.as_tuple()[2]}
 
-    info, results = {}, {}
-    for name in queries:
-        for _ in range(args.warmup):
-            run(name)
+    info, results, skipped = {}, {}, []
+    for name in list(queries):
+        try:
+            for _ in range(args.warmup):
+                run(name)
+        except L.PinotGpuError:  # a library without the math ops: "unknown op"
+            if not name.endswith(tuple("_" + s for s in NEW)):
+                raise
+            skipped.append(name)
+            del queries[name]
+            continue
         results[name], info[name] = run(name, describe=True)
     for f in FILTERS:  # the same groups and counts whatever is summed
-        counts = [{k: v[1] for k, v in results["%s_%s" % (f, s)].items()} for s in SUMS]
-        assert counts[0] == counts[1] == counts[2]
+        counts = [{k: v[1] for k, v in results["%s_%s" % (f, s)].items()} for s in SUMS if "%s_%s" % (f, s) in results]
+        assert all(c == counts[0] for c in counts)
     pairs = []
     for _ in range(args.repeats):
         pair = {}
@@ -91,7 +103,8 @@ def main():
             pair[name] = (statistics.median(x[0] for x in runs), statistics.median(x[1] for x in runs))
         pairs.append(pair)
     med = {n_: (statistics.median(p[n_][0] for p in pairs), statistics.median(p[n_][1] for p in pairs)) for n_ in queries}
-    out = {"tool": "expr_cost", "queries": sql, "segments": args.segments, "docs_per_segment": args.docs,
+    out = {"tool": "expr_cost", "library": os.environ.get("PGPU_LIB", "in-tree"), "queries": sql, "skipped": skipped,
+           "segments": args.segments, "docs_per_segment": args.docs,
            "steps": args.steps, "repeats": args.repeats,
            "gathered_bytes_per_matched_doc": {s: 12 * k for s, k in OPERANDS.items()}}
     for name in queries:
@@ -99,8 +112,9 @@ def main():
         out["scan_us_" + name] = med[name][1]
         out["plan_" + name] = info[name]
     for f in FILTERS:
-        for s in ("mult", "add_div_div"):
-            out["scan_ratio_%s_%s" % (f, s)] = med["%s_%s" % (f, s)][1] / med["%s_md" % f][1]
+        for s in SUMS:
+            if s != "md" and "%s_%s" % (f, s) in med:
+                out["scan_ratio_%s_%s" % (f, s)] = med["%s_%s" % (f, s)][1] / med["%s_md" % f][1]
     out["pairs_us"] = [{n_: list(p[n_]) for n_ in p} for p in pairs]
     print(json.dumps(out))
     t.close()

@@ -11,6 +11,9 @@ width -- r3 (3 values, 2 bits) beside the one-operand CASE over a, rp beside the
           ordinary dictionary column to the scan); the times are recorded.  Plans are warmed, then timed in alternation
           --repeats times of --steps executions each (PGPU_OPT_TIMING events: the whole execution and its scan launch).
 
+A time bucket rides along: GROUP BY datetimeconvert(ts, milliseconds -> hours) over a LONG column of milliseconds spanning 48 hours beside
+the real column rh of its 48 values; with PGPU_LIB naming a library from before the time ops it is skipped.
+
 Prints one JSON line.
 
     python tools/group_expr_cost.py --segments 20 --docs 1000000
@@ -28,9 +31,11 @@ sys.path.insert(0, ROOT)
 os.environ["PGPU_TRACE"] = ",".join(filter(None, [os.environ.get("PGPU_TRACE"), "derive"]))  # before the library loads
 
 CASE = "CASE WHEN a < 180 THEN 0 WHEN a < 650 THEN 1 ELSE 2 END"
-KEYS = {"case": CASE, "real3": "r3", "prod": "p * s", "realp": "rp"}
-PAIRS = {"case": "real3", "prod": "realp"}
-OPERAND_COLUMNS = {"case": ["a"], "prod": ["p", "s"]}
+HOURS = "datetimeconvert(ts,'1:MILLISECONDS:EPOCH','1:HOURS:EPOCH','1:HOURS')"
+KEYS = {"case": CASE, "real3": "r3", "prod": "p * s", "realp": "rp", "hours": HOURS, "realh": "rh"}
+PAIRS = {"case": "real3", "prod": "realp", "hours": "realh"}
+OPERAND_COLUMNS = {"case": ["a"], "prod": ["p", "s"], "hours": ["ts"]}
+NEW = ("hours",)  # (the ops a parent library answers "unknown op" to)
 FILTERS = {"c3": " WHERE daysSinceEpoch BETWEEN 17849 AND 17856 AND accountId IN (123456789)", "all": ""}
 TRACE = re.compile(r"\[pgpu\] derive (\S+) segment (\d+) docs (\d+) candidates (\d+) unique (\d+) card (\d+) bits (\d+) "
                    r"fwd_bytes (\d+): candidates_us ([\d.]+) ids_us ([\d.]+) pack_us ([\d.]+) build_us ([\d.]+)")
@@ -62,20 +67,24 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
+    from pinot_amd import _lib as L
     from pinot_amd.executor import GpuTable
     from pinot_amd.query import parse_query
     from pinot_amd.workloads import account_ids, zipf_cdf
     n = 100_000
     products = len({x * y for x in range(30) for y in range(1, 30)})
     schema = [("daysSinceEpoch", "INT"), ("accountId", "INT"), ("a", "INT"), ("p", "INT"), ("s", "INT"), ("r3", "INT"),
-              ("rp", "INT")]
+              ("rp", "INT"), ("ts", "LONG"), ("rh", "INT")]
     gen = [{"kind": "UNIFORM", "column_index": 0, "lo": 17532, "hi": 17897},
            {"kind": "ZIPF", "column_index": 1, "cdf": zipf_cdf(n), "ids": account_ids(n)},
            {"kind": "UNIFORM", "column_index": 2, "lo": 0, "hi": 1000},
            {"kind": "UNIFORM", "column_index": 3, "lo": 0, "hi": 30},
            {"kind": "UNIFORM", "column_index": 4, "lo": 1, "hi": 30},
            {"kind": "UNIFORM", "column_index": 5, "lo": 0, "hi": 3},
-           {"kind": "UNIFORM", "column_index": 6, "lo": 0, "hi": products}]
+           {"kind": "UNIFORM", "column_index": 6, "lo": 0, "hi": products},
+           # milliseconds over 48 hours from 2017-09-20T00:00Z: nearly every doc its own value, 48 one-hour buckets
+           {"kind": "UNIFORM", "column_index": 7, "lo": 1505865600000, "hi": 1505865600000 + 48 * 3600000},
+           {"kind": "UNIFORM", "column_index": 8, "lo": 0, "hi": 48}]
     t = GpuTable(schema)
     hs = [t.generate_segment(gen, row0=i * args.docs, num_docs=args.docs) for i in range(args.segments)]
     sql, queries = {}, {}
@@ -87,14 +96,25 @@ def main():
             queries[name].timing = True
 
     # ---- build: the first plan that names an expression builds its derived column in every segment
-    out = {"tool": "group_expr_cost", "queries": sql, "segments": args.segments, "docs_per_segment": args.docs,
+    out = {"tool": "group_expr_cost", "library": os.environ.get("PGPU_LIB", "in-tree"), "queries": sql, "segments": args.segments, "docs_per_segment": args.docs,
            "steps": args.steps, "repeats": args.repeats}
-    bits_of = {c: t.segment_column_bytes(hs[0], c)[1] for c in ("a", "p", "s", "r3", "rp")}
-    for k in PAIRS:
+    bits_of = {c: t.segment_column_bytes(hs[0], c)[1] for c in ("a", "p", "s", "r3", "rp", "ts")}
+    skipped = []
+    for k in list(PAIRS):
         before = t.device_bytes()
-        with CaptureStderr() as cap:
-            with t.plan(hs, queries["all_" + k]):
-                pass
+        try:
+            with CaptureStderr() as cap:
+                with t.plan(hs, queries["all_" + k]):
+                    pass
+        except L.PinotGpuError:  # a library without the time ops: "unknown op"
+            if k not in NEW:
+                raise
+            for f in FILTERS:
+                for name in ("%s_%s" % (f, k), "%s_%s" % (f, PAIRS[k])):
+                    skipped.append(name)
+                    del queries[name]
+            del PAIRS[k]
+            continue
         lines = [m.groups() for m in map(TRACE.search, cap.text.split("\n")) if m]
         assert len(lines) == args.segments, cap.text[-2000:]
         med = lambda i: statistics.median(float(x[i]) for x in lines)  # noqa: E731
@@ -107,6 +127,8 @@ def main():
             "candidates_kernel_us": med(8), "ids_kernel_us": med(9), "pack_kernel_us": med(10), "build_us": med(11),
             "ids_bytes_moved": moved, "ids_gb_per_s": moved / med(9) / 1e3 if med(9) else None}
         assert (card, bits) == tuple(t.segment_column_bytes(hs[0], KEYS[PAIRS[k]])[:2]), "the real column's cardinality and bits"
+
+    out["skipped"] = skipped
 
     # ---- query
     def run(name, describe=False):
