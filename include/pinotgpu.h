@@ -195,13 +195,45 @@ int pgpu_unpack_fixed_bit_device(const void* d_fwd, int64_t fwd_len, int32_t bit
  * pipelines, pgpu_filter_bitmap; one launch, never streamed).  Its operands are filter columns: they do not count in
  * numEntriesScannedPostFilter.  numEntriesScannedInFilter counts it as ExpressionScanDocIdIterator does
  * (PGPU_LEAF_EXPRESSION below).  Declined as for expression aggregations (STRING, raw or virtual operands:
- * PGPU_ERR_UNSUPPORTED, the message names "expression"). */
+ * PGPU_ERR_UNSUPPORTED, the message names "expression").
+ *
+ * PGPU_PRED_REGEXP_LIKE: REGEXP_LIKE(col, 'p'), and col LIKE 'p' after the reference's conversion of the LIKE pattern
+ * (RegexpPatternConverterUtils.likeToRegexpLike; RequestContextUtils.java:230-236, 326-331).  num_values is 1 and
+ * values[0] the Java pattern text; the column is a STRING dictionary column of the table's own.  The reference
+ * evaluates Pattern.compile(p, CASE_INSENSITIVE | UNICODE_CASE).matcher(value).find() per scanned doc
+ * (RegexpLikePredicateEvaluatorFactory.java:64-80).  Here the pattern is compiled once into a DFA, the DFA runs once
+ * over the column's table-global dictionary on the GPU when the plan is made, and every planned segment's leaf is the
+ * set of its matching dictIds, read by the scan as an IN's is.  As in the reference without an FST index the leaf is
+ * always a scan leaf -- on a sorted column and on one with an inverted index too --, is never folded to match-all or
+ * empty (a pattern that matches nothing is still scanned and counted in numEntriesScannedInFilter), has the scan
+ * priority in an AND, and a filter that holds one never takes a star-tree.  The pattern is part of the query and so of
+ * the plan-cache key.
+ * The answer is the reference's or a decline, so only a subset of java.util.regex whose meaning is unambiguous is
+ * accepted: ASCII patterns of literals (letters match case-insensitively), '.', '^' and '$' anywhere, groups ( ) and
+ * (?: ), alternation (empty alternatives too), the greedy quantifiers * + ? {n} {n,} {n,m} with bounds <= 64, classes
+ * [..] and [^..] of single characters, backslash-escaped non-alphanumerics, \d \w \s \D \W \S, ranges whose ends are
+ * both digits, both lower-case or both upper-case letters, '-' first, last or escaped and '^' not first (a class
+ * matches case-insensitively, a negated class excludes both cases), and outside a class the escapes backslash +
+ * non-alphanumeric (that literal), \t, \d \D \w \W \s \S (Java's default ASCII meanings).  The empty pattern matches
+ * every value.
+ * Declined with PGPU_ERR_UNSUPPORTED (the message names REGEXP_LIKE and what was met): any other backslash + letter or
+ * digit (back-references, \b \B \A \z \Z \G \Q \E \p \P \x \u \0 \c \h \v \R \k, \n \r \f \a \e; inside a class \t
+ * too); a '(?' other than '(?:'; lazy and possessive quantifiers; a quantifier with nothing to repeat, after another
+ * quantifier, or applied to '^' / '$'; {,n}; {n,m} with n > m or a bound above 64; a '{' that does not open a
+ * well-formed quantifier; an unescaped ']' or '}' outside its construct; inside a class '[', '&&', a leading ']', any
+ * other range and any other '-'; a non-ASCII byte; a trailing backslash; unbalanced parentheses or brackets; groups
+ * nested deeper than 200; a pattern longer than 1024 bytes; repeats that unroll into more than 32768 NFA states; a DFA
+ * whose transition table (states x byte classes x 2 bytes) is above PGPU_REGEX_MAX_TABLE_BYTES, the table the kernel
+ * keeps in LDS.  Declined likewise: a column that is not STRING, a virtual or derived column, a raw column, a
+ * dictionary of 2^31 bytes, and a column whose global dictionary snapshot holds a value with a byte >= 0x80, a \n or a
+ * \r (within that limit UNICODE_CASE is ASCII folding, '.' matches every byte and '$' means the end of input). */
 enum pgpu_predicate_type { PGPU_PRED_EQ = 0, PGPU_PRED_NOT_EQ = 1, PGPU_PRED_IN = 2, PGPU_PRED_NOT_IN = 3,
-                           PGPU_PRED_RANGE = 4 };
+                           PGPU_PRED_RANGE = 4, PGPU_PRED_REGEXP_LIKE = 5 };
+#define PGPU_REGEX_MAX_TABLE_BYTES 32768
 typedef struct {
   int32_t type;
   int32_t column;             /* a table column, or a virtual column (an expression: see above) */
-  int32_t num_values;         /* EQ/NOT_EQ 1, IN/NOT_IN k, RANGE 2 (lower, upper) */
+  int32_t num_values;         /* EQ/NOT_EQ 1, IN/NOT_IN k, RANGE 2 (lower, upper), REGEXP_LIKE 1 (the pattern) */
   int32_t lower_inclusive;
   const char* const* values;
   int32_t upper_inclusive;
@@ -540,6 +572,20 @@ int pgpu_plan_cancel(pgpu_plan plan);
  * leaf kind (counts[9]: NONE, ALL, RANGE, SET, DOCRANGE, BITMAP (a docId bitmap materialised per query),
  * RAW_RANGE, RAW_IN, BITDIR (inverted-index containers read in place)). */
 int pgpu_plan_leaf_kinds(pgpu_plan plan, int64_t* counts);
+
+/* Diagnostics of PGPU_PRED_REGEXP_LIKE.  pgpu_regex_check compiles the pattern only: PGPU_OK with the DFA's states, byte
+ * classes and table bytes (each pointer may be NULL), or the decline with its message.  pgpu_regex_match_host runs the
+ * host interpreter of the same table over value[0, len) (*matched 0 / 1).  pgpu_table_regexp_dict_ids returns the
+ * table-global dictIds of a STRING column that match, as computed on the GPU: bit i of `bitmap` (`words` 64-bit words,
+ * at least ceil(dictionary size / 64); the spare bits are 0) is set when global dictId i matches.
+ * pgpu_plan_regexp_stats: what making the plan built for its REGEXP_LIKE leaves -- out4[0] the (segment, leaf) local
+ * sets written on the GPU, out4[1] how many of them went through an affine local-to-global mapping (no LUT read),
+ * out4[2] the device bytes of the leaves' dictionaries (blob + offsets, as counted in pgpu_table_device_bytes), out4[3]
+ * the bytes of their DFA tables. */
+int pgpu_plan_regexp_stats(pgpu_plan plan, int64_t* out4);
+int pgpu_regex_check(const char* pattern, int32_t* states, int32_t* classes, int64_t* table_bytes);
+int pgpu_regex_match_host(const char* pattern, const void* value, int64_t len, int32_t* matched);
+int pgpu_table_regexp_dict_ids(pgpu_table table, int32_t column, const char* pattern, uint64_t* bitmap, int64_t words);
 
 /* Diagnostics: the group-by path the plan's scan takes (a numGroupsLimit plan: its first part's).  LDS: tables
  * privatised per workgroup in LDS; GLOBAL: a dense table with global atomics; HASH: the global open-addressing hash

@@ -35,6 +35,8 @@ TYPE_NAMES = {"INT": INT, "LONG": LONG, "FLOAT": FLOAT, "DOUBLE": DOUBLE, "STRIN
 TYPE_NAME_OF = {v: k for k, v in TYPE_NAMES.items()}
 FWD_FIXED_BIT, FWD_SORTED_PAIRS, FWD_RAW_FIXED = 0, 1, 2
 PRED_EQ, PRED_NOT_EQ, PRED_IN, PRED_NOT_IN, PRED_RANGE = 0, 1, 2, 3, 4
+PRED_REGEXP_LIKE = 5  # REGEXP_LIKE(col, 'p'); col LIKE 'p' after query.like_to_regexp_like
+REGEX_MAX_TABLE_BYTES = 32768  # PGPU_REGEX_MAX_TABLE_BYTES
 OP_PRED, OP_AND, OP_OR, OP_NOT = 0, 1, 2, 3
 LEAF_KIND_NAMES = ("none", "all", "range", "set", "docrange", "bitmap", "raw_range", "raw_in", "bitdir")
 GROUP_PATH_NAMES = ("lds", "global", "hash", "partitioned", "hash_partitioned")  # enum pgpu_group_path
@@ -237,6 +239,10 @@ _PROTOS = {
     "pgpu_plan_layout": (c_int, [c_voidp, c_i32p, c_i64p, c_i32p]),
     "pgpu_plan_leaf_kinds": (c_int, [c_voidp, c_i64p]),
     "pgpu_plan_group_path": (c_int, [c_voidp, c_i32p]),
+    "pgpu_plan_regexp_stats": (c_int, [c_voidp, c_i64p]),
+    "pgpu_regex_check": (c_int, [ctypes.c_char_p, c_i32p, c_i32p, c_i64p]),
+    "pgpu_regex_match_host": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_i64, c_i32p]),
+    "pgpu_table_regexp_dict_ids": (c_int, [c_voidp, c_i32, ctypes.c_char_p, c_u64p, c_i64]),
     "pgpu_plan_cancel": (c_int, [c_voidp]),
     "pgpu_plan_execute": (c_int, [c_voidp, c_voidp, c_voidp]),
     "pgpu_plan_finalize": (c_int, [c_voidp, c_voidp, c_voidp, ctypes.POINTER(c_voidp)]),
@@ -377,6 +383,26 @@ def check(code):
     if code == PGPU_ERR_TIMEOUT:
         raise QueryTimeoutError(code, msg)
     raise PinotGpuError(code, msg)
+
+
+def regex_check(pattern):
+    """pgpu_regex_check: (states, byte classes, table bytes) of the DFA of `pattern` (bytes or str), or
+    UnsupportedQueryError with the decline's message.  Host only."""
+    lib = load()
+    raw = pattern if isinstance(pattern, bytes) else pattern.encode()
+    st, cl, tb = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    check(lib.pgpu_regex_check(raw, ctypes.byref(st), ctypes.byref(cl), ctypes.byref(tb)))
+    return st.value, cl.value, tb.value
+
+
+def regex_match_host(pattern, value):
+    """pgpu_regex_match_host: the host interpreter of the pattern's DFA on `value` (bytes or str)."""
+    lib = load()
+    raw = pattern if isinstance(pattern, bytes) else pattern.encode()
+    v = value if isinstance(value, bytes) else value.encode()
+    m = ctypes.c_int32(0)
+    check(lib.pgpu_regex_match_host(raw, v, len(v), ctypes.byref(m)))
+    return bool(m.value)
 
 
 def ptr(arr, ctype):

@@ -13,19 +13,20 @@ LIB_PATH = os.path.join(HERE, "libpinotgpu.so")
 # build in parallel.
 # the host runtime (rt.h): rt_* (core, dictionaries, planning, execution, finalize, numGroupsLimit / plan cache)
 # and the C ABI
-RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_plan_create", "rt_exec", "rt_finalize", "rt_groups", "abi_table",
-           "abi_plan", "abi_combine", "abi_result"]
+RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_plan_create", "rt_exec", "rt_finalize", "rt_groups", "rt_regex",
+           "abi_table", "abi_plan", "abi_combine", "abi_result"]
 SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTIME] + [("startree.cpp", [], "startree"),
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
            ("k_partition.hip", [], "k_partition"), ("k_partition_fx.hip", [], "k_partition_fx"),
-           ("k_hashfinal.hip", [], "k_hashfinal"), ("k_derive.hip", [], "k_derive")] + \
+           ("k_hashfinal.hip", [], "k_hashfinal"), ("k_derive.hip", [], "k_derive"),
+           ("regex_dfa.cpp", [], "regex_dfa"), ("k_regex.hip", [], "k_regex")] + \
     [("k_%s.hip" % k, ["-DPGPU_FAMILY=%d" % f, "-DPGPU_MODE=%d" % m], "k_%s%s_%d" % (k, ("", "_fx", "_dc", "_hist", "_expr")[f], m))
      for k, f, modes in (("direct", 0, 3), ("startree", 0, 3), ("direct", 1, 3), ("startree", 1, 3), ("direct", 2, 2),
                          ("direct", 3, 2), ("direct", 4, 3))
      for m in range(modes)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "derive.h", "group_expr.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "derive.h", "group_expr.h", "regex_dfa.h", "scan_direct_body.inc", "part_aggregate_body.inc",
            "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
@@ -252,6 +253,29 @@ def build_expr_filter_check(force=False):
         res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if res.returncode != 0:
             raise RuntimeError("hipcc (expr_filter_check) failed:\n%s" % res.stdout[-6000:])
+    os.replace(out + ".tmp", out)
+    return out
+
+
+def build_regex_fuzz(force=False):
+    """build/regex_fuzz: tools/regex_fuzz.cpp with csrc/regex_dfa.cpp alone -- the REGEXP_LIKE pattern compiler and the
+    host interpreter of its table -- under AddressSanitizer + UndefinedBehaviorSanitizer.  A stand-alone program: plain
+    C++, no device code, no library."""
+    out = os.path.join(ROOT, "build", "regex_fuzz")
+    srcs = [os.path.join(ROOT, "tools", "regex_fuzz.cpp"), os.path.join(CSRC, "regex_dfa.cpp")]
+    deps = srcs + [os.path.join(CSRC, "regex_dfa.h")]
+    if not force and os.path.exists(out) and all(os.path.getmtime(f) <= os.path.getmtime(out) for f in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    hipcc = _hipcc()
+    objs = [out + "_%d.o" % i for i in range(len(srcs))]
+    cmds = [[hipcc, "--offload-arch=" + ARCH, "-O1", "-g", "-std=c++17", "-I" + CSRC] + SAN_FLAGS + ["-c", s, "-o", o]
+            for s, o in zip(srcs, objs)]
+    cmds.append([hipcc, "--offload-arch=" + ARCH, "-fsanitize=address", "-fsanitize=undefined"] + objs + ["-o", out + ".tmp"])
+    for cmd in cmds:
+        res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if res.returncode != 0:
+            raise RuntimeError("hipcc (regex_fuzz) failed:\n%s" % res.stdout[-6000:])
     os.replace(out + ".tmp", out)
     return out
 

@@ -427,6 +427,31 @@ int pgpu_plan_leaf_kinds(pgpu_plan P, int64_t* counts) try {
   return 0;
 } PGPU_ABI_CATCH
 
+int pgpu_plan_regexp_stats(pgpu_plan P, int64_t* out4) try {
+  PGPU_ABI_GUARD;
+  if (!P || !out4) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  for (int k = 0; k < 4; ++k) out4[k] = P->regex_stats[k];
+  for (const auto& part : P->parts)
+    for (int k = 0; k < 4; ++k) out4[k] += part.plan->regex_stats[k];
+  return 0;
+} PGPU_ABI_CATCH
+
+int pgpu_regex_check(const char* pattern, int32_t* states, int32_t* classes, int64_t* table_bytes) try {
+  return regex_check(pattern, states, classes, table_bytes);  // host only: no ABI guard, no device
+} PGPU_ABI_CATCH
+
+int pgpu_regex_match_host(const char* pattern, const void* value, int64_t len, int32_t* matched) try {
+  if (!matched || len < 0 || (len > 0 && !value)) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  return regex_match_host(pattern, reinterpret_cast<const uint8_t*>(value), len, matched);
+} PGPU_ABI_CATCH
+
+int pgpu_table_regexp_dict_ids(pgpu_table t, int32_t column, const char* pattern, uint64_t* bitmap, int64_t words) try {
+  PGPU_ABI_GUARD;
+  if (!t || !bitmap || words < 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  DeviceGuard g(t->device);
+  return regex_global_ids(t, column, pattern, bitmap, words);
+} PGPU_ABI_CATCH
+
 int pgpu_plan_group_path(pgpu_plan P, int32_t* path) try {
   PGPU_ABI_GUARD;
   if (!P || !path) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");

@@ -700,4 +700,23 @@ int launch_read_clock(uint64_t* out, void* stream);
 int launch_gen_pack(const int32_t* pos, const int32_t* pos_to_id, int32_t num_docs, int32_t bits, uint32_t* fwd_out,
                     void* stream);
 
+// REGEXP_LIKE (k_regex.hip).  regex_match_dict_kernel: the DFA (regex_dfa.h: `cls` kRegexClsBytes bytes, `table`
+// table_entries = states x num_classes uint16 row offsets, at most kRegexMaxTableBytes; both 8-byte aligned) over the n values of a dictionary held as a blob --
+// value i is blob[offsets[i], offsets[i + 1]), the allocation padded to whole 8-byte words -- into ceil(n / 64) words
+// of `out`, bit i set when value i matches; the unused bits of the last word are 0.
+int launch_regex_match_dict(const uint8_t* cls, const uint16_t* table, int32_t table_entries, int32_t num_classes,
+                            int32_t start_row, int32_t eos_class, const uint8_t* blob, const uint32_t* offsets, int64_t n, uint64_t* out,
+                            void* stream);
+// regex_local_sets_kernel: one task per (segment, leaf) -- bit l of the task's words is global bit lut[l] (lut null:
+// lut_off + l) for l < card.  A task owns 2 * ceil(card / 64) uint32 words from out[dst].
+struct KRegexSetTask {
+  const int32_t* lut;
+  int32_t lut_off;
+  int32_t card;
+  int64_t dst;  // uint32 index into the output, even
+};
+inline int64_t regex_set_words(int32_t card) { return 2 * (((int64_t)card + 63) / 64); }
+int launch_regex_local_sets(const KRegexSetTask* tasks, int32_t num_tasks, int32_t max_card, const uint64_t* global_bits,
+                            uint32_t* out, void* stream);
+
 }  // namespace pgpu

@@ -634,6 +634,17 @@ struct pgpu_table_s {
   };
   std::vector<GlobalValues> gvalues;
   GlobalValues& col_gvalues(int c) { return gvalues[col_slot(c)]; }
+  // REGEXP_LIKE (rt_regex.cpp): a real STRING column's global dictionary on the device -- the values back to back and
+  // offsets[n + 1] -- of snapshot `version`, built on first use (under mu) and rebuilt when the dictionary has grown;
+  // device_bytes holds `bytes` for it.  bad_value: the first global dictId outside the limit REGEXP_LIKE sets on the
+  // values (ASCII, no \n, no \r), -1 when the snapshot has none; such a snapshot, or one of 2^31 bytes, is not uploaded.
+  struct DeviceDict {
+    uint64_t version = ~0ull;
+    std::shared_ptr<DevMem> blob, offsets;
+    int64_t n = 0, bytes = 0, bad_value = -1;
+    bool too_large = false;
+  };
+  std::vector<DeviceDict> ddicts;  // per real column, sized on first use
   hipStream_t stream = nullptr;
   std::vector<std::unique_ptr<Scratch>> scratch_pool;
   GenScratch gen;
@@ -856,6 +867,9 @@ struct pgpu_plan_s {
   int64_t post_exempt_docs = 0;           // aggregation-only: docs of segments answered from metadata / dictionary
   int segments_matched_filter = 0;
   int64_t leaf_kinds[kLeafKinds] = {};     // (segment, leaf) pairs of the scanned segments by kernel leaf kind
+  // REGEXP_LIKE leaves (pgpu_plan_regexp_stats): (segment, leaf) local sets built on the device, how many of them
+  // through an affine LUT, the device bytes of the leaves' dictionaries, the bytes of their DFA tables
+  int64_t regex_stats[4] = {};
   std::vector<uint8_t> seg_scanned;       // per plan segment: 1 = scanned (filter not folded to empty)
   int grid = 0;
   size_t lds_bytes = 0;

@@ -1,5 +1,6 @@
 // rt_decls.h -- prototypes of the functions and variables the runtime's sources share (see rt.h).
 #pragma once
+#include "regex_dfa.h"
 #include "rt.h"
 
 namespace pgpu {
@@ -32,6 +33,36 @@ int64_t lz4_decode_block(const uint8_t* src, int64_t n, uint8_t* dst, int64_t ca
 int decode_raw_forward_index(int type, const uint8_t* b, int64_t n, int32_t num_docs, int c, RawValues* out);
 int parse_raw_column(int type, const pgpu_column_buffers& cb, int32_t num_docs, int c, Column* col, RawValues* out);
 int64_t register_segment(pgpu_table_s* t, std::unique_ptr<Segment> seg_in);
+
+// rt_regex.cpp (PGPU_PRED_REGEXP_LIKE)
+// pgpu_regex_check / pgpu_regex_match_host: the pattern compiled, and the host interpreter of its table.
+int regex_check(const char* pattern, int32_t* states, int32_t* classes, int64_t* table_bytes);
+int regex_match_host(const char* pattern, const uint8_t* value, int64_t len, int32_t* matched);
+// The predicate's column must be a real STRING dictionary column, in every one of `segs`.
+int regex_check_column(const pgpu_table_s* t, const std::vector<Segment*>& segs, int col);
+// The pattern compiled, or the decline (PGPU_ERR_UNSUPPORTED, the message names REGEXP_LIKE and what was met).
+int regex_compile_pattern(const char* pattern, RegexDfa* d);
+// One REGEXP_LIKE leaf of a plan being made: its DFA (compiled once, when the query's columns are bound), what
+// regex_job_snapshot takes under the table mutex -- the column's dictionary on the device and the planned segments' LUTs,
+// of one snapshot, kept alive by the job -- and what regex_job_run computes from them outside it.
+struct RegexJob {
+  RegexDfa dfa;
+  int col = -1;
+  std::string name;
+  std::shared_ptr<DevMem> blob, offsets;
+  int64_t n = 0, dict_bytes = 0;
+  std::vector<KRegexSetTask> tasks;  // one per segment
+  std::vector<std::shared_ptr<DevMem>> luts;
+  int64_t out_words = 0;
+  int32_t max_card = 0, affine = 0;  // affine: the tasks that go through lut_off
+  std::vector<std::vector<uint32_t>> sets;  // per segment: the bitset over its local dictIds that match (a LEAF_SET's words)
+};
+int regex_job_snapshot(pgpu_table_s* t, const std::vector<Segment*>& segs, int col, RegexJob* job);
+// Both kernels on the calling thread's stream, in a pooled scratch's device memory, and one synchronisation; global_out
+// (may be null): ceil(n / 64) words, the matching global dictIds.
+int regex_job_run(pgpu_table_s* t, RegexJob* job, uint64_t* global_out);
+// The global dictIds of column col that match, computed on the device, as a bitmap (takes the table mutex itself).
+int regex_global_ids(pgpu_table_s* t, int col, const char* pattern, uint64_t* bitmap, int64_t words);
 
 // rt_plan.cpp
 int64_t hash_capacity(int64_t groups);

@@ -24,6 +24,9 @@ struct PlanCtx {
   std::vector<int> qcol_dc;    // ... and its DISTINCTCOUNT entry (pgpu_plan_s::dc; -1: none)
   std::vector<int> qcol_hist;  // ... and its histogram (pgpu_plan_s::hist; -1: none)
   std::vector<int> perm;       // order_leaves: evaluation position -> predicate
+  // per predicate, used by the REGEXP_LIKE ones: the DFA (bind_query_columns), the snapshot taken under the table
+  // mutex (plan_regex_leaves) and the LEAF_SET words per plan segment, computed on the device (run_regex_leaves)
+  std::vector<RegexJob> regex;
   double t_start = 0, tr[8] = {0};  // trace marks
   int ntr = 0;
   void mark() { if (trace_on() && ntr < 8) tr[ntr++] = now_us(); }
@@ -69,6 +72,12 @@ const Column& pred_column(const pgpu_plan_s* P, const Segment* s, const pgpu_que
   static const Column kNoColumn;
   return P->expr_leaf(l) ? kNoColumn : s->cols[q->predicates[l].column];
 }
+
+// True for a REGEXP_LIKE predicate (a LIKE arrives as one): RegexpLikePredicate.  Its leaf is always a scan over the
+// forward index -- without an FST index FilterOperatorUtils.getLeafFilterOperator (:65-72) takes a
+// ScanBasedFilterOperator whatever other index the column has -- and its evaluator is never always-true or
+// always-false (BaseDictionaryBasedPredicateEvaluator.java:26-41), so the leaf is never folded.
+bool regex_leaf(const pgpu_query* q, int l) { return q->predicates[l].type == PGPU_PRED_REGEXP_LIKE; }
 
 // Segment references (SegmentDataManager acquire): the table mutex is held only to take them here and, in
 // build_device_arrays, to build the lazily made LUT / value arrays and snapshot the global dictionary sizes -- the
@@ -167,6 +176,15 @@ int bind_query_columns(PlanCtx& cx) {
   const pgpu_query* q = cx.q;
   pgpu_plan_s* P = cx.P;
   const int ncols = (int)cx.t->names.size();
+  for (int i = 0; i < q->num_predicates; ++i) {  // REGEXP_LIKE: declined here, before anything is built for the plan
+    if (!regex_leaf(q, i)) continue;
+    const pgpu_predicate& pr = q->predicates[i];
+    if (pr.num_values != 1 || !pr.values || !pr.values[0])
+      return fail(PGPU_ERR_INVALID_ARGUMENT, "REGEXP_LIKE predicate %d takes one value, the pattern", i);
+    TRY(regex_check_column(cx.t, P->segs, pr.column));
+    if (cx.regex.empty()) cx.regex.resize(q->num_predicates);
+    TRY(regex_compile_pattern(pr.values[0], &cx.regex[i].dfa));  // the one compilation of the plan
+  }
   for (int i = 0; i < q->num_predicates; ++i)
     if (q->predicates[i].column >= ncols) { P->leaf_exprs.assign(q->num_predicates, ExprProg{}); break; }
   for (int i = 0; i < q->num_predicates; ++i) {
@@ -701,6 +719,31 @@ int plan_global_values(PlanCtx& cx) {
   return 0;
 }
 
+// (under the table mutex) REGEXP_LIKE leaves: the column's dictionary on the device and the planned segments' LUTs, of
+// the snapshot the rest of the plan is built on (rt_regex.cpp).  Only references are taken here.
+int plan_regex_leaves(PlanCtx& cx) {
+  const pgpu_query* q = cx.q;
+  for (int l = 0; l < q->num_predicates; ++l)
+    if (regex_leaf(q, l)) TRY(regex_job_snapshot(cx.t, cx.P->segs, q->predicates[l].column, &cx.regex[l]));
+  return 0;
+}
+
+// (the table mutex released) The DFA over the global dictionary and every planned segment's local bitset, on the
+// device: planners of other queries on the table are not kept waiting for the round trip.
+int run_regex_leaves(PlanCtx& cx) {
+  pgpu_plan_s* P = cx.P;
+  for (int l = 0; l < cx.q->num_predicates; ++l) {
+    if (!regex_leaf(cx.q, l)) continue;
+    RegexJob& job = cx.regex[l];
+    TRY(regex_job_run(cx.t, &job, nullptr));
+    P->regex_stats[0] += (int64_t)job.tasks.size();
+    P->regex_stats[1] += job.affine;
+    P->regex_stats[2] += job.dict_bytes;
+    P->regex_stats[3] += job.dfa.table_bytes();
+  }
+  return 0;
+}
+
 // Under the table mutex: the global dictionary sizes the key layout is built on, and every segment's device LUT /
 // value arrays of the referenced columns (built once per segment, rebuilt out of place when the global dictionary
 // grows) -- taken together, so the LUTs the plan points at map into exactly the key space it sizes.
@@ -728,6 +771,7 @@ int build_device_arrays(PlanCtx& cx) {
   TRY(plan_segment_arrays(cx));
   TRY(plan_global_values(cx));
   TRY(plan_hist_values(cx));
+  TRY(plan_regex_leaves(cx));
   P->docid_fwd = t->d_docid_fwd;
   P->docid_key = t->d_docid_key;
   P->docid_bits = t->docid_bits;
@@ -955,7 +999,8 @@ int prepare_translation(PlanCtx& cx) {
   cx.star_allowed = q->num_group_by > 0 && !(q->options & PGPU_OPT_NO_STAR_TREE) && P->stage_end.empty() &&
                     P->dc.empty() && P->pct.empty() && P->exprs.empty() && star_composites(P->ops, q, &cx.star_comps);
   // (a filter with an expression leaf never takes the star-tree: StarTreeUtils.java:255-258)
-  for (int l = 0; l < P->num_leaves; ++l) cx.star_allowed &= !P->expr_leaf(l);
+  // (nor does one with a REGEXP_LIKE: StarTreeUtils.java:266-274)
+  for (int l = 0; l < P->num_leaves; ++l) cx.star_allowed &= !P->expr_leaf(l) && !regex_leaf(q, l);
   // Aggregation-only over a match-all segment: COUNT-only is answered from metadata, MIN / MAX / DISTINCTCOUNT-only
   // from the dictionaries (AggregationPlanNode.java:165-183, isFitForDictionaryBasedPlan :233-246; every dictionary
   // value occurs in its segment, so the scan gives the same set) -- same values, numEntriesScannedPostFilter 0
@@ -1013,6 +1058,7 @@ void order_leaves(PlanCtx& cx) {
     for (int l = 0; l < P->num_leaves; ++l) {
       const pgpu_predicate& pr = q->predicates[l];
       if (P->expr_leaf(l)) { last.push_back(l); continue; }
+      if (regex_leaf(q, l)) { rest.push_back(l); continue; }  // a scan, whatever index the column has
       const bool eq_in = pr.type == PGPU_PRED_EQ || pr.type == PGPU_PRED_NOT_EQ || pr.type == PGPU_PRED_IN ||
                          pr.type == PGPU_PRED_NOT_IN;
       bool all_sorted = !P->segs.empty(), all_inv = !P->segs.empty() && eq_in && !P->no_inverted;
@@ -1038,8 +1084,9 @@ void order_leaves(PlanCtx& cx) {
 
 // ------------------------------------------------------------------------------------ per-segment translation
 // The predicates of segment s as leaves; returns the folded program's value over them.
-int translate_leaves(const PlanCtx& cx, const Segment* s, std::vector<LeafHost>& leaves, std::vector<Tri>& tri,
+int translate_leaves(const PlanCtx& cx, size_t seg_index, std::vector<LeafHost>& leaves, std::vector<Tri>& tri,
                      std::vector<int>& ids_scratch, Tri* whole) {
+  const Segment* s = cx.P->segs[seg_index];
   const pgpu_query* q = cx.q;
   const pgpu_plan_s* P = cx.P;
   for (int l = 0; l < P->num_leaves; ++l) {
@@ -1049,6 +1096,12 @@ int translate_leaves(const PlanCtx& cx, const Segment* s, std::vector<LeafHost>&
     if (P->expr_leaf(l)) {  // the raw DOUBLE evaluator over computed keys; never folded (ExpressionFilterOperator)
       translate_raw_predicate(PGPU_DOUBLE, q->predicates[l], cx.parsed[l], &lh);
       lh.kind = lh.kind == LEAF_RAW_IN ? LEAF_EXPR_IN : LEAF_EXPR_RANGE;
+      tri[l] = T_VAR;
+      continue;
+    }
+    if (regex_leaf(q, l)) {  // the device's bitset as it is: never folded, no index leaf, no sorted doc range
+      lh.kind = LEAF_SET;
+      lh.set = cx.regex[l].sets[seg_index];
       tri[l] = T_VAR;
       continue;
     }
@@ -1083,7 +1136,7 @@ int32_t segment_stats(const PlanCtx& cx, const Segment* s, const std::vector<Lea
     // FilterOperatorUtils.getLeafFilterOperator (:42-82): sorted column -> SortedIndexBasedFilterOperator;
     // RANGE with a range index -> RangeIndexBasedFilterOperator; other predicates with an inverted index ->
     // BitmapBasedFilterOperator; else a scan.  An expression: ExpressionFilterOperator (FilterPlanNode.java:179-186)
-    const int k = P->expr_leaf(l) ? SL_EXPR : tri[l] == T_NONE ? SL_EMPTY : tri[l] == T_ALL ? SL_ALL : col.sorted ? SL_SORTED :
+    const int k = P->expr_leaf(l) ? SL_EXPR : regex_leaf(q, l) ? SL_SCAN : tri[l] == T_NONE ? SL_EMPTY : tri[l] == T_ALL ? SL_ALL : col.sorted ? SL_SORTED :
                   (pr.type != PGPU_PRED_RANGE && col.inv) ? SL_BITMAP :
                   (pr.type == PGPU_PRED_RANGE && col.rng && leaves[l].kind == LEAF_RANGE) ? SL_RANGEIDX : SL_SCAN;
     sig = sig * kStatLeafKinds + (uint64_t)k;
@@ -1114,7 +1167,8 @@ void estimate_chunk_selectivity(const PlanCtx& cx, const Segment* s, const std::
     if (lh.kind == LEAF_BITMAP) f = lh.inv_frac;
     if (lh.kind == LEAF_RAW_RANGE || lh.kind == LEAF_RAW_IN) f = 0.5;  // no dictionary to estimate from
     if (lh.kind == LEAF_EXPR_RANGE || lh.kind == LEAF_EXPR_IN) f = 0.5;  // likewise
-    if (lh.kind == LEAF_SET) {
+    if (regex_leaf(cx.q, l)) f = 0.5;  // likewise: the host does not look at the bits
+    else if (lh.kind == LEAF_SET) {
       int64_t ones = 0;
       for (uint32_t w : lh.set) ones += __builtin_popcount(w);
       f = ones / card;
@@ -1334,7 +1388,7 @@ int plan_range(const PlanCtx& cx, size_t b, size_t e, Chunk& C) {
   for (size_t i = b; i < e; ++i) {
     Segment* s = P->segs[i];
     Tri whole;
-    TRY(translate_leaves(cx, s, leaves, tri, ids_scratch, &whole));
+    TRY(translate_leaves(cx, i, leaves, tri, ids_scratch, &whole));
     C.scanned.push_back(0);
     if (whole == T_NONE || s->num_docs == 0) continue;  // EmptyFilterOperator: the segment is not scanned
     C.scanned.back() = 1;
@@ -1598,7 +1652,7 @@ int run_streamed(PlanCtx& cx, int stream_chunks) {
     P->tile_bound += (s->num_docs + kTileDocs - 1) / kTileDocs;
     for (int l = 0; l < P->num_leaves; ++l) {
       const int ty = q->predicates[l].type;
-      if (ty == PGPU_PRED_IN || ty == PGPU_PRED_NOT_IN)
+      if (ty == PGPU_PRED_IN || ty == PGPU_PRED_NOT_IN || ty == PGPU_PRED_REGEXP_LIKE)
         P->set_words_bound += ((int64_t)pred_column(P, s, q, l).card + 31) / 32;
     }
   }
@@ -1715,6 +1769,7 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
   TRY(assign_slots(cx));
   note_groups_limit(cx);
   TRY(build_device_arrays(cx));
+  TRY(run_regex_leaves(cx));
   std::vector<int64_t> kspan;  // per key column: the global ids the filter admits
   TRY(restrict_key_space(cx, &kspan));
   TRY(layout_keys(cx, kspan));

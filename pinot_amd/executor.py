@@ -558,6 +558,19 @@ class GpuTable:
                                             len(docs), L.ptr(out, ctypes.c_int32)))
         return out[:len(docs)]
 
+    def regexp_dict_ids(self, column, pattern):
+        """pgpu_table_regexp_dict_ids: which values of STRING column `column`'s table-global dictionary match the
+        REGEXP_LIKE pattern, as the GPU computes it -- (a bool array indexed by global dictId (dictionary(column)), the
+        bitmap's 64-bit words as the library wrote them).  A pattern outside the subset, a column that is not STRING or a value outside the limit is an
+        UnsupportedQueryError (this reader hands the pattern to the C ABI as it is)."""
+        ci = self.index[column]
+        n = ctypes.c_int64()
+        L.check(self.lib.pgpu_table_dictionary_size(self.handle, ci, ctypes.byref(n)))
+        words = np.zeros(max((n.value + 63) // 64, 1), dtype=np.uint64)
+        raw = pattern if isinstance(pattern, bytes) else pattern.encode()
+        L.check(self.lib.pgpu_table_regexp_dict_ids(self.handle, ci, raw, L.ptr(words, ctypes.c_uint64), len(words)))
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n.value].astype(bool), words
+
     def filter_bitmap(self, handle, query, num_docs):
         q, keep = self.query_c(query)
         out = np.zeros(max((num_docs + 63) // 64, 1), dtype=np.uint64)
@@ -676,6 +689,12 @@ class Plan:
         out = np.zeros(len(L.LEAF_KIND_NAMES), dtype=np.int64)
         L.check(self.lib.pgpu_plan_leaf_kinds(self.handle, L.ptr(out, ctypes.c_int64)))
         return {n: int(v) for n, v in zip(L.LEAF_KIND_NAMES, out) if v}
+
+    def regexp_stats(self):
+        """pgpu_plan_regexp_stats: {"sets", "affine", "dict_bytes", "table_bytes"} of the plan's REGEXP_LIKE leaves."""
+        out = np.zeros(4, dtype=np.int64)
+        L.check(self.lib.pgpu_plan_regexp_stats(self.handle, L.ptr(out, ctypes.c_int64)))
+        return dict(zip(("sets", "affine", "dict_bytes", "table_bytes"), (int(v) for v in out)))
 
     def group_path(self):
         """The group-by path of the plan's scan (pgpu_plan_group_path): "lds", "global", "hash", "partitioned" or

@@ -19,8 +19,10 @@ import decimal
 from . import _lib as L
 
 EQ, NOT_EQ, IN, NOT_IN, RANGE = "EQ", "NOT_EQ", "IN", "NOT_IN", "RANGE"
+REGEXP_LIKE = "REGEXP_LIKE"  # RegexpLikePredicate; col LIKE 'p' is one too, after like_to_regexp_like
 UNBOUNDED = "*"  # RangePredicate.UNBOUNDED
-_PRED_CODE = {EQ: L.PRED_EQ, NOT_EQ: L.PRED_NOT_EQ, IN: L.PRED_IN, NOT_IN: L.PRED_NOT_IN, RANGE: L.PRED_RANGE}
+_PRED_CODE = {EQ: L.PRED_EQ, NOT_EQ: L.PRED_NOT_EQ, IN: L.PRED_IN, NOT_IN: L.PRED_NOT_IN, RANGE: L.PRED_RANGE,
+              REGEXP_LIKE: L.PRED_REGEXP_LIKE}
 AGG_FUNCTIONS = {"COUNT": L.AGG_COUNT, "SUM": L.AGG_SUM, "MIN": L.AGG_MIN, "MAX": L.AGG_MAX, "AVG": L.AGG_AVG,
                  "DISTINCTCOUNT": L.AGG_DISTINCTCOUNT}
 DEFAULT_NUM_GROUPS_LIMIT = 100000  # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT (:70)
@@ -710,6 +712,36 @@ def parse_expression(text):
     return tree
 
 
+_LIKE_ESCAPED = "\\^$.{}[]()*+?|<>-&/"  # RegexpPatternConverterUtils.java:29-31, in its order: the backslash first
+
+
+def like_to_regexp_like(like_pattern):
+    """RegexpPatternConverterUtils.likeToRegexpLike (:36-49): each regex metacharacter is backslash-escaped, then '_'
+    becomes '.' and '%' becomes '.*', and the result is wrapped in ^...$.  A LIKE wildcard cannot be escaped."""
+    out = like_pattern
+    for c in _LIKE_ESCAPED:
+        out = out.replace(c, "\\" + c)
+    return "^" + out.replace("_", ".").replace("%", ".*") + "$"
+
+
+def check_regexp_pattern(pattern):
+    """ValueError unless `pattern` is inside the subset of java.util.regex that REGEXP_LIKE accepts (include/pinotgpu.h,
+    PGPU_PRED_REGEXP_LIKE): the library's own compiler decides, on the host, so that this layer and a plan never differ.
+    Returns (states, byte classes, table bytes) of the pattern's DFA."""
+    if not isinstance(pattern, str):
+        raise ValueError("REGEXP_LIKE pattern %r is no string literal" % (pattern,))
+    try:
+        raw = pattern.encode("ascii")
+    except UnicodeEncodeError:
+        raise ValueError("REGEXP_LIKE pattern %r: a non-ASCII character in the pattern" % (pattern,))
+    if b"\0" in raw:
+        raise ValueError("REGEXP_LIKE pattern %r: a NUL character in the pattern" % (pattern,))
+    try:
+        return L.regex_check(raw)
+    except L.UnsupportedQueryError as e:
+        raise ValueError("REGEXP_LIKE pattern %r: %s" % (pattern, e))
+
+
 class Predicate:
     def __init__(self, ptype, column, values, lower_inclusive=True, upper_inclusive=True):
         self.type = ptype
@@ -737,6 +769,12 @@ class Predicate:
     @staticmethod
     def range(col, lower=UNBOUNDED, upper=UNBOUNDED, lower_inclusive=True, upper_inclusive=True):
         return Predicate(RANGE, col, [lower, upper], lower_inclusive, upper_inclusive)
+
+    @staticmethod
+    def regexp_like(col, pattern):
+        """REGEXP_LIKE(col, pattern) on a STRING dictionary column; ValueError for a pattern outside the subset."""
+        check_regexp_pattern(pattern)
+        return Predicate(REGEXP_LIKE, col, [pattern])
 
     def __repr__(self):
         return "Predicate(%s %s %r)" % (self.column, self.type, self.values)
@@ -1313,14 +1351,45 @@ class _Parser:
 
     def predicate(self):
         f = self.predicate_of()
+        if f.type != FilterContext.PREDICATE:  # col NOT LIKE 'p': NOT over the predicate
+            return f
         tree = self.exprs.get(f.predicate.column)
         # a time function on the left is LONG whatever its column is (a CASE's type waits for the column types: query_c)
         if tree is not None and tree[0] in ("timeconvert", "datetimeconvert"):
             f.predicate = long_predicate(f.predicate)
         return f
 
+    def pattern_literal(self, what):
+        if self.peek()[0] != "lit":
+            raise ValueError("%s: the pattern must be a literal, got %r" % (what, self.peek()[1]))
+        return self.take("lit")
+
+    def regexp_column(self, col, what):
+        if col in self.exprs:
+            raise ValueError("%s over the expression %s: the left-hand side must be a column" % (what, col))
+        return col
+
     def predicate_of(self):
+        if self.kw("REGEXP_LIKE") and self.peek(1) == ("op", "("):
+            self.take("id")
+            self.take("op", "(")
+            if self.peek()[0] != "id" or self.peek(1) != ("op", ","):
+                raise ValueError("REGEXP_LIKE: the first argument must be a column, not an expression or a literal")
+            col = self.take("id")
+            self.take("op", ",")
+            pattern = self.pattern_literal("REGEXP_LIKE(%s, ..)" % col)
+            self.take("op", ")")
+            return FilterContext.pred(Predicate.regexp_like(col, pattern))
         col = self.predicate_lhs()
+        if self.kw("LIKE") or (self.kw("NOT") and self.peek(1)[0] == "id" and self.peek(1)[1].upper() == "LIKE"):
+            negate = self.kw("NOT")
+            if negate:
+                self.take("id")
+            self.take("id")
+            self.regexp_column(col, "LIKE")
+            pattern = like_to_regexp_like(self.pattern_literal("%s LIKE" % col))
+            f = FilterContext.pred(Predicate.regexp_like(col, pattern))
+            return FilterContext.not_(f) if negate else f
         if self.kw("BETWEEN"):
             self.take("id")
             lo = self.rhs_literal(col)
