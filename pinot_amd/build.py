@@ -26,7 +26,7 @@ SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTI
      for m in range(modes)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "derive.h", "group_expr.h", "regex_dfa.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "expr_docs.h", "derive.h", "group_expr.h", "regex_dfa.h", "scan_direct_body.inc", "part_aggregate_body.inc",
            "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 

@@ -152,35 +152,29 @@ static_assert(PGPU_EXPR_COLUMN == pgpu::EXPR_COLUMN && PGPU_EXPR_LITERAL == pgpu
 
 // The function form of a program: add(div(a,b),2.5).
 static std::string expr_default_name(const pgpu_table_s* t, const pgpu::ExprProg& g) {
+  static const char* const kFn[] = {"", "", "add", "sub", "mult", "div", "equals", "not_equals", "greater_than",
+                                    "greater_than_or_equal", "less_than", "less_than_or_equal", "and", "or", "case", "",
+                                    "abs", "ceil", "floor", "sqrt", "mod", "ldiv"};
   std::vector<std::string> st;
   for (int k = 0; k < g.nops; ++k) {
-    const int op = g.code[k] & 0xFF, arg = g.code[k] >> 8;
+    const int op = g.code[k] & 0xFF, arg = g.code[k] >> 8, pops = pgpu::expr_op_pops(op);
+    if (pops < 0 || (int)st.size() < pops) break;  // (no compiled program)
     if (op == pgpu::EXPR_COLUMN) {
       st.push_back(t->names[g.col[arg]]);
     } else if (op == pgpu::EXPR_LITERAL) {
       char buf[40];
       snprintf(buf, sizeof buf, "%.17g", g.lit[arg]);
       st.push_back(buf);
-    } else if (op == pgpu::EXPR_SELECT) {  // (else, then, cond): case(cond,then,else)
-      const std::string cond = st.back(), then = st[st.size() - 2];
-      st.resize(st.size() - 2);
-      st.back() = "case(" + cond + "," + then + "," + st.back() + ")";
-    } else if (op >= pgpu::EXPR_ABS && op <= pgpu::EXPR_SQRT) {
-      static const char* const kMath[] = {"abs", "ceil", "floor", "sqrt"};
-      st.back() = std::string(kMath[op - pgpu::EXPR_ABS]) + "(" + st.back() + ")";
-    } else if (op == pgpu::EXPR_MOD || op == pgpu::EXPR_LDIV) {
-      const std::string b = st.back();
-      st.pop_back();
-      st.back() = std::string(op == pgpu::EXPR_MOD ? "mod(" : "ldiv(") + st.back() + "," + b + ")";
-    } else {
-      static const char* const kFn[] = {"add", "sub", "mult", "div", "equals", "not_equals", "greater_than",
-                                        "greater_than_or_equal", "less_than", "less_than_or_equal", "and", "or"};
-      const std::string b = st.back();
-      st.pop_back();
-      st.back() = std::string(kFn[op - pgpu::EXPR_ADD]) + "(" + st.back() + "," + b + ")";
+    } else {  // fn(operands in the order they were pushed); SELECT's are (else, then, cond): case(cond,then,else)
+      std::vector<std::string> a(st.end() - pops, st.end());
+      st.resize(st.size() - pops);
+      if (op == pgpu::EXPR_SELECT) std::reverse(a.begin(), a.end());
+      std::string s = std::string(kFn[op]) + "(" + a[0];
+      for (int i = 1; i < pops; ++i) s += "," + a[i];
+      st.push_back(s + ")");
     }
   }
-  return st.back();
+  return st.empty() ? std::string() : st.back();
 }
 
 // (under the table mutex) the operand rules of a registered program: real columns that are no STRING.  `what` names the
@@ -221,62 +215,63 @@ static bool same_ops(const std::vector<pgpu::ExprOpIn>& x, const std::vector<pgp
   return x.size() == y.size() && std::equal(x.begin(), x.end(), y.begin(), same);
 }
 
+// (under the table mutex) what the two registrations share: the program compiled and its operands checked; an identical
+// program of the same result type already in `list` answers with its place (*added false), else the program is appended
+// -- up to `limit` entries -- under the caller's name or its function form.  `what` names the kind in the messages.
+static int register_expr(pgpu_table_s* t, std::vector<pgpu_table_s::Expr>& list, int limit, const char* what,
+                         const pgpu_expr_op* ops, int32_t n, const char* name, int32_t type, int32_t* index, bool* added) {
+  pgpu_table_s::Expr e;
+  const pgpu::ExprOpIn* in = reinterpret_cast<const pgpu::ExprOpIn*>(ops);
+  if (const int rc = pgpu::expr_compile(in, n, &e.prog))
+    return fail(PGPU_ERR_INVALID_ARGUMENT, "%s: %s", what, pgpu::expr_error_text(rc));
+  TRY(check_expr_operands(t, e.prog, what));
+  e.ops = normalized_ops(in, n);
+  e.type = type;
+  *added = false;
+  for (size_t i = 0; i < list.size(); ++i)
+    if (list[i].type == type && same_ops(list[i].ops, e.ops)) {
+      *index = (int32_t)i;
+      return 0;
+    }
+  if ((int)list.size() >= limit) return fail(PGPU_ERR_INVALID_ARGUMENT, "%s: the table already has %d of them", what, limit);
+  e.name = name && *name ? std::string(name) : expr_default_name(t, e.prog);
+  list.push_back(std::move(e));
+  *index = (int32_t)list.size() - 1;
+  *added = true;
+  return 0;
+}
+
 int pgpu_table_add_group_expression(pgpu_table t, const pgpu_expr_op* ops, int32_t n, const char* name,
                                     int32_t result_type, int32_t* column) try {
   PGPU_ABI_GUARD;
   if (!t || !column) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   if (result_type < PGPU_INT || result_type > PGPU_DOUBLE)
     return fail(PGPU_ERR_INVALID_ARGUMENT, "GROUP BY expression: result type %d is none of INT, LONG, FLOAT, DOUBLE", result_type);
-  pgpu_table_s::GroupExpr e;
-  const pgpu::ExprOpIn* in = reinterpret_cast<const pgpu::ExprOpIn*>(ops);
-  if (const int rc = pgpu::expr_compile(in, n, &e.prog))
-    return fail(PGPU_ERR_INVALID_ARGUMENT, "GROUP BY expression: %s", pgpu::expr_error_text(rc));
   std::lock_guard<std::mutex> g(t->mu);
-  TRY(check_expr_operands(t, e.prog, "GROUP BY expression"));
-  e.ops = normalized_ops(in, n);
-  e.type = result_type;
-  for (size_t i = 0; i < t->gexprs.size(); ++i)
-    if (t->gexprs[i].type == e.type && same_ops(t->gexprs[i].ops, e.ops)) {
-      *column = kGroupExprBase + (int32_t)i;
-      return 0;
-    }
-  if ((int)t->gexprs.size() >= kMaxGroupExprs)
-    return fail(PGPU_ERR_INVALID_ARGUMENT, "GROUP BY expression: the table already has %d of them", kMaxGroupExprs);
-  e.name = name && *name ? std::string(name) : expr_default_name(t, e.prog);
-  // what the table keeps per column (pgpu_table_s::col_slot): type, global dictionary and version, value arrays
-  auto d = std::make_shared<Dict>();
-  d->type = result_type;
-  d->id = g_dict_ids.fetch_add(1);
-  t->types.push_back(result_type);
-  t->global.push_back(std::move(d));
-  t->global_version.push_back(0);
-  t->gvalues.emplace_back();
-  t->gexprs.push_back(std::move(e));
-  *column = kGroupExprBase + (int32_t)t->gexprs.size() - 1;
+  int32_t k;
+  bool added;
+  TRY(register_expr(t, t->gexprs, kMaxGroupExprs, "GROUP BY expression", ops, n, name, result_type, &k, &added));
+  if (added) {  // what the table keeps per column (pgpu_table_s::col_slot): type, global dictionary and version, value arrays
+    auto d = std::make_shared<Dict>();
+    d->type = result_type;
+    d->id = g_dict_ids.fetch_add(1);
+    t->types.push_back(result_type);
+    t->global.push_back(std::move(d));
+    t->global_version.push_back(0);
+    t->gvalues.emplace_back();
+  }
+  *column = kGroupExprBase + k;
   return 0;
 } PGPU_ABI_CATCH
 
 int pgpu_table_add_expression(pgpu_table t, const pgpu_expr_op* ops, int32_t n, const char* name, int32_t* column) try {
   PGPU_ABI_GUARD;
   if (!t || !column) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  const int ncols = (int)t->names.size();
-  pgpu_table_s::Expr e;
-  const pgpu::ExprOpIn* in = reinterpret_cast<const pgpu::ExprOpIn*>(ops);
-  if (const int rc = pgpu::expr_compile(in, n, &e.prog))
-    return fail(PGPU_ERR_INVALID_ARGUMENT, "expression: %s", pgpu::expr_error_text(rc));
   std::lock_guard<std::mutex> g(t->mu);
-  TRY(check_expr_operands(t, e.prog, "expression"));
-  e.ops = normalized_ops(in, n);
-  for (size_t i = 0; i < t->exprs.size(); ++i)
-    if (same_ops(t->exprs[i].ops, e.ops)) {
-      *column = ncols + (int32_t)i;
-      return 0;
-    }
-  if ((int)t->exprs.size() >= pgpu::kMaxTableExprs)
-    return fail(PGPU_ERR_INVALID_ARGUMENT, "expression: the table already has %d expressions", pgpu::kMaxTableExprs);
-  e.name = name && *name ? std::string(name) : expr_default_name(t, e.prog);
-  t->exprs.push_back(std::move(e));
-  *column = ncols + (int32_t)t->exprs.size() - 1;
+  int32_t e;
+  bool added;
+  TRY(register_expr(t, t->exprs, pgpu::kMaxTableExprs, "expression", ops, n, name, PGPU_DOUBLE, &e, &added));
+  *column = (int32_t)t->names.size() + e;
   return 0;
 } PGPU_ABI_CATCH
 

@@ -14,14 +14,13 @@
 namespace pgpu {
 
 struct KDeriveTask {
-  const uint32_t* fwd[kExprMaxCols];  // the operands' forward indexes (MSB-first fixed-bit, padded)
-  const double* dval[kExprMaxCols];   // ... and dictId -> double tables (ensure_values)
-  int32_t bits[kExprMaxCols];
-  int32_t card[kExprMaxCols];         // the operands' segment-local dictionary sizes (>= 1)
-  ExprProg prog;                      // (col[] is not read on the device)
+  ExprOperands ops;            // (expr_eval.h; dval: ensure_values)
+  int32_t card[kExprMaxCols];  // the operands' segment-local dictionary sizes (>= 1)
+  ExprProg prog;               // (col[] is not read on the device)
   int32_t num_docs;
   int32_t pad;
 };
+static_assert(__builtin_offsetof(KDeriveTask, prog) == 96 && sizeof(KDeriveTask) == 320, "the layout the kernels were built for");
 
 constexpr int kDeriveBlockDocs = 8192;  // docs per workgroup of the ids and the pack kernel: one forward-index tile
 

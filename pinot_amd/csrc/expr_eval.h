@@ -85,6 +85,40 @@ struct ExprProg {
   double lit[kExprMaxOps];
 };
 
+// The operand columns of a program in one segment as the device reads them, operand c being P.col[c]: the MSB-first
+// fixed-bit forward index (padded), the dictId -> double table and the dictIds' width.  The first member of the tasks of
+// both kernels that evaluate a program per doc (KExprLeafTask, internal.h; KDeriveTask, derive.h).
+struct ExprOperands {
+  const uint32_t* fwd[kExprMaxCols];
+  const double* dval[kExprMaxCols];
+  int32_t bits[kExprMaxCols];
+};
+// ... of program P in segment s (rt.h's Segment, whose d_val the caller has made: ensure_values; a template so that the
+// host check of the leaves' tasks, which has no device runtime, fills its tasks here too).  Unused operands stay null.
+template <typename Seg>
+inline ExprOperands expr_operands(const Seg& s, const ExprProg& P) {
+  ExprOperands o = {};
+  for (int c = 0; c < P.ncols && c < kExprMaxCols; ++c) {
+    const auto& col = s.cols[P.col[c]];
+    o.fwd[c] = col.d_fwd;
+    o.dval[c] = col.d_val;
+    o.bits[c] = col.bits;
+  }
+  return o;
+}
+
+// The stack shape of an op: how many entries it reads -- 0 a push (COLUMN, LITERAL), 1 ABS .. SQRT, 2 the binary ops,
+// 3 SELECT -- or -1 for a code that is no op (15 among them).  Every op leaves one entry, so the depth changes by
+// 1 - pops.  The one table of the host's walkers (expr_compile, expr_compared_columns, expr_walk_chains, and the C ABI's
+// default name); the device dispatches for itself (expr_stack_op).
+constexpr int expr_op_pops(int op) {
+  return op == EXPR_COLUMN || op == EXPR_LITERAL                               ? 0
+         : op >= EXPR_ABS && op <= EXPR_SQRT                                   ? 1
+         : (op >= EXPR_ADD && op <= EXPR_OR) || op == EXPR_MOD || op == EXPR_LDIV ? 2
+         : op == EXPR_SELECT                                                   ? 3
+                                                                               : -1;
+}
+
 enum ExprError : int {
   EXPR_OK = 0, EXPR_BAD_LENGTH, EXPR_BAD_OP, EXPR_UNDERFLOW, EXPR_TOO_DEEP, EXPR_TOO_MANY_COLUMNS, EXPR_LEFTOVER,
   EXPR_NO_COLUMN, EXPR_BAD_COLUMN, EXPR_BAD_TYPE, EXPR_BAD_DIVISOR, EXPR_BAD_DIVIDEND, EXPR_BAD_MATH_TYPE
@@ -121,11 +155,14 @@ inline int expr_compile(const ExprOpIn* ops, int n, ExprProg* out) {
   // `integral` likewise where entry d is an integral value (an LDIV's dividend; a column provisionally: its type is the
   // caller's to check, expr_integral_columns), `posint` where it is a positive integer literal of at most 2^53.
   uint32_t boolean = 0, integral = 0, posint = 0;
-  auto is_bool = [&](int from_top) { return (boolean >> (depth - 1 - from_top)) & 1u; };
   auto bit = [&](uint32_t m, int from_top) { return (m >> (depth - 1 - from_top)) & 1u; };
+  auto is_bool = [&](int from_top) { return bit(boolean, from_top); };
   for (int k = 0; k < n; ++k) {
-    const int op = ops[k].op;
+    const int op = ops[k].op, pops = expr_op_pops(op);
+    if (pops < 0) return EXPR_BAD_OP;
+    if (depth < pops) return EXPR_UNDERFLOW;
     int arg = 0;
+    bool r_bool = false, r_integral = false, r_posint = false;  // what the entry the op leaves is
     if (op == EXPR_COLUMN) {
       if (ops[k].column < 0) return EXPR_BAD_COLUMN;
       int c = 0;
@@ -135,56 +172,39 @@ inline int expr_compile(const ExprOpIn* ops, int n, ExprProg* out) {
         out->col[out->ncols++] = ops[k].column;
       }
       arg = c;
-      ++depth;
-      integral |= 1u << (depth - 1);
+      r_integral = true;
     } else if (op == EXPR_LITERAL) {
       const double l = ops[k].literal;
       out->lit[nlit] = l;
       arg = nlit++;
-      ++depth;
-      if (l >= 1.0 && l <= kExprExact && l == (double)(int64_t)l) posint |= 1u << (depth - 1);
+      r_posint = l >= 1.0 && l <= kExprExact && l == (double)(int64_t)l;
     } else if (op >= EXPR_ADD && op <= EXPR_LE) {  // (number, number) -> number, or -> boolean of a comparison
-      if (depth < 2) return EXPR_UNDERFLOW;
       if (is_bool(0) || is_bool(1)) return EXPR_BAD_TYPE;
       // x, LITERAL n, MULT over an integral x is the long product x * n (the literal on top, as LDIV's divisor stands);
       // LITERAL, x, MULT is arithmetic's double product, as the n-ary MULT of a caller starts.
-      const bool whole = op == EXPR_MULT && bit(integral, 1) && bit(posint, 0);
-      --depth;
-      if (op >= EXPR_EQ) boolean |= 1u << (depth - 1);
-      integral = (integral & ~(1u << (depth - 1))) | ((whole ? 1u : 0u) << (depth - 1));
-      posint &= ~(1u << (depth - 1));
-    } else if (op >= EXPR_ABS && op <= EXPR_SQRT) {  // number -> number
-      if (depth < 1) return EXPR_UNDERFLOW;
+      r_integral = op == EXPR_MULT && bit(integral, 1) && bit(posint, 0);
+      r_bool = op >= EXPR_EQ;
+    } else if (pops == 1) {  // ABS .. SQRT: number -> number
       if (is_bool(0)) return EXPR_BAD_MATH_TYPE;
-      integral &= ~(1u << (depth - 1));
-      posint &= ~(1u << (depth - 1));
     } else if (op == EXPR_MOD || op == EXPR_LDIV) {
-      if (depth < 2) return EXPR_UNDERFLOW;
       if (is_bool(0) || is_bool(1)) return EXPR_BAD_MATH_TYPE;
       if (op == EXPR_LDIV) {
         if (ops[k - 1].op != EXPR_LITERAL || !bit(posint, 0)) return EXPR_BAD_DIVISOR;
         if (!bit(integral, 1)) return EXPR_BAD_DIVIDEND;
       }
-      --depth;
-      integral = (integral & ~(1u << (depth - 1))) | ((op == EXPR_LDIV ? 1u : 0u) << (depth - 1));
-      posint &= ~(1u << (depth - 1));
+      r_integral = op == EXPR_LDIV;
     } else if (op == EXPR_AND || op == EXPR_OR) {
-      if (depth < 2) return EXPR_UNDERFLOW;
       if (!is_bool(0) || !is_bool(1)) return EXPR_BAD_TYPE;
-      --depth;
-    } else if (op == EXPR_SELECT) {
-      if (depth < 3) return EXPR_UNDERFLOW;
+      r_bool = true;
+    } else {  // EXPR_SELECT
       if (!is_bool(0) || is_bool(1) || is_bool(2)) return EXPR_BAD_TYPE;
-      depth -= 2;
-      integral &= ~(1u << (depth - 1));
-      posint &= ~(1u << (depth - 1));
-    } else {
-      return EXPR_BAD_OP;
     }
+    depth += 1 - pops;
     if (depth > kExprMaxDepth) return EXPR_TOO_DEEP;
-    boolean &= (1u << depth) - 1u;
-    integral &= (1u << depth) - 1u;
-    posint &= (1u << depth) - 1u;
+    const uint32_t top = 1u << (depth - 1), below = top - 1u;
+    boolean = (boolean & below) | (r_bool ? top : 0u);
+    integral = (integral & below) | (r_integral ? top : 0u);
+    posint = (posint & below) | (r_posint ? top : 0u);
     out->code[k] = op | (arg << 8);
   }
   if (depth != 1) return EXPR_LEFTOVER;
@@ -268,16 +288,14 @@ inline uint32_t expr_compared_columns(const ExprProg& P) {
   uint32_t st[kExprMaxDepth + 1] = {}, marked = 0;
   int depth = 0;
   for (int k = 0; k < P.nops; ++k) {
-    const int op = P.code[k] & 0xFF, arg = P.code[k] >> 8;
-    if (op == EXPR_COLUMN) st[depth++] = 1u << arg;
-    else if (op == EXPR_LITERAL) st[depth++] = 0;
-    else if (op == EXPR_SELECT) { depth -= 2; st[depth - 1] |= st[depth]; }  // else | then (the condition is no value)
-    else if (op >= EXPR_ABS && op <= EXPR_SQRT) st[depth - 1] = 0;  // (one operand: the depth stays)
-    else {
-      if (op >= EXPR_EQ && op <= EXPR_LE) marked |= st[depth - 1] | st[depth - 2];
-      --depth;
-      st[depth - 1] = 0;
-    }
+    const int op = P.code[k] & 0xFF, arg = P.code[k] >> 8, pops = expr_op_pops(op);
+    if (pops < 0 || depth < pops) break;  // (no compiled program)
+    uint32_t r = 0;  // the columns whose value the entry the op leaves is
+    if (op == EXPR_COLUMN) r = 1u << arg;
+    else if (op == EXPR_SELECT) r = st[depth - 3] | st[depth - 2];  // else | then (the condition is no value)
+    else if (op >= EXPR_EQ && op <= EXPR_LE) marked |= st[depth - 1] | st[depth - 2];
+    depth -= pops;
+    st[depth++] = r;
   }
   return marked;
 }
@@ -295,27 +313,26 @@ struct ExprChain {
 template <typename Visit>
 inline bool expr_walk_chains(const ExprProg& P, Visit&& visit) {
   ExprChain st[kExprMaxDepth + 1] = {};
-  const ExprChain none = {-1, 0, 0, 0, false};
   int depth = 0;
   for (int k = 0; k < P.nops; ++k) {
-    const int op = P.code[k] & 0xFF, arg = P.code[k] >> 8;
-    if (op == EXPR_COLUMN) { st[depth] = none; st[depth++].col = arg; }
-    else if (op == EXPR_LITERAL) st[depth++] = none;
-    else if (op >= EXPR_ABS && op <= EXPR_SQRT) st[depth - 1] = none;
-    else if (op == EXPR_SELECT) { depth -= 2; st[depth - 1] = none; }
-    else {
+    const int op = P.code[k] & 0xFF, arg = P.code[k] >> 8, pops = expr_op_pops(op);
+    if (pops < 0 || depth < pops) break;  // (no compiled program)
+    ExprChain r = {-1, 0, 0, 0, false};  // what the op leaves: no chain value, but for a column and a chain op
+    if (op == EXPR_COLUMN) {
+      r.col = arg;
+    } else if (op == EXPR_MULT || op == EXPR_LDIV) {
       const int prev = k > 0 ? P.code[k - 1] : 0;
       const double n = (prev & 0xFF) == EXPR_LITERAL ? P.lit[prev >> 8] : 0.0;
       const bool posint = n >= 1.0 && n <= kExprExact && n == (double)(int64_t)n;
-      --depth;
-      ExprChain& e = st[depth - 1];
-      if ((op == EXPR_MULT || op == EXPR_LDIV) && posint && e.col >= 0) {
+      ExprChain& e = st[depth - 2];
+      if (posint && e.col >= 0) {
         if (!visit(e, op, (int64_t)n)) return false;
         ++e.len;
-      } else {
-        e = none;
+        r = e;
       }
     }
+    depth -= pops;
+    st[depth++] = r;
   }
   return true;
 }
@@ -336,13 +353,15 @@ inline uint32_t expr_integral_columns(const ExprProg& P) {
 // least and greatest value of column c of P.col[] (a sorted dictionary's ends) and answers false for a column that
 // holds no integers (FLOAT / DOUBLE: its chain is plain double arithmetic) or no values.  Every constant is positive,
 // so a chain is monotone and its ends are those of its values; the arithmetic is exact (overflow is detected).
+inline bool expr_within_exact(int64_t lo, int64_t hi) {  // the integers [lo, hi] are their doubles
+  return lo >= -(int64_t)kExprExact && hi <= (int64_t)kExprExact;
+}
 template <typename Range>
 inline bool expr_chains_exact(const ExprProg& P, Range&& range) {
-  constexpr int64_t kExact = 1ll << 53;
   return expr_walk_chains(P, [&](ExprChain& e, int op, int64_t n) {
     if (e.len == 0) {
       e.live = range(e.col, &e.lo, &e.hi);
-      if (e.live && (e.lo < -kExact || e.hi > kExact)) return false;
+      if (e.live && !expr_within_exact(e.lo, e.hi)) return false;
     }
     if (!e.live) return true;
     if (op == EXPR_LDIV) {
@@ -351,7 +370,7 @@ inline bool expr_chains_exact(const ExprProg& P, Range&& range) {
     } else if (__builtin_mul_overflow(e.lo, n, &e.lo) || __builtin_mul_overflow(e.hi, n, &e.hi)) {
       return false;
     }
-    return e.lo >= -kExact && e.hi <= kExact;
+    return expr_within_exact(e.lo, e.hi);
   });
 }
 

@@ -10,27 +10,16 @@
 
 namespace pgpu {
 
-// One operand column of a segment as the kernel reads it: the fixed-bit forward index and the dictId -> double table.
-struct ExprLeafOperand {
-  const uint32_t* fwd;
-  const double* dval;
-  int32_t bits;
-};
-
 // The task of a leaf whose translated predicate is `raw` -- inclusive key bounds {lo, hi} (in == false) or sorted
-// distinct keys (in == true), translate_raw_predicate's forms -- over program `prog` with operands ops[0, prog.ncols)
-// of a segment of num_docs docs, writing the docbits region at word `dst`.  The keys of an IN leaf are appended to
-// *vals, whose first free index is vals_base + vals->size() in the plan's key array.
-inline KExprLeafTask make_expr_leaf_task(const ExprProg& prog, const ExprLeafOperand* ops, int32_t num_docs, bool in,
+// distinct keys (in == true), translate_raw_predicate's forms -- over program `prog` with operands `ops` (expr_operands,
+// expr_eval.h) of a segment of num_docs docs, writing the docbits region at word `dst`.  The keys of an IN leaf are
+// appended to *vals, whose first free index is vals_base + vals->size() in the plan's key array.
+inline KExprLeafTask make_expr_leaf_task(const ExprProg& prog, const ExprOperands& ops, int32_t num_docs, bool in,
                                          const std::vector<int64_t>& raw, int negate, int64_t dst, int64_t vals_base,
                                          std::vector<int64_t>* vals) {
   KExprLeafTask t;
   memset(&t, 0, sizeof t);
-  for (int c = 0; c < prog.ncols && c < kExprMaxCols; ++c) {
-    t.fwd[c] = ops[c].fwd;
-    t.dval[c] = ops[c].dval;
-    t.bits[c] = ops[c].bits;
-  }
+  t.ops = ops;
   t.prog = prog;
   t.dst = dst;
   t.num_docs = num_docs;

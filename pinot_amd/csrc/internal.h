@@ -552,14 +552,11 @@ struct KRawJob {
 };
 
 // One expression leaf of one segment (ExpressionFilterOperator: a predicate on a virtual column): per doc the
-// program's double over its operand columns -- dictId from the MSB-first fixed-bit forward index fwd[c] (bits[c] wide),
-// double from the segment's dictId -> double table dval[c] -- as its order-preserving key (expr_value_key), tested
-// against [lo, hi] (kind LEAF_RAW_RANGE) or the hi sorted keys expr_vals[lo, lo + hi) (LEAF_RAW_IN), negated for
+// program's double over its operand columns (ExprOperands, expr_eval.h) as its order-preserving key (expr_value_key),
+// tested against [lo, hi] (kind LEAF_RAW_RANGE) or the hi sorted keys expr_vals[lo, lo + hi) (LEAF_RAW_IN), negated for
 // NOT_EQ / NOT_IN, into the docbits words from `dst` in KRawTask's layout (the region's even word count written whole).
 struct KExprLeafTask {
-  const uint32_t* fwd[kExprMaxCols];
-  const double* dval[kExprMaxCols];
-  int32_t bits[kExprMaxCols];
+  ExprOperands ops;
   ExprProg prog;  // (col[] is not read on the device)
   int64_t dst;
   int64_t lo, hi;
@@ -568,6 +565,7 @@ struct KExprLeafTask {
   int32_t negate;
   int32_t pad;
 };
+static_assert(__builtin_offsetof(KExprLeafTask, prog) == 80 && sizeof(KExprLeafTask) == 336, "the layout the kernel was built for");
 // expr_leaf_bitmap_kernel work item: docs [doc0, doc0 + kExprLeafJobDocs) of task `task`, a quarter per wave.
 constexpr int kExprLeafJobDocs = 8192;
 struct KExprLeafJob {

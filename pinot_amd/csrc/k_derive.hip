@@ -3,7 +3,7 @@
 // then reads the result as any dictionary column.  An object of its own, so that no existing kernel is compiled
 // differently.
 #include "derive.h"
-#include "device.h"
+#include "expr_docs.h"
 
 namespace pgpu {
 
@@ -26,67 +26,36 @@ __global__ __launch_bounds__(256) void derive_candidates_kernel(const KDeriveTas
       const int64_t card = T.card[c];
       const int64_t id = rest % card;  // < card: inside the operand's dictId -> double table
       rest /= card;
-      v[c][0] = gp(T.dval[c])[id];
+      v[c][0] = gp(T.ops.dval[c])[id];
     }
   }
   expr_eval<1>(T.prog, v, out);
   keys[p] = expr_value_key(out[0]);
 }
 
-// Ids, the hot kernel: expr_leaf_bitmap_kernel's shape.  One lane per doc; a wave's 64 docs read adjacent forward-index
-// words of each operand; the dictId -> double gathers of all operands of four 64-doc steps are issued before the program
-// is interpreted.  The doc's key is then looked up in the sorted candidates (every key a doc can have is among them:
-// the candidates enumerate the operands' whole dictionaries) and the index stored, 4 bytes per doc, coalesced.  Marking:
-// a candidate's word is tested before it is written, so the three candidates of a CASE over a million docs take a
-// handful of plain stores of the same 1, not an atomic per doc; racing stores write the same value.
+// Ids, the hot kernel: one lane per doc, four 64-doc steps of a wave at a time (expr_eval_docs, expr_docs.h).  The
+// doc's key is then looked up in the sorted candidates (every key a doc can have is among them: the candidates enumerate
+// the operands' whole dictionaries) and the index stored, 4 bytes per doc, coalesced.  Marking: a candidate's word is
+// tested before it is written, so the three candidates of a CASE over a million docs take a handful of plain stores of
+// the same 1, not an atomic per doc; racing stores write the same value.
 __global__ __launch_bounds__(256) void derive_ids_kernel(const KDeriveTask T, const int64_t* __restrict__ cand,
                                                          const int32_t ncand, uint32_t* __restrict__ scratch,
                                                          uint32_t* __restrict__ used) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int32_t num_docs = T.num_docs;
-  const int nc = T.prog.ncols;
   gmem<int64_t>* __restrict__ set = gp(cand);
   constexpr int kWaveDocs = kDeriveBlockDocs / 4;
-  constexpr int kU = 4;  // 64-doc steps in flight per wave (expr_leaf_bitmap_kernel's reason)
+  constexpr int kU = 4;  // 64-doc steps in flight per wave
   for (int it = 0; it < kWaveDocs / (64 * kU); ++it) {
     const int64_t base = (int64_t)blockIdx.x * kDeriveBlockDocs + wave * kWaveDocs + it * (64 * kU);  // wave-uniform
     if (base >= num_docs) break;
     bool live[kU];
-    uint32_t id[kExprMaxCols][kU];
-    double v[kExprMaxCols][kU], out[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) live[u] = base + u * 64 + lane < num_docs;
-#pragma unroll
-    for (int c = 0; c < kExprMaxCols; ++c) {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        id[c][u] = 0;
-        v[c][u] = 0.0;
-      }
-      if (c < nc) {  // wave-uniform
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-          if (live[u]) id[c][u] = gather_id(T.fwd[c], T.bits[c], base + u * 64 + lane);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < kExprMaxCols; ++c)
-      if (c < nc) {
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-          if (live[u]) v[c][u] = gp(T.dval[c])[id[c][u]];
-      }
-    expr_eval<kU>(T.prog, v, out);
+    double out[kU];
+    expr_eval_docs<kU>(T.ops, T.prog, base, lane, num_docs, live, out);
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
       if (!live[u]) continue;
-      const int64_t key = expr_value_key(out[u]);
-      int a = 0, b = ncand;  // first candidate >= key
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (set[mid] < key) a = mid + 1;
-        else b = mid;
-      }
+      int a = key_lower_bound(set, ncand, expr_value_key(out[u]));
       if (a >= ncand) a = ncand - 1;  // (cannot happen: the key is a candidate; keeps every index inside `used`)
       scratch[base + u * 64 + lane] = (uint32_t)a;
       if (used[a] == 0u) used[a] = 1u;

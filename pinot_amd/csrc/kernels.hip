@@ -14,6 +14,7 @@
 // into an LDS-privatised dense group table (small key spaces), a global dense table (large) or a global open
 // addressing hash table (huge/overflowing key spaces).
 #include "device.h"
+#include "expr_docs.h"
 
 namespace pgpu {
 
@@ -732,11 +733,10 @@ int launch_raw_leaf_bitmaps(const KRawJob* jobs, int64_t num_jobs, const KRawTas
   return PGPU_HIP_OK(hipGetLastError());
 }
 
-// Expression filter leaves (WHERE price * qty > 1000): one lane per doc.  A wave's 64 docs read adjacent forward-index
-// words of each operand column; the dictId -> double gathers of all operands are issued before the program is
-// interpreted (expr_eval over a register stack), four 64-doc steps at a time; the result's key is tested as a raw
-// DOUBLE leaf's and the wave's ballot is its two docbits words.  Lanes past numDocs load nothing and vote 0.  The task
-// is read through the constant address space: program, pointers and bounds are scalar operands.
+// Expression filter leaves (WHERE price * qty > 1000): one lane per doc, four 64-doc steps of a wave at a time
+// (expr_eval_docs, expr_docs.h); the result's key is tested as a raw DOUBLE leaf's and the wave's ballot is its two
+// docbits words.  Lanes past numDocs vote 0.  The task is read through the constant address space: program, pointers
+// and bounds are scalar operands.
 __global__ __launch_bounds__(256) void expr_leaf_bitmap_kernel(const KExprLeafJob* __restrict__ jobs,
                                                                const KExprLeafTask* __restrict__ tasks,
                                                                const int64_t* __restrict__ expr_vals,
@@ -745,42 +745,17 @@ __global__ __launch_bounds__(256) void expr_leaf_bitmap_kernel(const KExprLeafJo
   cmem<KExprLeafTask>* T = cp(tasks + J.task);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int32_t num_docs = T->num_docs;
-  const int nc = T->prog.ncols;
   const int kind = T->kind, negate = T->negate;
   const int64_t lo = T->lo, hi = T->hi;
   gmem<int64_t>* __restrict__ set = gp(expr_vals) + (kind == LEAF_RAW_IN ? lo : 0);
   constexpr int kWaveDocs = kExprLeafJobDocs / 4;
-  constexpr int kU = 4;  // 64-doc steps in flight per wave: their loads are issued together (the chain dictId ->
-                         // double is two dependent loads per operand, and a step on its own waits for both)
+  constexpr int kU = 4;  // 64-doc steps in flight per wave
   for (int it = 0; it < kWaveDocs / (64 * kU); ++it) {
     const int64_t base = (int64_t)J.doc0 + wave * kWaveDocs + it * (64 * kU);  // wave-uniform
     if (base >= num_docs) break;
     bool live[kU];
-    uint32_t id[kExprMaxCols][kU];
-    double v[kExprMaxCols][kU], out[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) live[u] = base + u * 64 + lane < num_docs;
-#pragma unroll
-    for (int c = 0; c < kExprMaxCols; ++c) {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        id[c][u] = 0;
-        v[c][u] = 0.0;
-      }
-      if (c < nc) {  // wave-uniform
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-          if (live[u]) id[c][u] = gather_id(T->fwd[c], T->bits[c], base + u * 64 + lane);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < kExprMaxCols; ++c)
-      if (c < nc) {
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-          if (live[u]) v[c][u] = gp(T->dval[c])[id[c][u]];
-      }
-    expr_eval<kU>(T->prog, v, out);
+    double out[kU];
+    expr_eval_docs<kU>(T->ops, T->prog, base, lane, num_docs, live, out);
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
       const int64_t d0 = base + u * 64;
@@ -790,13 +765,7 @@ __global__ __launch_bounds__(256) void expr_leaf_bitmap_kernel(const KExprLeafJo
       if (kind == LEAF_RAW_RANGE) {
         hit = lo <= key && key <= hi;
       } else {
-        const int n = (int)hi;
-        int a = 0, b = n;  // first set key >= key
-        while (a < b) {
-          const int mid = (a + b) >> 1;
-          if (set[mid] < key) a = mid + 1;
-          else b = mid;
-        }
+        const int n = (int)hi, a = key_lower_bound(set, n, key);
         hit = a < n && set[a] == key;
       }
       if (negate) hit = !hit;

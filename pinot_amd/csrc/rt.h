@@ -596,17 +596,13 @@ struct pgpu_table_s {
     pgpu::ExprProg prog;
     std::vector<pgpu::ExprOpIn> ops;
     std::string name;
+    int32_t type = PGPU_DOUBLE;  // (what a group expression's result is read as; a virtual column's is a double)
   };
   std::vector<Expr> exprs;
   // Group-by expressions (pgpu_table_add_group_expression): expression k is column kGroupExprBase + k, a dictionary
   // column of type `type` whose per-segment form is Segment::derived[k].  The table keeps for it what it keeps per
   // real column: the global dictionary snapshot, its version and the global value arrays.  Under mu; never removed.
-  struct GroupExpr {
-    pgpu::ExprProg prog;
-    std::vector<pgpu::ExprOpIn> ops;
-    std::string name;
-    int32_t type = PGPU_DOUBLE;
-  };
+  using GroupExpr = Expr;
   std::vector<GroupExpr> gexprs;
   // Column index -> its slot in types / global / global_version / gvalues: real columns first, then the group
   // expressions (the vectors grow by one per registration; names keeps the real columns only).

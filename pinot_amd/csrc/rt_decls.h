@@ -24,6 +24,7 @@ int ensure_values(pgpu_table_s* t, Segment& s, int col, hipStream_t stream);
 int ensure_global_values(pgpu_table_s* t, int col, hipStream_t stream);
 int ensure_value_map(pgpu_table_s* t, Segment& s, int col);
 int ensure_docid(pgpu_table_s* t, int64_t n, hipStream_t stream);
+int check_expr_segment(const pgpu_table_s* t, const Segment& s, const ExprProg& prog, bool long_result, const char* what);
 int ensure_derived(pgpu_table_s* t, Segment& s, int col, hipStream_t stream);
 int segment_column(pgpu_table_s* t, Segment& s, int col, const Column** out);
 int table_reader_dict(pgpu_table_s* t, int col);

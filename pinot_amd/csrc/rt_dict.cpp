@@ -255,6 +255,42 @@ int ensure_docid(pgpu_table_s* t, int64_t n, hipStream_t stream) {
   return 0;
 }
 
+// Whether program `prog` may run over segment s: the rules every per-doc evaluation of an expression shares (aggregation
+// operands, filter leaves, derived columns), each a PGPU_ERR_UNSUPPORTED whose message starts with `what` ("expression",
+// "predicate 3: expression", "GROUP BY expression <name>").  In the order they are reported:
+//   1. no operand is a raw (no-dictionary) column;
+//   2. a LONG operand lies within +-2^53 where its value reaches a comparison as it is (expr_compared_columns: the VM
+//      compares doubles, the reference Long.compare) or, with long_result, where the program's result is read as a LONG (a
+//      group expression of that type) -- beyond, the double the VM reads is not the long;
+//   3. every integral chain (timeConvert, dateTimeConvert: x * n and the truncating x / n over an INT / LONG column) stays
+//      within +-2^53, run over the ends of the segment's sorted dictionaries (expr_chains_exact).
+int check_expr_segment(const pgpu_table_s* t, const Segment& s, const ExprProg& prog, bool long_result, const char* what) {
+  for (int c = 0; c < prog.ncols; ++c)
+    if (s.cols[prog.col[c]].raw)
+      return fail(PGPU_ERR_UNSUPPORTED, "%s over raw (no-dictionary) column %d", what, prog.col[c]);
+  // the least and greatest value of operand c, where it holds integers
+  auto range = [&](int c, int64_t* lo, int64_t* hi) {
+    const int col = prog.col[c];
+    const std::vector<int64_t>& iv = s.cols[col].dict.iv;
+    if ((t->types[col] != PGPU_INT && t->types[col] != PGPU_LONG) || iv.empty()) return false;
+    *lo = iv.front();
+    *hi = iv.back();
+    return true;
+  };
+  const uint32_t compared = expr_compared_columns(prog);
+  for (int c = 0; c < prog.ncols; ++c) {
+    int64_t lo, hi;
+    if (t->types[prog.col[c]] == PGPU_LONG && (long_result || ((compared >> c) & 1u)) && range(c, &lo, &hi) &&
+        !expr_within_exact(lo, hi))
+      return fail(PGPU_ERR_UNSUPPORTED, "%s compares or yields LONG column %d, whose values go beyond +-2^53", what,
+                  prog.col[c]);
+  }
+  if (!expr_chains_exact(prog, range))
+    return fail(PGPU_ERR_UNSUPPORTED, "%s: a time conversion or long division leaves +-2^53 over the values of segment "
+                "%lld, where the reference's long arithmetic is no longer a double's", what, (long long)s.handle);
+  return 0;
+}
+
 // The derived column of group expression `col` (kGroupExprBase + k) in segment s, built on first use (under the table
 // mutex, like the LUTs): candidates over the operands' local dictionaries, the docs' candidate ids, the used candidates
 // compacted into the dictionary on the host (group_expr.h), the forward index packed (k_derive.hip).  The column is an
@@ -265,51 +301,21 @@ int ensure_derived(pgpu_table_s* t, Segment& s, int col, hipStream_t stream) {
   if (k < 0 || k >= (int)t->gexprs.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "bad column %d", col);
   if (s.derived[k]) return 0;
   const pgpu_table_s::GroupExpr& ge = t->gexprs[k];
-  constexpr int64_t kExact = 1ll << 53;
-  const uint32_t compared = expr_compared_columns(ge.prog);
+  TRY(check_expr_segment(t, s, ge.prog, ge.type == PGPU_LONG, ("GROUP BY expression " + ge.name).c_str()));
   KDeriveTask T;
   memset(&T, 0, sizeof T);
   T.prog = ge.prog;
   T.num_docs = s.num_docs;
   int64_t product = s.num_docs > 0 ? 1 : 0;
   for (int c = 0; c < ge.prog.ncols; ++c) {
-    const int oc = ge.prog.col[c];
-    Column& o = s.cols[oc];
-    if (o.raw)
-      return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s over raw (no-dictionary) column %d", ge.name.c_str(), oc);
-    // A LONG operand past +-2^53 is not the double the evaluator reads: a LONG result would not be the reference's
-    // long, and a comparison not its Long.compare (check_compared_longs, rt_plan_create.cpp).
-    if (t->types[oc] == PGPU_LONG && (ge.type == PGPU_LONG || ((compared >> c) & 1u)) && !o.dict.iv.empty() &&
-        (o.dict.iv.front() < -kExact || o.dict.iv.back() > kExact))
-      return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s over LONG column %d, whose values go beyond +-2^53",
-                  ge.name.c_str(), oc);
-    product *= std::max<int64_t>(o.card, 1);
+    T.card[c] = std::max(s.cols[ge.prog.col[c]].card, 1);
+    product *= T.card[c];
     if (product > kGroupExprMaxProduct)
       return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s: the operands' dictionaries of segment %lld have more "
                   "than %lld combinations", ge.name.c_str(), (long long)s.handle, (long long)kGroupExprMaxProduct);
   }
-  {  // the integral chains (time conversions, long divisions) within +-2^53, as check_compared_longs has them for a plan
-    auto range = [&](int c, int64_t* lo, int64_t* hi) {
-      const int oc = ge.prog.col[c];
-      const std::vector<int64_t>& iv = s.cols[oc].dict.iv;
-      if ((t->types[oc] != PGPU_INT && t->types[oc] != PGPU_LONG) || iv.empty()) return false;
-      *lo = iv.front();
-      *hi = iv.back();
-      return true;
-    };
-    if (!expr_chains_exact(ge.prog, range))
-      return fail(PGPU_ERR_UNSUPPORTED, "GROUP BY expression %s: a time conversion or long division leaves +-2^53 over the "
-                  "values of segment %lld", ge.name.c_str(), (long long)s.handle);
-  }
-  for (int c = 0; c < ge.prog.ncols; ++c) {
-    const int oc = ge.prog.col[c];
-    TRY(ensure_values(t, s, oc, stream));
-    const Column& o = s.cols[oc];
-    T.fwd[c] = o.d_fwd;
-    T.dval[c] = o.d_val;
-    T.bits[c] = o.bits;
-    T.card[c] = std::max(o.card, 1);
-  }
+  for (int c = 0; c < ge.prog.ncols; ++c) TRY(ensure_values(t, s, ge.prog.col[c], stream));
+  T.ops = expr_operands(s, ge.prog);
   // PGPU_TRACE=derive: the build's three kernels between event pairs, one line per derived column on stderr
   static const bool timed = diag("derive");
   struct Events {

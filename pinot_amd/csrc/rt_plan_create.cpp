@@ -99,57 +99,24 @@ int acquire_segments(PlanCtx& cx, const int64_t* handles, int32_t nsegs) {
   return 0;
 }
 
-// A comparison inside a program (CASE WHEN a > 1 ..) compares doubles, where the reference compares INT / LONG operands
-// as integers: the same thing within +-2^53.  A LONG column that reaches a comparison as it is (expr_compared_columns)
-// is declined where a planned segment's dictionary (sorted: its ends) goes beyond.
-int check_compared_longs(PlanCtx& cx, const ExprProg& prog) {
-  constexpr int64_t kExact = 1ll << 53;
-  const uint32_t compared = expr_compared_columns(prog);
-  for (int c = 0; c < prog.ncols; ++c) {
-    const int col = prog.col[c];
-    if (!((compared >> c) & 1u) || cx.t->types[col] != PGPU_LONG) continue;
-    for (const Segment* s : cx.P->segs) {
-      const std::vector<int64_t>& iv = s->cols[col].dict.iv;
-      if (!iv.empty() && (iv.front() < -kExact || iv.back() > kExact))
-        return fail(PGPU_ERR_UNSUPPORTED, "expression compares LONG column %d, whose values go beyond +-2^53", col);
-    }
-  }
-  // The integral chains (timeConvert, dateTimeConvert: x * n and the truncating x / n over an INT / LONG column) are the
-  // reference's long arithmetic only while every value stays within +-2^53: run over the ends of each planned
-  // segment's dictionary (expr_chains_exact).
-  for (const Segment* s : cx.P->segs) {
-    auto range = [&](int c, int64_t* lo, int64_t* hi) {
-      const int col = prog.col[c];
-      const std::vector<int64_t>& iv = s->cols[col].dict.iv;
-      if ((cx.t->types[col] != PGPU_INT && cx.t->types[col] != PGPU_LONG) || iv.empty()) return false;
-      *lo = iv.front();
-      *hi = iv.back();
-      return true;
-    };
-    if (!expr_chains_exact(prog, range))
-      return fail(PGPU_ERR_UNSUPPORTED, "expression: a time conversion or long division leaves +-2^53 over the values of "
-                  "segment %lld, where the reference's long arithmetic is no longer a double's", (long long)s->handle);
-  }
+// The program of the table's virtual column vcol (an expression), copied under the table mutex (registrations append to
+// the table's list); `what` prefixes the message for a column that is none.
+int table_expr_prog(pgpu_table_s* t, int vcol, const char* what, ExprProg* out) {
+  std::lock_guard<std::mutex> g(t->mu);
+  const int e = vcol - (int)t->names.size();
+  if (e < 0 || e >= (int)t->exprs.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "%s: bad column %d", what, vcol);
+  *out = t->exprs[e].prog;
   return 0;
 }
 
-// The program of predicate i's virtual column vcol (ExpressionFilterOperator), copied under the table mutex as
-// plan_expr copies an aggregation's.  Operands are those of expression aggregations: dictionary columns (STRING and
-// virtual operands were refused when the expression was registered).
+// Predicate i is on the virtual column vcol (ExpressionFilterOperator): its program, admitted over every planned
+// segment (check_expr_segment).  Operands are those of expression aggregations: dictionary columns (STRING and virtual
+// operands were refused when the expression was registered).
 int bind_expr_leaf(PlanCtx& cx, int i, int vcol) {
-  pgpu_plan_s* P = cx.P;
-  ExprProg& prog = P->leaf_exprs[i];
-  {
-    std::lock_guard<std::mutex> g(cx.t->mu);
-    const int e = vcol - (int)cx.t->names.size();
-    if (e < 0 || e >= (int)cx.t->exprs.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "predicate %d: bad column %d", i, vcol);
-    prog = cx.t->exprs[e].prog;
-  }
-  for (int c = 0; c < prog.ncols; ++c)
-    for (const Segment* s : P->segs)
-      if (s->cols[prog.col[c]].raw)
-        return fail(PGPU_ERR_UNSUPPORTED, "predicate %d: expression over raw (no-dictionary) column %d", i, prog.col[c]);
-  TRY(check_compared_longs(cx, prog));
+  ExprProg& prog = cx.P->leaf_exprs[i];
+  const std::string what = "predicate " + std::to_string(i);
+  TRY(table_expr_prog(cx.t, vcol, what.c_str(), &prog));
+  for (const Segment* s : cx.P->segs) TRY(check_expr_segment(cx.t, *s, prog, false, (what + ": expression").c_str()));
   cx.any_raw_leaf = true;  // planned and launched as a raw-value leaf is: a docbits region per query
   return 0;
 }
@@ -322,28 +289,18 @@ int add_percentile_slot(pgpu_plan_s* P, int tcol, int32_t p_e4) {
 }
 
 // The plan's entry of the table's virtual column vcol (an expression), added on first use with its operand columns as
-// query columns (*out).  The program is copied under the table mutex (registrations append to the table's list).
+// query columns (*out), once it is admitted over every planned segment (check_expr_segment).
 int plan_expr(PlanCtx& cx, int vcol, int* out) {
   pgpu_plan_s* P = cx.P;
   for (size_t e = 0; e < P->exprs.size(); ++e)
     if (P->exprs[e].vcol == vcol) { *out = (int)e; return 0; }
   pgpu_plan_s::PlanExpr pe;
   pe.vcol = vcol;
-  {
-    std::lock_guard<std::mutex> g(cx.t->mu);
-    const int e = vcol - (int)cx.t->names.size();
-    if (e < 0 || e >= (int)cx.t->exprs.size()) return fail(PGPU_ERR_INVALID_ARGUMENT, "aggregation: bad column %d", vcol);
-    pe.prog = cx.t->exprs[e].prog;
-  }
+  TRY(table_expr_prog(cx.t, vcol, "aggregation", &pe.prog));
   if ((int)P->exprs.size() >= kMaxPlanExprs)
     return fail(PGPU_ERR_UNSUPPORTED, "more than %d distinct expression aggregations in one query", kMaxPlanExprs);
-  for (int c = 0; c < pe.prog.ncols; ++c) {
-    for (const Segment* s : P->segs)
-      if (s->cols[pe.prog.col[c]].raw)
-        return fail(PGPU_ERR_UNSUPPORTED, "expression over raw (no-dictionary) column %d", pe.prog.col[c]);
-    query_col(P, pe.prog.col[c]);
-  }
-  TRY(check_compared_longs(cx, pe.prog));
+  for (const Segment* s : P->segs) TRY(check_expr_segment(cx.t, *s, pe.prog, false, "expression"));
+  for (int c = 0; c < pe.prog.ncols; ++c) query_col(P, pe.prog.col[c]);
   P->exprs.push_back(pe);
   *out = (int)P->exprs.size() - 1;
   return 0;
@@ -1269,13 +1226,9 @@ void emit_raw_task(Chunk& C, const Segment* s, const Column& col, const LeafHost
 // (expr_leaf_bitmap_kernel, negation included) that the scan reads as a LEAF_BITMAP.
 void emit_expr_task(Chunk& C, const Segment* s, const ExprProg& prog, const LeafHost& lh, KLeaf& kl, int64_t field) {
   C.bit_fix.emplace_back(field, C.docbit_words);
-  ExprLeafOperand ops[kExprMaxCols];
-  for (int c = 0; c < prog.ncols; ++c) {
-    const Column& col = s->cols[prog.col[c]];
-    ops[c] = ExprLeafOperand{col.d_fwd, col.d_val, col.bits};  // (d_val: ensure_values, plan_segment_arrays)
-  }
-  C.expr_tasks.push_back(make_expr_leaf_task(prog, ops, s->num_docs, lh.kind == LEAF_EXPR_IN, lh.raw, lh.negate,
-                                             C.docbit_words, 0, &C.expr_vals));
+  // (the operands' d_val: ensure_values, plan_segment_arrays)
+  C.expr_tasks.push_back(make_expr_leaf_task(prog, expr_operands(*s, prog), s->num_docs, lh.kind == LEAF_EXPR_IN, lh.raw,
+                                             lh.negate, C.docbit_words, 0, &C.expr_vals));
   C.docbit_words += leaf_region_words(s->num_docs);
   kl.kind = LEAF_BITMAP;
   kl.negate = 0;

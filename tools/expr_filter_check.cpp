@@ -61,6 +61,16 @@ struct HostColumn {
   std::vector<uint32_t> ids;
 };
 
+// What expr_operands (expr_eval.h) reads of a segment: its columns' device arrays, here the host's.
+struct HostSegment {
+  struct Col {
+    const uint32_t* d_fwd = nullptr;
+    const double* d_val = nullptr;
+    int32_t bits = 0;
+  };
+  std::vector<Col> cols;
+};
+
 uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
 
 HostColumn make_column(int bits, const std::vector<double>& values, int32_t num_docs, uint64_t seed) {
@@ -115,7 +125,7 @@ void run_job(const KExprLeafJob& J, const std::vector<KExprLeafTask>& tasks, con
           if (doc >= T.num_docs) continue;
           seen[(size_t)doc]++;
           double v[kExprMaxCols][1] = {{0.0}, {0.0}, {0.0}, {0.0}}, out[1];
-          for (int c = 0; c < T.prog.ncols; ++c) v[c][0] = T.dval[c][gather_id(T.fwd[c], T.bits[c], doc)];
+          for (int c = 0; c < T.prog.ncols; ++c) v[c][0] = T.ops.dval[c][gather_id(T.ops.fwd[c], T.ops.bits[c], doc)];
           expr_eval<1>(T.prog, v, out);
           const int64_t key = expr_value_key(out[0]);
           bool hit;
@@ -164,8 +174,11 @@ void check_tasks() {
                     make_column(11, v11, docs[s], 37 + s)});
   }
   for (size_t s = 0; s < cols.size(); ++s) {
-    ExprLeafOperand o[kExprMaxCols] = {};
-    for (int c = 0; c < 3; ++c) o[c] = ExprLeafOperand{cols[s][(size_t)c].fwd.data(), cols[s][(size_t)c].dval.data(), cols[s][(size_t)c].bits};
+    HostSegment seg;  // the program's operands are its columns 7, 2 and 9, filled as the planner fills a task's
+    seg.cols.resize(10);
+    for (int c = 0; c < 3; ++c)
+      seg.cols[(size_t)prog.col[c]] = {cols[s][(size_t)c].fwd.data(), cols[s][(size_t)c].dval.data(), cols[s][(size_t)c].bits};
+    const ExprOperands o = expr_operands(seg, prog);
     const bool in = s % 2 == 1;
     const std::vector<int64_t> raw = in ? std::vector<int64_t>{expr_value_key(-0.0), expr_value_key(0.0), expr_value_key(1.5)}
                                         : std::vector<int64_t>{expr_value_key(-1.0), expr_value_key(1e300)};
@@ -173,7 +186,8 @@ void check_tasks() {
     tasks.push_back(make_expr_leaf_task(prog, o, docs[s], in, raw, (int)(s % 3 == 0), words, 0, &vals));
     const KExprLeafTask& t = tasks.back();
     CHECK(t.num_docs == docs[s] && t.dst == words && t.negate == (s % 3 == 0));
-    CHECK(t.fwd[2] == o[2].fwd && t.dval[1] == o[1].dval && t.bits[0] == 1 && t.bits[2] == 11 && t.fwd[3] == nullptr);
+    CHECK(t.ops.fwd[2] == cols[s][2].fwd.data() && t.ops.dval[1] == cols[s][1].dval.data() && t.ops.bits[0] == 1 &&
+          t.ops.bits[2] == 11 && t.ops.fwd[3] == nullptr);
     if (in) CHECK(t.kind == LEAF_RAW_IN && t.lo == (int64_t)before && t.hi == 3 && vals.size() == before + 3);
     else CHECK(t.kind == LEAF_RAW_RANGE && t.lo == raw[0] && t.hi == raw[1] && vals.size() == before);
     words += leaf_region_words(docs[s]);
@@ -208,7 +222,7 @@ void check_tasks() {
       CHECK(((docbits[(size_t)(t.dst + (d >> 5))] >> (d & 31)) & 1u) == 0u);
   }
   // an empty range (no bounds) matches nothing
-  ExprLeafOperand o[kExprMaxCols] = {};
+  const ExprOperands o = {};
   std::vector<int64_t> none;
   const KExprLeafTask e = make_expr_leaf_task(prog, o, 5, false, {1, 0}, 0, 0, 0, &none);
   CHECK(e.lo > e.hi && none.empty());
