@@ -573,6 +573,26 @@ int pgpu_plan_cancel(pgpu_plan plan);
  * RAW_RANGE, RAW_IN, BITDIR (inverted-index containers read in place)). */
 int pgpu_plan_leaf_kinds(pgpu_plan plan, int64_t* counts);
 
+/* Byte-code sketches of wide filter columns.  When a segment is pinned (or generated), every dictionary-encoded,
+ * fixed-bit, unsorted column of at least min_bits bits gets a second forward index of one byte per doc: a code that is
+ * monotone in the dictId, where up to 127 of the segment's most frequent dictIds have a code of their own and the
+ * dictIds between them share interval codes.  The sketch is kept if the docs of those 127 dictIds are at least
+ * min_cover of the segment's.  A plan then scans the 8-bit codes instead of the dictIds for the predicates the codes
+ * answer exactly -- an equality or IN on frequent values, a range that ends on code boundaries -- per (segment,
+ * column), and only if they answer every scan leaf of the query on that column; results and statistics are the same
+ * bit for bit.  Defaults: on, min_bits 12, min_cover 1/8.  pgpu_table_set_filter_sketch: min_bits 0 switches sketches
+ * off for segments pinned afterwards and for planning (sketches already built stay pinned, unused); like
+ * pgpu_table_set_config it applies to plans made afterwards and clears the compiled-plan cache.
+ * pgpu_segment_sketch_info: *ncodes 0 = the column has no sketch; else its codes, the docs whose dictId has a code
+ * of its own, the device bytes of the code bytes (counted in pgpu_table_device_bytes) and, where cap > 0, the first
+ * min(cap, ncodes + 1) entries of first_id (code c holds the dictIds [first_id[c], first_id[c + 1]); first_id[ncodes]
+ * is the cardinality).  pgpu_plan_sketch_leaves: the plan's (scanned segment, scan leaf) pairs on sketched columns
+ * that read the sketch, and those that stayed on the dictIds. */
+int pgpu_table_set_filter_sketch(pgpu_table table, int32_t min_bits, double min_cover);
+int pgpu_segment_sketch_info(pgpu_table table, int64_t segment_handle, int32_t column, int32_t* ncodes,
+                             int64_t* singleton_docs, int64_t* bytes, int32_t* first_id_out, int32_t cap);
+int pgpu_plan_sketch_leaves(pgpu_plan plan, int64_t* pairs_using_sketch, int64_t* pairs_declined);
+
 /* Diagnostics of PGPU_PRED_REGEXP_LIKE.  pgpu_regex_check compiles the pattern only: PGPU_OK with the DFA's states, byte
  * classes and table bytes (each pointer may be NULL), or the decline with its message.  pgpu_regex_match_host runs the
  * host interpreter of the same table over value[0, len) (*matched 0 / 1).  pgpu_table_regexp_dict_ids returns the

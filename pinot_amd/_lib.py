@@ -238,6 +238,9 @@ _PROTOS = {
                                          ctypes.POINTER(c_voidp)]),
     "pgpu_plan_layout": (c_int, [c_voidp, c_i32p, c_i64p, c_i32p]),
     "pgpu_plan_leaf_kinds": (c_int, [c_voidp, c_i64p]),
+    "pgpu_table_set_filter_sketch": (c_int, [c_voidp, c_i32, ctypes.c_double]),
+    "pgpu_segment_sketch_info": (c_int, [c_voidp, c_i64, c_i32, c_i32p, c_i64p, c_i64p, c_i32p, c_i32]),
+    "pgpu_plan_sketch_leaves": (c_int, [c_voidp, c_i64p, c_i64p]),
     "pgpu_plan_group_path": (c_int, [c_voidp, c_i32p]),
     "pgpu_plan_regexp_stats": (c_int, [c_voidp, c_i64p]),
     "pgpu_regex_check": (c_int, [ctypes.c_char_p, c_i32p, c_i32p, c_i64p]),

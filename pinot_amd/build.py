@@ -14,19 +14,19 @@ LIB_PATH = os.path.join(HERE, "libpinotgpu.so")
 # the host runtime (rt.h): rt_* (core, dictionaries, planning, execution, finalize, numGroupsLimit / plan cache)
 # and the C ABI
 RUNTIME = ["rt_core", "rt_dict", "rt_plan", "rt_plan_create", "rt_exec", "rt_finalize", "rt_groups", "rt_regex",
-           "abi_table", "abi_plan", "abi_combine", "abi_result"]
+           "rt_sketch", "abi_table", "abi_plan", "abi_combine", "abi_result"]
 SOURCES = [("kernels.hip", [], "kernels")] + [(n + ".cpp", [], n) for n in RUNTIME] + [("startree.cpp", [], "startree"),
            ("filter_stats.cpp", [], "filter_stats"), ("range_index.cpp", [], "range_index"), ("comm.cpp", [], "comm"), ("server_response.cpp", [], "server_response"),
            ("k_partition.hip", [], "k_partition"), ("k_partition_fx.hip", [], "k_partition_fx"),
            ("k_hashfinal.hip", [], "k_hashfinal"), ("k_derive.hip", [], "k_derive"),
-           ("regex_dfa.cpp", [], "regex_dfa"), ("k_regex.hip", [], "k_regex")] + \
+           ("regex_dfa.cpp", [], "regex_dfa"), ("k_regex.hip", [], "k_regex"), ("k_sketch.hip", [], "k_sketch")] + \
     [("k_%s.hip" % k, ["-DPGPU_FAMILY=%d" % f, "-DPGPU_MODE=%d" % m], "k_%s%s_%d" % (k, ("", "_fx", "_dc", "_hist", "_expr")[f], m))
      for k, f, modes in (("direct", 0, 3), ("startree", 0, 3), ("direct", 1, 3), ("startree", 1, 3), ("direct", 2, 2),
                          ("direct", 3, 2), ("direct", 4, 3))
      for m in range(modes)]
 HEADERS = ["internal.h", "device.h", "scan_direct.h", "host_common.h", "startree_kernels.h",
            "partition.h", "filter_stats.h", "host_result.h", "comm.h", "range_index.h", "rt.h",
-           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "expr_docs.h", "derive.h", "group_expr.h", "regex_dfa.h", "scan_direct_body.inc", "part_aggregate_body.inc",
+           "rt_decls.h", "tile_split.h", "fx_sum.h", "key_range.h", "expr_eval.h", "expr_leaf.h", "expr_docs.h", "derive.h", "group_expr.h", "regex_dfa.h", "col_sketch.h", "scan_direct_body.inc", "part_aggregate_body.inc",
            "part_hash_aggregate_body.inc"]
 ARCH = os.environ.get("PGPU_OFFLOAD_ARCH", "gfx950")
 
@@ -190,6 +190,11 @@ AGREE_CHECK_PATH = os.path.join(ROOT, "build", "fx_agree_check")
 def build_tile_split_check(force=False):
     """The scan's tile split against its LEAP2 LDS reservation (tile_split.h)."""
     return _build_header_check("tile_split_check", "tile_split_check.cpp", "tile_split.h", force)
+
+
+def build_col_sketch_check(force=False):
+    """The code assignment and the exactness tests of the filter columns' byte-code sketches (col_sketch.h)."""
+    return _build_header_check("col_sketch_check", "col_sketch_check.cpp", "col_sketch.h", force)
 
 
 def build_fx_sum_check(force=False):

@@ -420,6 +420,16 @@ int pgpu_generate_segment(pgpu_table t, const pgpu_gen_column* gc, int32_t ncols
       return fail(PGPU_ERR_DEVICE, "gen pack launch failed");
     HIP_TRY(hipStreamSynchronize(st));  // pos_to_id is reused by the next column
   }
+  {  // byte-code sketches of the wide filter columns, as pgpu_pin_segment builds them (rt_sketch.cpp)
+    SketchBuild sketches;
+    int rc = sketch_begin(t, seg.get(), st, &sketches);
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(PGPU_ERR_DEVICE, "sketch histogram failed");
+    if (!rc) rc = sketch_finish(t, seg.get(), st, &sketches);
+    if (rc) {
+      account_unpin(t, seg.get());
+      return rc;
+    }
+  }
   std::lock_guard<std::mutex> lk(t->mu);
   *handle = register_segment(t, std::move(seg));
   return 0;

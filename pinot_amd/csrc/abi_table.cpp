@@ -428,6 +428,12 @@ int pgpu_pin_segment(pgpu_table t, const pgpu_segment_desc* d, int64_t* handle) 
         return fail(PGPU_ERR_DEVICE, "forward-index check launch failed: %s", hipGetErrorString(hipGetLastError()));
     HIP_TRY(hipMemcpyAsync(hmax.data(), dmax.p, check.size() * 4, hipMemcpyDeviceToHost, t->stream));
   }
+  // byte-code sketches of the wide filter columns (rt_sketch.cpp): their doc histograms ride on this synchronize
+  SketchBuild sketches;
+  if (const int rc = sketch_begin(t, seg.get(), t->stream, &sketches)) {
+    account_unpin(t, seg.get());
+    return rc;
+  }
   HIP_TRY(hipStreamSynchronize(t->stream));
   for (size_t i = 0; i < check.size(); ++i)
     if ((int64_t)hmax[i] >= seg->cols[check[i]].card) {
@@ -435,6 +441,10 @@ int pgpu_pin_segment(pgpu_table t, const pgpu_segment_desc* d, int64_t* handle) 
       return fail(PGPU_ERR_INVALID_ARGUMENT, "column %d: forward index holds dictId %u, cardinality is %d", check[i],
                   hmax[i], seg->cols[check[i]].card);
     }
+  if (const int rc = sketch_finish(t, seg.get(), t->stream, &sketches)) {
+    account_unpin(t, seg.get());
+    return rc;
+  }
   std::lock_guard<std::mutex> lk(t->mu);
   if (any_raw) TRY(ensure_docid(t, d->num_docs, t->stream));
   *handle = register_segment(t, std::move(seg));

@@ -323,8 +323,10 @@ __device__ __forceinline__ uint32_t raw_group_mask(int kind, int64_t lo, int64_t
   return m;
 }
 
+// (KLeaf.fwd: the leaf scans the column's byte-code sketch instead of its dictIds)
 __device__ __forceinline__ uint32_t leaf_mask(KLeafC& L, KColC& C, int64_t group) {
-  return leaf_eval(L.kind, L.negate, L.lo, L.span, L.set, C.fwd, C.bits, group);
+  const uint32_t* lf = L.fwd;
+  return leaf_eval(L.kind, L.negate, L.lo, L.span, L.set, lf ? lf : C.fwd, lf ? L.bits : C.bits, group);
 }
 
 // ---------------------------------------------------------------------------------------------- helpers
@@ -403,8 +405,9 @@ __device__ __forceinline__ LeafReg load_leaf_reg(const KParams& p, const SegView
   LeafReg r;
   KLeafC& L = S.leaves[l];
   KColC& C = S.cols[p.leaf_col[l]];
-  r.fwd = C.fwd;
-  r.bits = C.bits;
+  const uint32_t* lf = L.fwd;  // the column's byte-code sketch, where the plan swapped the leaf to it
+  r.fwd = lf ? lf : C.fwd;
+  r.bits = lf ? L.bits : C.bits;
   r.kind = L.kind;
   r.negate = L.negate;
   r.lo = L.lo;

@@ -92,12 +92,18 @@ constexpr int kStatsReadBytes = kStatsReadWords * 8;
 
 // One predicate leaf evaluated against one segment: dictId in [lo, lo + span) (RANGE), bit set in `set`
 // (SET), docId in [lo, lo + span) (DOCRANGE), constant (ALL / NONE); `negate` flips the result (NOT_EQ / NOT_IN).
+// fwd (null: the column's own, KCol.fwd / bits): the forward index a RANGE / SET leaf scans instead -- the column's
+// byte-code sketch (col_sketch.h; bits = 8), with lo / span / set over its codes.  The column's KCol is untouched:
+// group-by and aggregation gathers of the same column keep reading the dictIds.
 struct KLeaf {
   int32_t kind;
   int32_t negate;
   uint32_t lo;
   uint32_t span;
   const uint32_t* set;
+  const uint32_t* fwd;
+  int32_t bits;
+  int32_t pad;
 };
 
 // One query column of one segment.  Dictionaries of consecutive values need no lookup: `lut` null = the segment's
@@ -577,6 +583,13 @@ struct KExprLeafJob {
 int launch_unpack(const uint32_t* fwd, int32_t bits, int64_t start, int64_t n, int32_t* out, void* stream);
 int launch_gather_ids(const uint32_t* fwd, int32_t bits, const int32_t* docs, int32_t n, int32_t* out, void* stream);
 int launch_fwd_max(const void* d_fwd, int64_t n, int32_t bits, unsigned int* d_out, void* stream);
+// Byte-code sketches (k_sketch.hip, col_sketch.h).  launch_sketch_hist: counts[id] += docs of dictId id, for id < card
+// (counts zeroed by the caller; a dictId >= card is counted nowhere).  launch_sketch_encode: out byte i = lut[dictId of
+// doc i] for i < num_docs, 0 up to the end of the last 32-doc group; `out` holds padded_fwd_words(num_docs, 8) words.
+int launch_sketch_hist(const uint32_t* fwd, int32_t bits, int32_t num_docs, int32_t card, uint32_t* counts,
+                       void* stream);
+int launch_sketch_encode(const uint32_t* fwd, int32_t bits, int32_t num_docs, int32_t card, const uint8_t* lut,
+                         uint32_t* out, void* stream);
 int launch_hash_unpack(uint64_t* table, const unsigned long long* hash_keys, int64_t cap, int32_t pack_slot,
                        int32_t shift, void* stream);
 int launch_table_init(uint64_t* table, const int32_t* slot_kind, int32_t num_slots, int64_t num_keys,

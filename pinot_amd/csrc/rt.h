@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/pinotgpu.h"
+#include "col_sketch.h"
 #include "comm.h"
 #include "filter_stats.h"
 #include "host_common.h"
@@ -383,6 +384,12 @@ struct Column {
   // docs, taken when they are decoded at pin time; of a dictionary on first use (fx_known, under the table mutex)
   pgpu::FxRange fx;
   bool fx_known = false;
+  // the column's byte-code sketch (col_sketch.h; rt_sketch.cpp builds it when the segment is pinned): one code byte
+  // per doc in an allocation of its own, laid out as an 8-bit forward index (sketch_bytes of it, in the table's
+  // device_bytes), and the host side of the assignment.  Null / ncodes 0: the column has none.  Immutable once built.
+  uint8_t* d_sketch = nullptr;
+  int64_t sketch_bytes = 0;
+  pgpu::ColSketch sketch;
 };
 
 // A pinned star-tree (pgpu_attach_startree): one device block holding the nodes, the star-tree documents'
@@ -437,6 +444,7 @@ struct Segment {
     for (auto& c : cols) {
       if (c.d_key) hipFree(c.d_key);
       if (c.d_val) hipFree(c.d_val);
+      if (c.d_sketch) hipFree(c.d_sketch);
     }
     for (auto& d : derived) {
       if (!d) continue;
@@ -586,6 +594,11 @@ struct pgpu_table_s {
   // executor settings (pgpu_table_set_config); plans copy them when they are made
   mutable std::mutex cfg_mu;
   pgpu_config cfg = default_config();
+  // byte-code sketches of filter columns (pgpu_table_set_filter_sketch; under cfg_mu): a dictionary column of at least
+  // sketch_min_bits bits gets one when pinned if its singleton codes cover sketch_min_cover of the docs; 0 bits = off,
+  // for segments pinned afterwards and for planning
+  int32_t sketch_min_bits = 12;
+  double sketch_min_cover = 0.125;
   std::vector<std::string> names;
   std::vector<int32_t> types;
   std::mutex mu;
@@ -866,7 +879,11 @@ struct pgpu_plan_s {
   // REGEXP_LIKE leaves (pgpu_plan_regexp_stats): (segment, leaf) local sets built on the device, how many of them
   // through an affine LUT, the device bytes of the leaves' dictionaries, the bytes of their DFA tables
   int64_t regex_stats[4] = {};
-  std::vector<uint8_t> seg_scanned;       // per plan segment: 1 = scanned (filter not folded to empty)
+  // byte-code sketches (col_sketch.h): the table's switch when the plan was made, and the (scanned segment, scan leaf)
+  // pairs on sketched columns that read the sketch [0] / stayed on the dictIds [1] (pgpu_plan_sketch_leaves)
+  bool sketch_on = true;
+  int64_t sketch_leaves[2] = {};
+  std::vector<uint8_t> seg_scanned;      // per plan segment: 1 = scanned (filter not folded to empty)
   int grid = 0;
   size_t lds_bytes = 0;
   ScanVariant variant = kScanSparse;      // the scan kernel's instance the plan launches (configure_scan_grid)

@@ -35,6 +35,22 @@ int decode_raw_forward_index(int type, const uint8_t* b, int64_t n, int32_t num_
 int parse_raw_column(int type, const pgpu_column_buffers& cb, int32_t num_docs, int c, Column* col, RawValues* out);
 int64_t register_segment(pgpu_table_s* t, std::unique_ptr<Segment> seg_in);
 
+// rt_sketch.cpp (byte-code sketches of filter columns, col_sketch.h): what the two steps of a segment's build share --
+// the qualifying columns, where each one's histogram starts in the count buffers, and the cover rule as read at the start.
+struct SketchBuild {
+  std::vector<int> cols;
+  std::vector<int64_t> off;
+  DevBuf d_counts;
+  std::vector<uint32_t> h_counts;
+  double min_cover = 0;
+  SketchBuild() = default;
+  SketchBuild(const SketchBuild&) = delete;
+  SketchBuild& operator=(const SketchBuild&) = delete;
+  ~SketchBuild() { d_counts.release(); }
+};
+int sketch_begin(pgpu_table_s* t, Segment* seg, hipStream_t st, SketchBuild* b);
+int sketch_finish(pgpu_table_s* t, Segment* seg, hipStream_t st, SketchBuild* b);
+
 // rt_regex.cpp (PGPU_PRED_REGEXP_LIKE)
 // pgpu_regex_check / pgpu_regex_match_host: the pattern compiled, and the host interpreter of its table.
 int regex_check(const char* pattern, int32_t* states, int32_t* classes, int64_t* table_bytes);

@@ -433,6 +433,7 @@ void account_unpin(pgpu_table_s* t, const Segment* s) {
   int64_t fwd_words = 0;
   for (const auto& c : s->cols) {
     if (c.inv) t->device_bytes -= c.inv->bytes;
+    t->device_bytes -= c.sketch_bytes;  // the byte-code sketch (rt_sketch.cpp)
     t->device_bytes -= (c.lut ? 4 * std::max(c.card, 1) : 0) +
                        (c.d_key ? 16 * (c.raw ? raw_padded_docs(s->num_docs) : std::max(c.card, 1)) : 0);
     if (!c.raw) fwd_words += (c.fwd_words + 63) & ~int64_t(63);

@@ -53,6 +53,7 @@ struct Chunk {
   std::vector<uint8_t> scanned;
   int64_t tiles = 0, entries = 0, matched = 0, sel_docs = 0, exempt = 0;
   int64_t leaf_kinds[kLeafKinds] = {};
+  int64_t sketch_leaves[2] = {};  // pgpu_plan_s::sketch_leaves
   double sel = 1.0;
   int rc = 0;
   std::string err;
@@ -1191,10 +1192,57 @@ bool fill_kcols(const PlanCtx& cx, size_t i, KCol* kc) {
 }
 
 // LEAF_SET: the bitset words, every leaf's 8-byte aligned; `field`: the chunk offset of the record's KLeaf::set.
-void emit_set_words(Chunk& C, const LeafHost& lh, int64_t field) {
+void emit_set_words(Chunk& C, const uint32_t* words, size_t n, int64_t field) {
   C.set_fix.emplace_back(field, (int64_t)C.set_words.size());
-  C.set_words.insert(C.set_words.end(), lh.set.begin(), lh.set.end());
+  C.set_words.insert(C.set_words.end(), words, words + n);
   if (C.set_words.size() & 1) C.set_words.push_back(0);
+}
+
+// A scan leaf as its column's byte-code sketch answers it (col_sketch.h): the code range of a LEAF_RANGE, the code set
+// of a LEAF_SET.
+struct SketchLeaf {
+  bool on_sketched = false;  // a RANGE / SET leaf on a column that has a sketch
+  bool exact = false;        // ... which the codes answer exactly
+  bool use = false;          // ... and so do they every such leaf of the query on that column in this segment
+  uint32_t lo = 0, span = 0;
+  uint32_t codes[kSketchSetWords] = {};
+};
+
+// Which leaves of segment s read their column's sketch instead of its dictIds.  Called after everything that is
+// decided from the dictId leaves (fold, index leaves, statistics, selectivity, instance): the swap changes the bytes
+// a leaf reads and nothing else.  All-or-nothing per column: with one leaf left on the dictIds both copies would be
+// read.  sk: per predicate; counts the pairs in C.sketch_leaves.
+void choose_sketch_leaves(const PlanCtx& cx, const Segment* s, const std::vector<LeafHost>& leaves,
+                          std::array<SketchLeaf, kMaxLeaves>& sk, Chunk& C) {
+  const pgpu_plan_s* P = cx.P;
+  const int nl = P->num_leaves;
+  for (SketchLeaf& x : sk) x = SketchLeaf();
+  if (!P->sketch_on || nl > kMaxLeaves) return;
+  const Column* lcol[kMaxLeaves] = {};
+  for (int l = 0; l < nl; ++l) {
+    const LeafHost& lh = leaves[l];
+    if ((lh.kind != LEAF_RANGE && lh.kind != LEAF_SET) || P->expr_leaf(l)) continue;
+    const Column& col = pred_column(P, s, cx.q, l);
+    if (!col.d_sketch || col.sketch.ncodes <= 0) continue;
+    lcol[l] = &col;
+    sk[l].on_sketched = true;
+    if (lh.kind == LEAF_RANGE) {
+      int a = 0, b = 0;
+      sk[l].exact = sketch_range_exact(col.sketch, lh.lo, (int64_t)lh.lo + lh.span, &a, &b);
+      sk[l].lo = (uint32_t)a;
+      sk[l].span = (uint32_t)(b - a);
+    } else {
+      sk[l].exact = (int64_t)lh.set.size() * 32 >= col.card && sketch_set_exact(col.sketch, lh.set.data(), sk[l].codes);
+    }
+  }
+  for (int l = 0; l < nl; ++l) {
+    if (!sk[l].on_sketched) continue;
+    bool all = true;
+    for (int m = 0; m < nl; ++m)
+      if (lcol[m] == lcol[l]) all &= sk[m].exact;
+    sk[l].use = all;
+    C.sketch_leaves[all ? 0 : 1]++;
+  }
 }
 
 // Raw-value leaf: evaluated per query into a docId bitmap region (raw_leaf_bitmap_kernel, negation included) that the
@@ -1306,6 +1354,8 @@ void emit_bitmap_tasks(Chunk& C, const Segment* s, const Column& col, const Leaf
 // kl_off: the byte offset of kl[0] in the chunk's records.
 void emit_leaves(const PlanCtx& cx, const Segment* s, const std::vector<LeafHost>& leaves, KLeaf* kl, int64_t kl_off,
                  Chunk& C) {
+  std::array<SketchLeaf, kMaxLeaves> sk;
+  choose_sketch_leaves(cx, s, leaves, sk, C);
   for (int k = 0; k < cx.P->num_leaves; ++k) {
     const LeafHost& lh = leaves[cx.perm[k]];
     const Column& col = pred_column(cx.P, s, cx.q, cx.perm[k]);
@@ -1315,7 +1365,19 @@ void emit_leaves(const PlanCtx& cx, const Segment* s, const std::vector<LeafHost
     kl[k].lo = lh.lo;
     kl[k].span = lh.span;
     kl[k].set = nullptr;
-    if (lh.kind == LEAF_SET) emit_set_words(C, lh, field);
+    const SketchLeaf* sl = cx.perm[k] < kMaxLeaves && sk[cx.perm[k]].use ? &sk[cx.perm[k]] : nullptr;
+    if (sl) {  // the leaf over the column's codes: the same docs match (negate carries over)
+      kl[k].fwd = reinterpret_cast<const uint32_t*>(col.d_sketch);
+      kl[k].bits = kSketchBits;
+      if (lh.kind == LEAF_RANGE) {
+        kl[k].lo = sl->lo;
+        kl[k].span = sl->span;
+      }
+    }
+    if (lh.kind == LEAF_SET) {
+      if (sl) emit_set_words(C, sl->codes, kSketchSetWords, field);
+      else emit_set_words(C, lh.set.data(), lh.set.size(), field);
+    }
     if (lh.kind == LEAF_RAW_RANGE || lh.kind == LEAF_RAW_IN) emit_raw_task(C, s, col, lh, kl[k], field);
     if (lh.kind == LEAF_EXPR_RANGE || lh.kind == LEAF_EXPR_IN)
       emit_expr_task(C, s, cx.P->leaf_exprs[cx.perm[k]], lh, kl[k], field);
@@ -1589,6 +1651,7 @@ void merge_chunk(pgpu_plan_s* P, Chunk& C, int64_t tile_shift) {
   P->scanned_entries_model += C.entries;
   P->post_exempt_docs += C.exempt;
   for (int k = 0; k < kLeafKinds; ++k) P->leaf_kinds[k] += C.leaf_kinds[k];
+  for (int k = 0; k < 2; ++k) P->sketch_leaves[k] += C.sketch_leaves[k];
   if (P->sel_docs == 0 && C.sel_docs) { P->sel_estimate = C.sel; P->sel_docs = C.sel_docs; }
 }
 
@@ -1708,6 +1771,10 @@ int plan_create_impl(pgpu_table_s* t, const int64_t* handles, int32_t nsegs, con
   PlanCtx cx{t, q, P, se};
   cx.t_start = trace_on() ? now_us() : 0;
   P->cfg = table_config(t);
+  {
+    std::lock_guard<std::mutex> g(t->cfg_mu);
+    P->sketch_on = t->sketch_min_bits > 0;
+  }
   // num_group_by == 0: aggregation-only (AggregationOperator, core/operator/query/AggregationOperator.java:58-95):
   // one accumulator row (key space G = 1), reduced per wave before any atomic.
   if (q->num_group_by < 0) return fail(PGPU_ERR_INVALID_ARGUMENT, "negative group-by count");

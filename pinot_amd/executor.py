@@ -261,6 +261,25 @@ class GpuTable:
         L.check(self.lib.pgpu_config_default(ctypes.byref(c)))
         L.check(self.lib.pgpu_table_set_config(self.handle, ctypes.byref(c)))
 
+    def set_filter_sketch(self, min_bits=12, min_cover=0.125):
+        """pgpu_table_set_filter_sketch: the byte-code sketches of wide filter columns.  Columns of at least min_bits
+        bits get one when a segment is pinned, kept if the 127 most frequent dictIds cover min_cover of its docs;
+        min_bits=0 switches them off for segments pinned afterwards and for planning."""
+        L.check(self.lib.pgpu_table_set_filter_sketch(self.handle, int(min_bits), float(min_cover)))
+
+    def segment_sketch_info(self, handle, column):
+        """pgpu_segment_sketch_info: None where the column of the pinned segment has no sketch, else {"ncodes",
+        "singleton_docs", "bytes", "first_id"} (first_id: ncodes + 1 dictIds, the last one the cardinality)."""
+        n, docs, nbytes = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        first = np.zeros(257, dtype=np.int32)
+        L.check(self.lib.pgpu_segment_sketch_info(self.handle, handle, self.index[column], ctypes.byref(n),
+                                                  ctypes.byref(docs), ctypes.byref(nbytes),
+                                                  L.ptr(first, ctypes.c_int32), len(first)))
+        if n.value == 0:
+            return None
+        return {"ncodes": n.value, "singleton_docs": docs.value, "bytes": nbytes.value,
+                "first_id": first[:n.value + 1].copy()}
+
     def close(self):
         if self.handle:
             self.lib.pgpu_table_destroy(self.handle)
@@ -689,6 +708,13 @@ class Plan:
         out = np.zeros(len(L.LEAF_KIND_NAMES), dtype=np.int64)
         L.check(self.lib.pgpu_plan_leaf_kinds(self.handle, L.ptr(out, ctypes.c_int64)))
         return {n: int(v) for n, v in zip(L.LEAF_KIND_NAMES, out) if v}
+
+    def sketch_leaves(self):
+        """pgpu_plan_sketch_leaves: (pairs using a sketch, pairs declined) -- the (scanned segment, scan leaf) pairs of
+        the plan on sketched columns that read the 8-bit codes / stayed on the dictIds."""
+        used, declined = ctypes.c_int64(), ctypes.c_int64()
+        L.check(self.lib.pgpu_plan_sketch_leaves(self.handle, ctypes.byref(used), ctypes.byref(declined)))
+        return used.value, declined.value
 
     def regexp_stats(self):
         """pgpu_plan_regexp_stats: {"sets", "affine", "dict_bytes", "table_bytes"} of the plan's REGEXP_LIKE leaves."""
